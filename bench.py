@@ -13,7 +13,14 @@ and the survivors of every launch travel to rank 0 as fixed-layout tensors (the 
 per-round gather, dist.gather_arrays) -- no other data-path collective.  configs[1] (500 images,
 one MI355X) follows as an extra key at N = 1.  The BA section runs configs[3] point-sharded.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only what the headline needs: set-up, `W` warm-up steps, `K` timed steps, the
+result line.  `--full` adds everything else the line used to carry: the oracle self-check of the
+timed store, configs[1], the dense-overlap regime, BA, SIFT, consolidation, the configs[4] slice,
+host post-processing and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (see dump_outputs()), so that two builds can be compared output for
+output; the inputs are seeded, identical from run to run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -41,6 +48,13 @@ CONFIG2_IMAGES = 2812                            # configs[2]: 3 952 266 pairs
 E2E_FRAMES = 128                                 # configs[4] slice of the default run (rendered 20 MP frames)
 MATCH_RATIO = 0.75
 MAX_DISTANCE = 270.0
+# --dump-outputs: every ordered pair's survivor count (a seeded sample of them beyond this many
+# pairs: 32 MB as float32) and the survivor lists of DUMP_PAIRS_PER_LAUNCH fixed ordered pairs in
+# each of DUMP_LAUNCHES launches spread evenly over the schedule (< 16 MB as query / train row +
+# metric)
+DUMP_PAIRS = 8000000
+DUMP_LAUNCHES = 32
+DUMP_PAIRS_PER_LAUNCH = 8
 
 
 def synth_descriptors(n_img, first, count, device, seed=1234):
@@ -90,10 +104,13 @@ def pair_schedule(n_img, rank, world, sub_batch):
     return launches, hi - lo
 
 
-def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, verify_pairs):
+def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, verify_pairs,
+                  dump=False, cpu_sample=False):
     """The matching half of the metric on an `n_img`-image survey: `warmup` untimed steps, then
     exactly `steps` timed ones between barriers (max over ranks).  Returns the figures of the
-    JSON line (seconds, pairs, survivor counts, the sweep's roofline, the oracle self-check)."""
+    JSON line (seconds, pairs, survivor counts, the sweep's roofline, the oracle self-check).
+    dump: the last timed step also copies its results aside (device to device, enqueued behind
+    each launch's filter) for dump_outputs(); returned as host arrays under "outputs"."""
     from imageanalysis_amd import kernels
 
     # ---- survey: configs[1] on one GPU, configs[2] (strong scaling) on several.  Image slots
@@ -165,6 +182,44 @@ def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, v
 
     candidates = torch.zeros(1, dtype=torch.int64, device=dev)
 
+    # ---- --dump-outputs: buffers the last timed step copies its results into (allocated here,
+    #      outside the timed region; `capture` is switched on for that step only)
+    capture = [False]
+    if dump:
+        pair_off = np.concatenate([[0], np.cumsum([b.n_pairs for b in batches])]).astype(np.int64)
+        dump_cnt = torch.zeros(int(pair_off[-1]), dtype=torch.int32, device=dev)
+        picks = np.unique(np.linspace(0, len(batches) - 1, min(DUMP_LAUNCHES, len(batches)))
+                          .round().astype(np.int64))
+        window = torch.arange(KPTS, dtype=torch.int64, device=dev)   # (a pair's survivors <= its query rows)
+        dump_surv = {}
+        for k in picks:
+            # the launch's neighbour pairs (planted overlap: most survivors) first, then pairs
+            # spread over the launch, DUMP_PAIRS_PER_LAUNCH in all
+            o, n = launches[k], len(launches[k])
+            sel = list(np.nonzero(np.abs(o[:, 0] - o[:, 1]) == 1)[0][:DUMP_PAIRS_PER_LAUNCH // 2])
+            sel += [p for p in np.linspace(0, n - 1, DUMP_PAIRS_PER_LAUNCH).round().astype(np.int64)
+                    if p not in sel]
+            sel = np.sort(np.array(sel[:DUMP_PAIRS_PER_LAUNCH], np.int64))
+            rows = len(sel) * KPTS
+            dump_surv[int(k)] = (sel, torch.from_numpy(sel).to(dev),
+                                 torch.zeros(rows, dtype=torch.int32, device=dev),
+                                 torch.zeros(rows, dtype=torch.int32, device=dev),
+                                 torch.zeros(rows, dtype=torch.float64, device=dev))
+
+    def capture_outputs(b, w, k):
+        o = int(pair_off[k])
+        dump_cnt[o:o + b.n_pairs].copy_(w.surv_cnt[:b.n_pairs])
+        if k in dump_surv:
+            # pair p's survivors are surv_*[surv_off[p] .. + surv_cnt[p]) in either layout (the
+            # symmetric form leaves them at the start of the pair's row range, the one-direction
+            # form compacts them): gather a KPTS-row window from each picked pair's offset on the
+            # device (no host sync), the host keeps its first surv_cnt[p] rows
+            _sel, dsel, q, t, m = dump_surv[k]
+            idx = (w.surv_off[dsel].unsqueeze(1) + window).clamp_(max=w.max_rows - 1).view(-1)
+            q.copy_(w.surv_q[idx])
+            t.copy_(w.surv_t[idx])
+            m.copy_(w.surv_metric[idx])
+
     # ---- N > 1: what the product does with a round's results (matcher._MatchRun.exchange:
     #      every rank's share of a round -> rank 0 as ONE fixed-layout tensor gather).  Here a
     #      "round" is GATHER_GROUP launches; a rank's share is, per launch, the survivor count of
@@ -203,6 +258,8 @@ def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, v
     def count_survivors(b, w, k=None):
         survivors.add_(w.surv_cnt[:b.n_pairs].sum())
         candidates.add_(w.seg_count[:b.n_pairs].sum())     # rows that passed the bound test
+        if capture[0]:
+            capture_outputs(b, w, k)
         if gather is not None and k is not None:
             g, slot = divmod(k, GATHER_GROUP)
             st = gather["stage"][g & 1]
@@ -253,10 +310,12 @@ def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, v
         gather["truncated"].zero_()
         gather["received"].zero_()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
+        capture[0] = dump and i == steps - 1
         step(timed_events=True)
     barrier()
     dt = time.perf_counter() - t0
+    capture[0] = False
     per_rank = None
     # (each rank's own clock from the common start barrier to the moment ITS work of the K steps
     #  was done would need a second sync point; what is reported per rank is the barrier-to-barrier
@@ -334,8 +393,30 @@ def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, v
                                  verify_pairs, not args.one_direction)
 
     ws_unresolved = sum(int(w.unresolved.item()) for w in (ws_pair if overlap else [ws]))
-    cpu_sample = raw[:2].cpu().numpy() if (rank == 0 and mine >= 2) else None
-    return {"dt": dt, "total_pairs": total_pairs, "survivors": int(survivors.item()),
+    cpu_sample = raw[:2].cpu().numpy() if (cpu_sample and rank == 0 and mine >= 2) else None
+    outputs = None
+    if dump:
+        # what a caller of the path receives per launch (PairWorkspace.survivors): the survivor
+        # count of every ordered pair, and for the sampled launches the compacted survivors
+        # (query row, train row, metric; pair p owns [off[p], off[p] + count[p]) of its launch)
+        cnt_all = dump_cnt.cpu().numpy()
+        cnt = cnt_all
+        if cnt.size > DUMP_PAIRS:
+            cnt = cnt[np.sort(np.random.default_rng(0).choice(cnt.size, DUMP_PAIRS, replace=False))]
+        q, t, m = [], [], []
+        for k in sorted(dump_surv):
+            sel, _dsel, kq, kt, km = dump_surv[k]
+            kq, kt, km = kq.cpu().numpy(), kt.cpu().numpy(), km.cpu().numpy()
+            for i, p in enumerate(sel):
+                c = int(cnt_all[pair_off[k] + p])
+                q.append(kq[i * KPTS:i * KPTS + c])
+                t.append(kt[i * KPTS:i * KPTS + c])
+                m.append(km[i * KPTS:i * KPTS + c])
+        outputs = {"pair_survivor_count": cnt.astype(np.float32),
+                   "sample_survivor_query_row": np.concatenate(q).astype(np.float32),
+                   "sample_survivor_train_row": np.concatenate(t).astype(np.float32),
+                   "sample_survivor_metric": np.concatenate(m).astype(np.float64)}
+    return {"dt": dt, "outputs": outputs, "total_pairs": total_pairs, "survivors": int(survivors.item()),
             "candidates": int(candidates.item()), "unresolved": int(ws_unresolved),
             "verified": verified, "roofline": roofline, "cpu_sample": cpu_sample,
             "launches": len(batches), "per_rank_seconds": per_rank,
@@ -347,6 +428,19 @@ def match_section(args, rank, world, dev, dist, one_gpu, n_img, steps, warmup, v
                 "gathers_per_step": gather["groups"], "bytes_per_rank_and_gather": gather["words"] * 4,
                 "survivors_beyond_cap": int(gather["truncated"].item()),
                 "survivor_count_seen_by_rank0": int(gather["received"].item())}}
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: the last timed step's results (match_section's "outputs"; rank 0's share at
+    N > 1), one DIR/<name>.npy per array:
+      pair_survivor_count        float32, survivors of every ordered pair in schedule order (launch
+                                 by launch; beyond DUMP_PAIRS pairs a sample seeded with 0)
+      sample_survivor_query_row  float32, \\  the survivors of DUMP_PAIRS_PER_LAUNCH fixed ordered
+      sample_survivor_train_row  float32,  > pairs in each of DUMP_LAUNCHES launches spread evenly
+      sample_survivor_metric     float64, /   over the schedule, pair after pair (query rows ascending)"""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), arr)
 
 
 def main():
@@ -392,7 +486,16 @@ def main():
                     help='also run the whole chain (detect -> match -> link -> triangulate -> BA, '
                          'BASELINE configs[4] shape) on N rendered images through the drop-in entry '
                          'points and report per-stage seconds')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the oracle self-check (--verify-pairs), '
+                         'configs[1], dense overlap, BA, SIFT, consolidation, the configs[4] slice, '
+                         'host post-processing and the CPU baselines (the --no-* switches apply here)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / '
+                         'float64, < 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -427,18 +530,24 @@ def main():
             dist.init_process_group('nccl', device_id=dev)
 
     n_img = args.images or CONFIG2_IMAGES
+    full = args.full
     sift_early = None
-    if args.sift_first and not args.no_sift:
+    if full and args.sift_first and not args.no_sift:
         sift_early = sift_bench(rank, world, dev, dist, args)
+    # (the oracle self-check of the timed store and the CPU baseline's sample: --full only)
     m = match_section(args, rank, world, dev, dist, one_gpu, n_img, args.steps, args.warmup,
-                      args.verify_pairs)
+                      args.verify_pairs if full else 0, dump=args.dump_outputs is not None,
+                      cpu_sample=full)
+    if m["outputs"] is not None and rank == 0:
+        dump_outputs(args.dump_outputs, m["outputs"])
+    m["outputs"] = None
     # The feature-detection section runs HERE, directly behind the headline section.  Behind the
     # survey / dense-overlap / BA sections of the same process its single-stream loop reads 2.8 ms
     # per detection where the same kernels, buffers and loop read 1.66 ms here and 1.70 ms in a
     # fresh process -- while eight detections in flight read 1.39 ms in both places
     # (profiles/r5_bench_sift_{inplace,first}.json, r5_sift_stream_bisect.txt: not the stream
     # count, page-locked memory, allocator state, loaded code objects or ba_bench on its own).
-    if sift_early is None and not args.no_sift and not args.sift_last:
+    if full and sift_early is None and not args.no_sift and not args.sift_last:
         try:
             from threadpoolctl import threadpool_limits as _tl
             _q = _tl(limits=1, user_api='blas')
@@ -456,7 +565,7 @@ def main():
     # ---- configs[1] (the one-MI355X configuration of BASELINE.json: 500 images, 124 750 pairs) as
     #      an extra key at N = 1: same kernels, same timed-step contents, 0.23 s per step
     survey = None
-    if world == 1 and n_img != CONFIG1_IMAGES and not args.no_survey and not args.one_direction:
+    if full and world == 1 and n_img != CONFIG1_IMAGES and not args.no_survey and not args.one_direction:
         torch.cuda.empty_cache()
         s = match_section(args, rank, world, dev, dist, one_gpu, CONFIG1_IMAGES, 5, 1,
                           min(args.verify_pairs, 16))
@@ -472,7 +581,7 @@ def main():
         del s
         torch.cuda.empty_cache()
     dense = None
-    if rank == 0 and world == 1 and not args.no_survey and not args.one_direction:
+    if full and rank == 0 and world == 1 and not args.no_survey and not args.one_direction:
         dense = dense_overlap_bench(dev)
         torch.cuda.empty_cache()
     # ---- second half of the metric: sparse bundle adjustment (BASELINE configs[3])
@@ -489,17 +598,18 @@ def main():
         quiet_blas = contextlib.nullcontext()
     sift = cleanup = None
     with quiet_blas:
-        if not args.no_ba:
+        if full and not args.no_ba:
             torch.cuda.empty_cache()
             ba = ba_bench(rank, world, dev, dist, args)
-        if not args.no_sift:
+        if full and not args.no_sift:
             sift = sift_early if sift_early is not None else sift_bench(rank, world, dev, dist, args)
-        cleanup = cleanup_bench(args) if rank == 0 else None
+        cleanup = cleanup_bench(args) if full and rank == 0 else None
     # BASELINE configs[4] as a slice at its own frame size: 24 rendered 5472 x 3648 JPEGs through
     # detect -> match -> link -> triangulate -> BA (the drop-in entry points, host side included)
     e2e = e2e_small = e2e_big = None
     if rank == 0 and world == 1:
-        if not args.no_e2e:
+        # (--e2e-full N and --e2e N are runs of their own, asked for by name: with or without --full)
+        if full and not args.no_e2e:
             # 128 rendered 20 MP frames (13 s of untimed rendering), the distance-window schedule
             # of a real survey; `--e2e-full N` runs the same at N >= 512
             e2e = e2e_bench(E2E_FRAMES, full_frame=True, schedule='distance')
@@ -511,7 +621,7 @@ def main():
     # CPU baselines of the BA and SIFT sections run AFTER every timed GPU section: their OpenMP /
     # OpenBLAS worker threads keep spinning for a while after a parallel region and a GPU
     # section timed right behind them loses 4x (measured: 3.9 -> 20.9 ms per SIFT frame)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if ba is not None:
             ba["cpu_baseline"] = ba_cpu_baseline()
         if sift is not None and _SIFT_SAMPLE is not None:
@@ -519,14 +629,14 @@ def main():
 
     out = None
     if rank == 0:
-        host_post = host_postprocess_rate()              # (times a device kernel: before the
-        cpu = None                                       #  OpenMP baseline, see above)
-        if not args.no_cpu_baseline and world == 1:      # CPU baselines: rank 0 at N=1 only
+        host_post = host_postprocess_rate() if full else None   # (times a device kernel: before
+        cpu = None                                              #  the OpenMP baseline, see above)
+        if full and not args.no_cpu_baseline and world == 1:    # CPU baselines: rank 0 at N=1 only
             cpu = cpu_baseline(cpu_sample)
         value = total_pairs * args.steps / dt
         out = {
             "metric": "image_pairs_matched_per_sec", "value": round(value, 1), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(full),
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None,
             "dtype": "u8 (int8 MFMA, int32 accumulate)",

@@ -25,7 +25,7 @@ def test_two_rank_bench_verifies_pairs_across_ranks():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(REPO, 'bench.py'),
            '--gpus', '2', '--steps', '1', '--warmup', '0', '--images', '64', '--no-sift',
-           '--no-cpu-baseline', '--ba-iters', '1']
+           '--no-cpu-baseline', '--ba-iters', '1', '--full']
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]

@@ -544,8 +544,9 @@ def test_detector_slots_are_private_per_thread_and_always_returned():
         s.__enter__()
         got.append(s)
     assert sorted(x.slot for x in got) == list(range(1, kernels.DETECT_SLOTS + 1))
-    for s in got:
+    for s in reversed(got):                                  # (nested: the last one entered leaves first)
         s.__exit__(None, None, None)
+    assert kernels._slot_key(Dev()) == (0, 0)               # this thread is back on the shared slot
 
 
 def test_quiet_pair_overwrites_a_stale_entry():

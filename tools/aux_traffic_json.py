@@ -58,7 +58,7 @@ frames = sum(v["dispatches"] for k, v in kernels.items() if k.startswith('pyrami
 sift_total = sum(v["hbm_bytes_per_launch"] * v["dispatches"] for k, v in kernels.items()
                  if k.split('<')[0] in SIFT)
 doc = {"source": "profiles/%s_aux_pmc_fetch.txt, profiles/%s_aux_pmc_write.txt (separate rocprofv3 --pmc "
-                 "passes of bench.py --images 64 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 "
+                 "passes of bench.py --full --images 64 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 "
                  "--no-e2e --no-sift-full --no-survey)" % (tag, tag),
        "fetch_correction": "x2 on gfx950 (MI355X_MICROARCH.md, HBM section)",
        "kernels": kernels,

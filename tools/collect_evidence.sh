@@ -15,7 +15,7 @@ SUM="python $REPO/tools/prof_summary.py"
 #  image, 6 s in, before the first sweep: profiles/r6_pmc_2812_segfault.txt)
 BENCH_PMC="python $REPO/bench.py --images 500 --steps 1 --warmup 0 --no-ba --no-sift --no-cpu-baseline --verify-pairs 0 --no-e2e --no-survey"
 # BA + SIFT kernels (a small matching section in front of them)
-AUX_PMC="python $REPO/bench.py --images 64 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-e2e --no-sift-full --no-survey"
+AUX_PMC="python $REPO/bench.py --full --images 64 --steps 1 --warmup 0 --no-cpu-baseline --verify-pairs 0 --no-e2e --no-sift-full --no-survey"
 
 step() { echo "== $1 ($(date +%T))"; }
 # The instantiation the library launches: every summary below must name it, or the run fails
@@ -70,14 +70,14 @@ python "$REPO/tools/update_traffic_json.py" "$TAG" || FAILED=1
 [ -f "$REPO/profiles/${TAG}_knn2sym_traffic.json" ] && cp "$REPO/profiles/${TAG}_knn2sym_traffic.json" "$OUT/"
 
 step "bench"
-timeout 1500 python bench.py --steps 20 --warmup 5 > "$OUT/${TAG}_bench_latest.json" 2> "$OUT/${TAG}_bench_latest.err"
+timeout 1500 python bench.py --full --steps 20 --warmup 5 > "$OUT/${TAG}_bench_latest.json" 2> "$OUT/${TAG}_bench_latest.err"
 tail -c 600 "$OUT/${TAG}_bench_latest.json"; echo
 
 fi
 if [ "${STAGE:-AB}" != "A" ]; then
 step "kernel stats of the bench command"
 (cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o b -- \
-    python "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-survey > "$OUT/${TAG}_bench_under_rocprof.json" 2> /tmp/p_stats.err)
+    python "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-survey > "$OUT/${TAG}_bench_under_rocprof.json" 2> /tmp/p_stats.err)
 $SUM /tmp/p_stats "$OUT/${TAG}_kernel_stats.txt" > /dev/null
 python "$REPO/tools/prof_gaps.py" /tmp/p_stats lsmr > "$OUT/${TAG}_lsmr_gaps.txt" 2>&1
 head -8 "$OUT/${TAG}_kernel_stats.txt" | cut -c1-160

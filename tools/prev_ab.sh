@@ -2,7 +2,7 @@
 # same-box A/B against the tree of an earlier commit checked out and built under _prev/
 # (git worktree add _prev <commit>; bash _prev/imageanalysis_amd/csrc/build.sh)
 cd "$(dirname "$0")/.."
-FLAGS="--steps 3 --warmup 1 --no-ba --no-sift --no-cpu-baseline --verify-pairs 0 --no-e2e"
+FLAGS="--full --steps 3 --warmup 1 --no-ba --no-sift --no-cpu-baseline --verify-pairs 0 --no-e2e"
 for tree in _prev . _prev .; do
   (cd $tree && python bench.py $FLAGS 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['summary']; o=d['dense_overlap']
