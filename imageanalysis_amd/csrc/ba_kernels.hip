@@ -519,21 +519,18 @@ extern "C" int iamx_ba_residual_prepared(const double *cams, int n_cams, const d
         // steps per wave: a multiple of PIPE_SETS (the walk is unrolled by it), at most 60 (the
         // redo mask); then as few workgroups as cover the chunks in that many steps -- 256 (one per
         // CU, one wave per SIMD) x 15 steps at configs[3]
+        // (a form with five register sets -- indices and gather two steps ahead -- was measured and
+        //  removed: profiles/r6_ba_resid_ab.txt)
         const int64_t n_chunks = (n_obs + 127) / 128;
-        const char *sets_e = getenv("IAMX_BA_RESIDUAL_SETS");
-        const int sets = sets_e && sets_e[0] == '5' ? 5 : 3;
+        constexpr int sets = 3;
         int64_t g = wgs ? atoll(wgs) : 256;
         if (g < 1) g = 1;
         int64_t steps = (n_chunks + 4 * g - 1) / (4 * g);
         steps = (steps + sets - 1) / sets * sets;
         if (steps > 60) steps = 60;
         g = (n_chunks + 4 * steps - 1) / (4 * steps);
-        if (sets == 5)
-            hipLaunchKernelGGL(ba_residual_pipe_kernel<5>, dim3((unsigned)g), dim3(256), 0, st, cams, pts,
-                               cam_idx, pt_idx, uv, n_obs, calib, r, (int)steps, n_cams);
-        else
-            hipLaunchKernelGGL(ba_residual_pipe_kernel<3>, dim3((unsigned)g), dim3(256), 0, st, cams, pts,
-                               cam_idx, pt_idx, uv, n_obs, calib, r, (int)steps, n_cams);
+        hipLaunchKernelGGL(ba_residual_pipe_kernel<sets>, dim3((unsigned)g), dim3(256), 0, st, cams, pts,
+                           cam_idx, pt_idx, uv, n_obs, calib, r, (int)steps, n_cams);
     }
     return iamx::check_launch("iamx_ba_residual_prepared");
 }

@@ -187,7 +187,7 @@ int64_t link_impl(const LinkInput &in, int64_t n_matches, int64_t n_pts, int32_t
     // is bound by memory latency (6.4 M points on a 128-frame survey, several passes).
     // A negative index or more than 2^31 table entries fall back to the hash map.
     int32_t n_img = 0;
-    bool dense = getenv("IAMX_LINK_HASH") == nullptr;      // (A/B switch: the hash map of rounds 1-3)
+    bool dense = true;
     for (int64_t j = 0; j < n_pts; ++j) {
         if (img[j] < 0 || kp[j] < 0) { dense = false; break; }
         if (img[j] >= n_img) n_img = img[j] + 1;

@@ -124,14 +124,14 @@ __device__ __forceinline__ bool lex_less(int da, int ia, int db, int ib)
     return da < db || (da == db && ia < ib);
 }
 
-// VARIANT is 0 in the product; other values are timing ablations reachable only through
-// the iamxdbg_knn2_variant entry point (tools/knn2_ablate.py): bit0 skip the top-2 epilogue,
-// bit1 skip the MFMAs, bit2 stage only the first chunk (no barriers in the sweep).
+// VARIANT is 0: the timing ablations it selected (no epilogue, no MFMAs, one staged chunk) were
+// measured and removed (profiles/r1_ubench_mfma_clock.txt).
 // QW_ = 32-query blocks per wave, WAVES_ = waves per workgroup, OCC = launch-bounds waves/SIMD,
 // FLAGS bit0: s_setprio(1) around the MFMA groups, bit1: two independent top-2 chains per query.
 template <int VARIANT, int QW_, int WAVES_, int OCC, int FLAGS>
 __global__ __launch_bounds__(WAVES_ * 64, OCC) void knn2_pairs_kernel(Knn2Args A)
 {
+    static_assert(VARIANT == 0, "the timing ablations were removed");
     constexpr int NT = WAVES_ * 64;            // threads
     constexpr int QB_ = WAVES_ * QW_ * 32;     // query rows per workgroup
     constexpr int PIECES = CHUNK * D / 16 / NT;  // 16-byte pieces staged per thread
@@ -228,11 +228,10 @@ __global__ __launch_bounds__(WAVES_ * 64, OCC) void knn2_pairs_kernel(Knn2Args A
 
     for (int ch = 0; ch < nchunks; ++ch) {
         const int buf = ch & 1;
-        if constexpr (!(VARIANT & 4))
-            if (ch + 1 < nchunks) load_chunk(ch + 1);
+        if (ch + 1 < nchunks) load_chunk(ch + 1);
 
-        const int8_t *tile_base = lds_tile + ((VARIANT & 4) ? 0 : buf) * (CHUNK * D);
-        const int *tb_base = lds_tb + ((VARIANT & 4) ? 0 : buf) * CHUNK;
+        const int8_t *tile_base = lds_tile + buf * (CHUNK * D);
+        const int *tb_base = lds_tb + buf * CHUNK;
 #pragma unroll
         for (int tile = 0; tile < CHUNK / 32; ++tile) {
             const int r = tile * 32 + c;
@@ -250,24 +249,15 @@ __global__ __launch_bounds__(WAVES_ * 64, OCC) void knn2_pairs_kernel(Knn2Args A
                 v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
                 if constexpr (FLAGS & 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if constexpr (VARIANT & 2) {
-                        acc[s] += a[s][0] ^ bq[qb][s][1];
-                    } else {
-                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qb][s], acc, 0, 0, 0);
-                    }
-                }
+                for (int s = 0; s < 4; ++s)
+                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qb][s], acc, 0, 0, 0);
                 if constexpr (FLAGS & 1) __builtin_amdgcn_s_setprio(0);
-                if constexpr (VARIANT & 1) {
-                    asm volatile("" ::"v"(acc));
-                } else {
 #pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int h = (NCH == 2) ? (reg & 1) : 0;
-                        int key = tbv[reg >> 2][reg & 3] + (acc[reg] << 9);
-                        m2[qb][h] = med3_i32(m1[qb][h], m2[qb][h], key);
-                        m1[qb][h] = min(m1[qb][h], key);
-                    }
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int h = (NCH == 2) ? (reg & 1) : 0;
+                    int key = tbv[reg >> 2][reg & 3] + (acc[reg] << 9);
+                    m2[qb][h] = med3_i32(m1[qb][h], m2[qb][h], key);
+                    m1[qb][h] = min(m1[qb][h], key);
                 }
             }
         }
@@ -299,10 +289,8 @@ __global__ __launch_bounds__(WAVES_ * 64, OCC) void knn2_pairs_kernel(Knn2Args A
             }
         }
 
-        if constexpr (!(VARIANT & 4)) {
-            if (ch + 1 < nchunks) store_chunk(buf ^ 1);
-            __syncthreads();
-        }
+        if (ch + 1 < nchunks) store_chunk(buf ^ 1);
+        __syncthreads();
     }
 
     // ---- merge the two lane halves, add the query norm, store
@@ -547,47 +535,6 @@ extern "C" int iamx_knn2_l2_pairs(const int8_t *desc, const int32_t *norm_q,
                        iamx::as_stream(stream), a);
     return iamx::check_launch("iamx_knn2_l2_pairs");
 }
-
-#ifdef IAMX_ABLATE   // scaffolding of tools/*_ablate.py: built into libiamx_ablate.so only
-// timing ablations (not part of the C ABI; see the VARIANT comment above)
-extern "C" int iamxdbg_knn2_variant(int variant, const int8_t *desc, const int32_t *norm_q,
-                                    const int32_t *norm_t, const int32_t *img_off,
-                                    const int32_t *img_n, const int32_t *pairs,
-                                    const int32_t *wg_off, const int64_t *out_off, int n_pairs,
-                                    int total_wg, int32_t *out_idx, int32_t *out_d2, void *stream)
-{
-    Knn2Args a{desc, desc, norm_q, norm_t, img_off, img_n, pairs, wg_off, out_off,
-               out_idx, out_d2, n_pairs, total_wg, 0, 0};
-    hipStream_t st = iamx::as_stream(stream);
-    dim3 g((unsigned)total_wg);
-#define V(id, ...) case id: hipLaunchKernelGGL((knn2_pairs_kernel<__VA_ARGS__>), g, dim3(WV * 64), 0, st, a); break;
-    switch (variant) {
-#define WV 4
-        V(0, 0, 2, 4, 2, 0) V(1, 1, 2, 4, 2, 0) V(2, 2, 2, 4, 2, 0) V(4, 4, 2, 4, 2, 0)
-        V(5, 5, 2, 4, 2, 0) V(6, 6, 2, 4, 2, 0)
-        V(10, 0, 2, 4, 2, 1)      // setprio
-        V(11, 0, 2, 4, 2, 2)      // dual chains
-        V(12, 0, 2, 4, 2, 3)      // both
-        V(13, 0, 2, 4, 3, 0)      // occupancy hint 3
-        V(14, 0, 2, 4, 4, 0)      // occupancy hint 4 (<=128 VGPR)
-        V(15, 0, 2, 4, 4, 2)
-        V(16, 0, 1, 4, 4, 0)      // QW=1: 128 queries per workgroup
-        V(17, 0, 1, 4, 4, 2)
-        V(18, 0, 3, 4, 2, 0)      // QW=3
-        V(19, 0, 4, 4, 1, 0)      // QW=4
-#undef WV
-#define WV 8
-        V(20, 0, 2, 8, 2, 0)      // 8 waves share the staged tile
-        V(21, 0, 2, 8, 2, 2)
-        V(22, 0, 1, 8, 2, 0)
-        V(23, 0, 1, 8, 4, 2)
-#undef WV
-    default: return iamx::fail(IAMX_EINVAL, "unknown variant");
-    }
-#undef V
-    return iamx::check_launch("iamxdbg_knn2_variant");
-}
-#endif
 
 extern "C" int iamx_knn2_l2_u8(const int8_t *q_desc, const int32_t *q_norm_q, int nq,
                                const int8_t *t_desc, const int32_t *t_norm_t, int nt,

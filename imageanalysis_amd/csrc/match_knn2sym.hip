@@ -418,21 +418,22 @@ __device__ __forceinline__ void half_wave_min16(int (&r)[16], int lo, int &m0, i
     m1 = w[1];
 }
 
-// VARIANT != 0: timing ablations, compiled only with -DIAMX_ABLATE (tools/knn2sym_ablate.py):
-// bit0 no column direction, bit1 no row direction, bit2 row direction without the cross-lane
-// butterfly, bit3 no MFMA.  Results are meaningless.
 // PIPE: the MFMAs of a pair of query blocks are issued while the minima of the previous pair are
-// taken (software pipeline across the 8 steps of a chunk, sched_group_barrier interleave).
-// MERGEW: waves that share the per-chunk row merge (CHUNK / MERGEW rows each); SLEEP: s_sleep
-// argument for the second half of the waves at the start of every chunk (de-phasing experiments)
+// taken (software pipeline across the 8 steps of a chunk, sched_group_barrier interleave); PIPE
+// epilogue VALU instructions go beside every MFMA.
+// MERGEW: waves that share the per-chunk row merge (CHUNK / MERGEW rows each).
 // GROUPLO: the Cq floor is shared by the four lanes l, l^4, l^8, l^12 (they hold 4 QW consecutive
 // sorted rows) and added after the two butterfly levels inside a 16-lane row instead of riding in
 // the C operand; with it the fused butterfly (half_wave_min16<true>).
-template <int QW, int NW, int VARIANT = 0, int PIPE = 0, int MERGEW = 2, int SLEEP = 0, bool GROUPLO = false,
-          int CH = 128, int WPE = 2>
+// The timing ablations (VARIANT), the de-phasing sleep (SLEEP), the Cq floor in the C operand
+// (GROUPLO = false), 256-row chunks (CH), other merge splits and the unpipelined tile loop were
+// measured and removed (profiles/r2_knn2sym_ablate*.txt); the parameters stay in the kernel's name.
+template <int QW, int NW, int VARIANT, int PIPE, int MERGEW, int SLEEP, bool GROUPLO, int CH, int WPE>
 __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
 {
-    constexpr int CHUNK = CH;        // train rows per LDS stage (experiments: 256)
+    static_assert(VARIANT == 0 && PIPE > 0 && MERGEW == 2 && SLEEP == 0 && GROUPLO && CH == 128,
+                  "only the shipped sweep is implemented");
+    constexpr int CHUNK = CH;        // train rows per LDS stage
     constexpr int WGROWS = NW * QW * 32;
     constexpr int NT = NW * 64;
     constexpr int PIECES = CHUNK * D / 16 / NT;
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     // hundred for SIFT-like rows, the rows are sorted) widens the upper bound afterwards.
     // (GROUPLO: lane c holds the row quadruple rc, c's bits 3:2 moved to the bottom, so that
     //  the lanes that differ in bits 3:2 hold 4 QW CONSECUTIVE rows)
-    const int rc = GROUPLO ? ((c & 16) | ((c & 3) << 2) | ((c >> 2) & 3)) : c;
+    const int rc = (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3);
     v4i bq[QW][4];
 #pragma unroll
     for (int qb = 0; qb < QW; ++qb) {
@@ -494,7 +495,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     {
         int spread = 0;
         if (wave_valid) {
-            const int g_lo = GROUPLO ? (rc & ~3) : rc, g_hi = GROUPLO ? (rc | 3) : rc;
+            const int g_lo = rc & ~3, g_hi = rc | 3;
             const int r_lo = q0 + QW * g_lo < nb ? q0 + QW * g_lo : nb - 1;
             const int r_hi = q0 + QW * g_hi + QW - 1 < nb ? q0 + QW * g_hi + QW - 1 : nb - 1;
             lo_lane = A.sn2[boff + r_lo] >> 1;
@@ -560,11 +561,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     for (int w = 0; w < NW; ++w) spread_w[w] = __builtin_amdgcn_readfirstlane(lds_cq[w]);
     for (int ch = 0; ch < nchunks; ++ch) {
         const int buf = ch & 1;
-        if (ch + 1 < nchunks && (!(VARIANT & 64) || ch == 0)) stage_direct(ch + 1, buf ^ 1);
-        if constexpr (SLEEP > 0)
-            if (wave >= NW / 2) __builtin_amdgcn_s_sleep(SLEEP);
-        if constexpr (!(VARIANT & 16))
-            if (ch > 0 && merger) merge_rows(ch - 1, buf ^ 1);
+        if (ch + 1 < nchunks) stage_direct(ch + 1, buf ^ 1);
+        if (ch > 0 && merger) merge_rows(ch - 1, buf ^ 1);
         if (wave_valid) {
             const int8_t *tile_base = lds_tile + buf * (CHUNK * D);
             const int *tb_base = lds_tb + buf * CHUNK;
@@ -577,177 +575,76 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                 for (int k = 0; k < 4; ++k)
                     tbv[k] = *reinterpret_cast<const v4i *>(tb_base + tile * 32 + 8 * k + 4 * g);
             };
+            // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3); after the
+            // butterfly a quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per quad
+            // stores them; the others store into a dump area (no branch in the tile loop: a branch
+            // there makes the compiler sink the column minima below it and keep the accumulators alive)
             int *row_dst = (lane & 3) == 0
                 ? lds_row + (buf * NW + wave) * CHUNK + 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1)
                 : lds_dump + wave * 256 + lane;                 // + tile*32 (+16) stays inside [0, 256)
-            if constexpr (PIPE != 0) {
-                constexpr int PP = QW / 2, NS = (CHUNK / 32) * PP;
-                v4i aop[2][4], tbop[2][4];
-                v16i accs[2][2];
-                int r[16];
-                auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
+            constexpr int PP = QW / 2, NS = (CHUNK / 32) * PP;
+            v4i aop[2][4], tbop[2][4];
+            v16i accs[2][2];
+            int r[16];
+            auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
 #pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
+                for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
-                    }
-                    if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
-                };
-                load_ops(0, aop[0], tbop[0]);
-                if constexpr (!GROUPLO) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) tbop[0][k] += lo_lane;
+                for (int s = 0; s < 4; ++s) {
+                    acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
                 }
-                issue(0, 0, accs[0][0], accs[0][1]);
-                load_ops(1, aop[1], tbop[1]);
-                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
+            };
+            load_ops(0, aop[0], tbop[0]);
+            issue(0, 0, accs[0][0], accs[0][1]);
+            load_ops(1, aop[1], tbop[1]);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int st = 0; st < NS; ++st) {
-                    const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
-                    if (st + 1 < NS) {
-                        const int t1 = (st + 1) / PP, qp1 = 2 * ((st + 1) % PP);
-                        if (!GROUPLO && t1 != t) {
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) tbop[t1 & 1][k] += lo_lane;
-                        }
-                        issue(t1, qp1, accs[cur ^ 1][0], accs[cur ^ 1][1]);
-                        if (t1 != t && t1 + 1 < CHUNK / 32) load_ops(t1 + 1, aop[t & 1], tbop[t & 1]);
-                    }
-                    const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
-                    int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
-                    int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
-#pragma unroll
-                    for (int reg = 2; reg < 16; reg += 2) {
-                        t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
-                        t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
-                    }
-                    m[qp][t & 3] = t0;
-                    m[qp + 1][t & 3] = t1m;
-                    if (qp == 0) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) r[reg] = min(acc0[reg], acc1[reg]);
-                    } else {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) r[reg] = min(min(r[reg], acc0[reg]), acc1[reg]);
-                    }
-                    if (qp == QW - 2) {
-                        int m0, m1;
-                        half_wave_min16<GROUPLO>(r, GROUPLO ? lo_lane : 0, m0, m1);
-                        int *dst = row_dst + t * 32;
-                        dst[0] = m0;
-                        dst[16] = m1;
-                    }
-                    if (st + 1 < NS) {
-                        // one MFMA, then the VALU work that fits beside it
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+            for (int st = 0; st < NS; ++st) {
+                const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
+                if (st + 1 < NS) {
+                    const int t1 = (st + 1) / PP, qp1 = 2 * ((st + 1) % PP);
+                    issue(t1, qp1, accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                    if (t1 != t && t1 + 1 < CHUNK / 32) load_ops(t1 + 1, aop[t & 1], tbop[t & 1]);
                 }
-            } else {
-            v4i a[4], tbv[4];
-            load_ops(0, a, tbv);
+                const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
+                int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
+                int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
 #pragma unroll
-            for (int tile = 0; tile < CHUNK / 32; ++tile) {
-                v4i a_nx[4], tb_nx[4];
-                if (tile + 1 < CHUNK / 32) {
-                    if constexpr (VARIANT & 256) {      // (timing only: operands reused, no LDS reads)
-#pragma unroll
-                        for (int s2 = 0; s2 < 4; ++s2) { a_nx[s2] = a[s2]; a_nx[s2][0] += 1; tb_nx[s2] = tbv[s2]; }
-                    } else {
-                        load_ops(tile + 1, a_nx, tb_nx);
-                    }
+                for (int reg = 2; reg < 16; reg += 2) {
+                    t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
+                    t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
                 }
-                int r[16];
-                static_assert(QW % 2 == 0, "query blocks are processed in pairs");
-                int cl[16];                    // C operand: Ct of the 16 rows + the lane's Cq floor
+                m[qp][t & 3] = t0;
+                m[qp + 1][t & 3] = t1m;
+                if (qp == 0) {
 #pragma unroll
-                for (int reg = 0; reg < 16; ++reg) cl[reg] = tbv[reg >> 2][reg & 3] + (GROUPLO ? 0 : lo_lane);
-#pragma unroll
-                for (int qp = 0; qp < QW; qp += 2) {
-                    // two independent accumulator chains in flight (C operand = Ct of the rows)
-                    v16i acc0, acc1;
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = cl[reg];
-                    if constexpr (VARIANT & 128) {      // (experiment: MFMA bursts at raised priority)
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_setprio(3);
-                    }
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        if constexpr (VARIANT & 8) {
-                            acc0[s] += a[s][0] ^ bq[qp][s][1];
-                            acc1[s] += a[s][1] ^ bq[qp + 1][s][1];
-                        } else {
-                            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qp][s], acc0, 0, 0, 0);
-                            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qp + 1][s], acc1, 0, 0, 0);
-                        }
-                    }
-                    if constexpr (VARIANT & 128) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        __builtin_amdgcn_s_setprio(0);
-                    }
-                    if constexpr (VARIANT & 1) {
-                        asm volatile("" ::"v"(acc0), "v"(acc1));
-                    } else {
-                        // column direction: one of four interleaved running minima per query
-                        int t0 = min(min(m[qp][tile & 3], acc0[0]), acc0[1]);
-                        int t1 = min(min(m[qp + 1][tile & 3], acc1[0]), acc1[1]);
-#pragma unroll
-                        for (int reg = 2; reg < 16; reg += 2) {
-                            t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
-                            t1 = min(min(t1, acc1[reg]), acc1[reg + 1]);
-                        }
-                        m[qp][tile & 3] = t0;
-                        m[qp + 1][tile & 3] = t1;
-                    }
-                    // row direction: minimum over the wave's query blocks, per accumulator register
-                    if constexpr (VARIANT & 2) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) r[reg] = 0;
-                    } else if (qp == 0) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) r[reg] = min(acc0[reg], acc1[reg]);
-                    } else {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) r[reg] = min(min(r[reg], acc0[reg]), acc1[reg]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);     // keep the pairs apart: two chains live
-                }
-                int m0, m1;
-                if constexpr (VARIANT & 6) {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) asm volatile("" ::"v"(r[reg]));
-                    m0 = r[0];
-                    m1 = r[1];
+                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(acc0[reg], acc1[reg]);
                 } else {
-                    half_wave_min16<GROUPLO>(r, GROUPLO ? lo_lane : 0, m0, m1);
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(min(r[reg], acc0[reg]), acc1[reg]);
                 }
-                {
-                    // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3);
-                    // this quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per
-                    // quad stores them; the others store into a dump area (no branch in the tile
-                    // loop: a branch here makes the compiler sink the column minima of all four
-                    // tiles below it and keep 128 accumulator registers alive)
-                    int *dst = row_dst + tile * 32;
+                if (qp == QW - 2) {
+                    int m0, m1;
+                    half_wave_min16<true>(r, lo_lane, m0, m1);
+                    int *dst = row_dst + t * 32;
                     dst[0] = m0;
                     dst[16] = m1;
                 }
-                if (tile + 1 < CHUNK / 32) {
+                if (st + 1 < NS) {
+                    // one MFMA, then the VALU work that fits beside it
 #pragma unroll
-                    for (int s = 0; s < 4; ++s) { a[s] = a_nx[s]; tbv[s] = tb_nx[s]; }
+                    for (int i = 0; i < 8; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
+                    }
                 }
-                __builtin_amdgcn_sched_barrier(0);     // keep tiles apart (no hoisting -> no spills)
-            }
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
         wait_direct();
-        if constexpr (!(VARIANT & 32)) __syncthreads();
+        __syncthreads();
     }
     if (merger) merge_rows(nchunks - 1, (nchunks - 1) & 1);
 
@@ -774,13 +671,12 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
 #endif
         }
         const unsigned othpack = A.colmask ? (unsigned)__shfl_xor((int)ownpack, 32) : 0u;
-        const int sub = GROUPLO ? 0 : lo_lane;           // (GROUPLO: the accumulators never saw it)
         const int row0 = q0 + QW * rc;
         if (g == 0) {
 #pragma unroll
             for (int qb = 0; qb < QW; ++qb)
                 if (row0 + qb < nb)
-                    *reinterpret_cast<v2i *>(A.col + 2 * (A.col_off[u] + row0 + qb)) = v2i{v1s[qb] - sub, v2s[qb] - sub};
+                    *reinterpret_cast<v2i *>(A.col + 2 * (A.col_off[u] + row0 + qb)) = v2i{v1s[qb], v2s[qb]};
             if (A.colmask) {
                 // byte qb = own nibble | other half's nibble << 4
                 uint8_t *dst = A.colmask + A.col_off[u] + row0;
@@ -802,266 +698,6 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
         }
     }
 }
-
-#ifdef IAMX_ABLATE
-// ---------------------------------------------------------------------------------
-// EXPERIMENT (ablation build only; measured, not shipped: profiles/r3_knn2sym_crosschunk.txt --
-// 1 % with the barrier on the chunk boundary, register spills with it anywhere else).
-// The same sweep with the software pipeline carried ACROSS the chunk boundary (round 3).
-// knn2sym_kernel drains its pipeline at every chunk barrier: the last epilogue of a chunk has no
-// MFMAs beside it, the first MFMAs of the next chunk no epilogue, and the barrier puts the two
-// waves of every SIMD back into lockstep eight steps later.  Here the A rows are staged THREE
-// chunks deep, so the one barrier per chunk does not have to sit on the boundary:
-//   barrier M(ch), taken by a wave somewhere in the first steps of chunk ch (step BAR_LO for the
-//   first half of the waves, BAR_HI for the second: the two waves of a SIMD arrive from different
-//   points of their step sequence), says
-//     (1) chunk ch+1 is in LDS (every wave waited for its part of the staging it issued behind
-//         M(ch-1), a whole chunk ago),
-//     (2) nobody reads chunk ch-1 any more -> its buffer takes chunk ch+2,
-//     (3) every wave has stored its row minima of chunk ch-1 -> waves 0/1 merge them.
-//   The last step of a chunk issues the MFMAs of the next chunk's first step (operands read from
-//   the next buffer behind M(ch)), so the MFMA / epilogue interleave never stops; the step behind
-//   the last chunk computes on stale rows and is dropped.  The row minima rotate through three
-//   buffers as well (a wave may write chunk ch+2's while the merge of chunk ch is still running).
-// Arithmetic, bounds and result layout are those of knn2sym_kernel<.., GROUPLO = true>.
-// ---------------------------------------------------------------------------------
-template <int QW, int NW, int PIPE, int BAR_LO, int BAR_HI>
-__global__ __launch_bounds__(NW * 64, 2) void knn2sym_x_kernel(SymArgs A)
-{
-    constexpr int WGROWS = NW * QW * 32;
-    constexpr int NT = NW * 64;
-    constexpr int PIECES = CHUNK * D / 16 / NT;
-    constexpr int TPC = CHUNK / 32;                  // 32-row tiles per chunk
-    constexpr int PP = QW / 2, NS = TPC * PP;        // steps (pairs of query blocks) per chunk
-    static_assert(QW % 2 == 0 && (TPC % 2) == 0, "operand / accumulator parity continues across chunks");
-    static_assert(BAR_LO <= NS - PP - 1 && BAR_HI <= NS - PP - 1, "the barrier precedes the first read of the next chunk");
-    __shared__ __attribute__((aligned(16))) int8_t lds[3 * CHUNK * D + 3 * CHUNK * 4 + 3 * NW * CHUNK * 4 + 2 * NW * 4 + NW * 256 * 4];
-    int8_t *lds_tile = lds;
-    int *lds_tb = reinterpret_cast<int *>(lds + 3 * CHUNK * D);      // [3][CHUNK]     Ct
-    int *lds_row = lds_tb + 3 * CHUNK;                               // [3][NW][CHUNK] R_w
-    int *lds_cq = lds_row + 3 * NW * CHUNK;                          // [NW] (2 NW reserved) S_w
-    int *lds_dump = lds_cq + 2 * NW;                                 // [NW][256]      unused stores
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 31, g = lane >> 5;
-
-    int vid;
-    {
-        const int total = A.total_wg, bid = blockIdx.x;
-        const int xcd = bid & 7, k = bid >> 3, q = total >> 3, r = total & 7;
-        vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
-    int lo = 0, hi = A.n_u;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (A.wg_off[mid] <= vid) lo = mid; else hi = mid;
-    }
-    const int u = lo;
-    const int bimg = A.upairs[2 * u], aimg = A.upairs[2 * u + 1];
-    const int boff = A.img_off[bimg], nb = A.img_n[bimg];
-    const int aoff = A.img_off[aimg], na = A.img_n[aimg];
-    const int capA = (na + CHUNK - 1) / CHUNK * CHUNK;
-    const int nchunks = capA / CHUNK;
-    const int wgi = vid - A.wg_off[u];
-    const int q0 = wgi * WGROWS + wave * (QW * 32);
-    const bool wave_valid = q0 < nb;
-    const int64_t rbase = A.rowp_off[u] + (int64_t)wgi * capA;
-
-    // B operand and Cq floor as in knn2sym_kernel (GROUPLO lane -> row map)
-    const int rc = (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3);
-    v4i bq[QW][4];
-#pragma unroll
-    for (int qb = 0; qb < QW; ++qb) {
-        int row = q0 + QW * rc + qb;
-        row = row < nb ? row : nb - 1;
-        const v4i *src = reinterpret_cast<const v4i *>(A.sdesc + (int64_t)(boff + row) * D);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) bq[qb][s] = ~src[2 * s + g];
-    }
-    int lo_lane = 0;
-    {
-        int spread = 0;
-        if (wave_valid) {
-            const int g_lo = rc & ~3, g_hi = rc | 3;
-            const int r_lo = q0 + QW * g_lo < nb ? q0 + QW * g_lo : nb - 1;
-            const int r_hi = q0 + QW * g_hi + QW - 1 < nb ? q0 + QW * g_hi + QW - 1 : nb - 1;
-            lo_lane = A.sn2[boff + r_lo] >> 1;
-            spread = (A.sn2[boff + r_hi] >> 1) - lo_lane;
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
-        if (lane == 0) lds_cq[wave] = spread;
-    }
-    if (!wave_valid) {
-#pragma unroll
-        for (int k = 0; k < 3 * CHUNK / 64; ++k)
-            lds_row[((k / (CHUNK / 64)) * NW + wave) * CHUNK + (k % (CHUNK / 64)) * 64 + lane] = BIG;
-    }
-    int m[QW][4];
-#pragma unroll
-    for (int qb = 0; qb < QW; ++qb)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m[qb][k] = BIG;
-
-    const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
-    const int32_t *tci = A.sct + aoff;
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    auto stage_direct = [&](int ch, int buf) {
-#pragma unroll
-        for (int j = 0; j < PIECES; ++j) {
-            const int e = j * NT + tid, row = e >> 3, slot = (e & 7) ^ ((row >> 1) & 7);
-            const int8_t *gsrc = tbase + (int64_t)(ch * CHUNK + row) * D + slot * 16;
-            int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
-            __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
-        }
-        if (wave < CHUNK / 64)
-            __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + tid,
-                                             (lds_ptr)(lds_tb + buf * CHUNK + wave * 64), 4, 0, 0);
-    };
-    auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
-    constexpr int MROWS = CHUNK / 2;                     // waves 0 and 1 merge 64 rows each
-    const int mrow = wave * MROWS + lane;
-    const bool merger = wave < 2;
-    auto merge_rows = [&](int ch, int buf) {
-        int L = BIG, U1 = BIG, U2 = BIG;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int R = lds_row[(buf * NW + w) * CHUNK + mrow];
-            const int uw = R + lds_cq[w];
-            L = min(L, R);
-            U2 = min(max(U1, uw), U2);
-            U1 = min(U1, uw);
-        }
-        *reinterpret_cast<v2i *>(A.rowp + 2 * (rbase + ch * CHUNK + mrow)) = v2i{L, pack_row_bounds(L, U1, U2)};
-    };
-    // barrier M(ch): see the header.  b2 = buffer of chunk ch+2 = buffer of chunk ch-1
-    auto mid_barrier = [&](int ch, int b2) {
-        wait_direct();
-        __syncthreads();
-        if (ch + 2 < nchunks) stage_direct(ch + 2, b2);
-        if (ch > 0 && merger) merge_rows(ch - 1, b2);
-    };
-
-    stage_direct(0, 0);
-    if (nchunks > 1) stage_direct(1, 1);
-    wait_direct();
-    __syncthreads();
-
-    if (!wave_valid) {
-        int b2 = 2;
-        for (int ch = 0; ch < nchunks; ++ch) {
-            mid_barrier(ch, b2);
-            b2 = b2 == 2 ? 0 : b2 + 1;
-        }
-    } else {
-        const int bar_st = wave < NW / 2 ? BAR_LO : BAR_HI;
-        auto load_tile = [&](const int8_t *tile_base, const int *tb_base, int tile, v4i (&a)[4], v4i (&tbv)[4]) {
-            const int r = tile * 32 + c, swz = (r >> 1) & 7;
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                a[s] = *reinterpret_cast<const v4i *>(tile_base + r * D + (((2 * s + g) ^ swz) * 16));
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                tbv[k] = *reinterpret_cast<const v4i *>(tb_base + tile * 32 + 8 * k + 4 * g);
-        };
-        v4i aop[2][4], tbop[2][4];
-        v16i accs[2][2];
-        int r[16];
-        auto issue = [&](int par, int qp, v16i &acc0, v16i &acc1) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[par][reg >> 2][reg & 3];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[par][s], bq[qp][s], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[par][s], bq[qp + 1][s], acc1, 0, 0, 0);
-            }
-        };
-        const int row_lane = 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1);
-        const bool row_owner = (lane & 3) == 0;
-        // prologue: the first step of chunk 0 is in flight when the loop starts
-        load_tile(lds_tile, lds_tb, 0, aop[0], tbop[0]);
-        issue(0, 0, accs[0][0], accs[0][1]);
-        load_tile(lds_tile, lds_tb, 1, aop[1], tbop[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        int b = 0;
-        for (int ch = 0; ch < nchunks; ++ch) {
-            const int b1 = b == 2 ? 0 : b + 1, b2 = b == 0 ? 2 : b - 1;
-            const int8_t *tile_cur = lds_tile + b * (CHUNK * D), *tile_nxt = lds_tile + b1 * (CHUNK * D);
-            const int *tb_cur = lds_tb + b * CHUNK, *tb_nxt = lds_tb + b1 * CHUNK;
-            int *row_dst = row_owner ? lds_row + (b * NW + wave) * CHUNK + row_lane
-                                     : lds_dump + wave * 256 + lane;     // + t*32 (+16) stays inside [0, 256)
-#pragma unroll
-            for (int st = 0; st < NS; ++st) {
-                const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
-                if (st == BAR_LO || st == BAR_HI) {
-                    if (bar_st == st) mid_barrier(ch, b2);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                {
-                    // the next step's MFMAs (past the last step of the chunk: the next chunk's first)
-                    const int t1 = (st + 1) / PP, qp1 = 2 * ((st + 1) % PP);
-                    issue(t1 & 1, qp1, accs[cur ^ 1][0], accs[cur ^ 1][1]);
-                    if (t1 != t) {
-                        const int T = t1 + 1;            // operands of the tile after that one
-                        if (T >= TPC) load_tile(tile_nxt, tb_nxt, T - TPC, aop[t & 1], tbop[t & 1]);
-                        else load_tile(tile_cur, tb_cur, T, aop[t & 1], tbop[t & 1]);
-                    }
-                }
-                const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
-                int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
-                int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
-#pragma unroll
-                for (int reg = 2; reg < 16; reg += 2) {
-                    t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
-                    t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
-                }
-                m[qp][t & 3] = t0;
-                m[qp + 1][t & 3] = t1m;
-                if (qp == 0) {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(acc0[reg], acc1[reg]);
-                } else {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(min(r[reg], acc0[reg]), acc1[reg]);
-                }
-                if (qp == QW - 2) {
-                    int m0, m1;
-                    half_wave_min16<true>(r, lo_lane, m0, m1);
-                    int *dst = row_dst + t * 32;
-                    dst[0] = m0;
-                    dst[16] = m1;
-                }
-                // one MFMA, then the VALU work that fits beside it
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            b = b1;
-        }
-    }
-    wait_direct();
-    __syncthreads();
-    if (merger) merge_rows(nchunks - 1, (nchunks - 1) % 3);
-
-    // ---- column results: two smallest of the 4 x 2 group minima of every query
-    if (wave_valid) {
-#pragma unroll
-        for (int qb = 0; qb < QW; ++qb) {
-            const int lo01 = min(m[qb][0], m[qb][1]), hi01 = max(m[qb][0], m[qb][1]);
-            const int lo23 = min(m[qb][2], m[qb][3]), hi23 = max(m[qb][2], m[qb][3]);
-            const int a1 = min(lo01, lo23), a2 = min(max(lo01, lo23), min(hi01, hi23));
-            const int b1 = __shfl_xor(a1, 32), b2 = __shfl_xor(a2, 32);
-            const int v1 = min(a1, b1), v2 = min(max(a1, b1), min(a2, b2));
-            const int row = q0 + QW * rc + qb;
-            if (g == 0 && row < nb)
-                *reinterpret_cast<v2i *>(A.col + 2 * (A.col_off[u] + row)) = v2i{v1, v2};
-        }
-    }
-}
-
-#endif  // IAMX_ABLATE
 
 // ---------------------------------------------------------------------------------
 // candidates.  Pass 1 (symcand_rows_kernel, one thread per query row) visits the rows in SORTED
@@ -1127,7 +763,7 @@ struct CandArgs {
     int32_t *task_total;         // [2] wave tasks / workgroup tasks appended so far (zeroed by symcompact_kernel)
     int32_t *tasks;              // [..][2] (ordered pair, block): wave tasks from entry 0, workgroup tasks from entry n_pairs
     int32_t *d2;                 // [rows][2]: [.][1] of a candidate row = upper bound of its exact second distance
-    int wg_shift;                // log2 of the candidates of a workgroup task (8, or 9 for the four-set form)
+    int wg_shift;                // log2 of the candidates of a workgroup task (8; the exact kernels check it)
     // narrow exact stage (nar == NULL: off)
     const uint8_t *colmask;
     int8_t *nar;
@@ -1339,7 +975,7 @@ __global__ __launch_bounds__(256) void symcand_kernel(CandArgs A)
         return;
     }
     // two task lists in one buffer: a pair with <= 64 candidates is ONE wave's task (entries
-    // [0, n_pairs): at most one per pair), a pair with more gets workgroup tasks of 256 or 512 candidates
+    // [0, n_pairs): at most one per pair), a pair with more gets workgroup tasks of 256 candidates
     // whose four waves share every train tile through LDS (entries from n_pairs on)
     const bool small = out <= 64;
     const int ntask = small ? (out > 0 ? 1 : 0) : (out + (1 << A.wg_shift) - 1) >> A.wg_shift;
@@ -1606,7 +1242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const v2i task = *reinterpret_cast<const v2i *>(A.tasks + 2 * ((int64_t)A.n_pairs + t));
         const int p = __builtin_amdgcn_readfirstlane(task.x);
         const int ttag = __builtin_amdgcn_readfirstlane(task.y);
-        if ((ttag >> 24) != 8) {        // cut for the other form of this stage: refuse loudly
+        if ((ttag >> 24) != 8) {        // not cut to 256 candidates: refuse loudly
             if (threadIdx.x == 0) atomicAdd(A.zero_div + 1, 1);
             continue;
         }
@@ -1752,171 +1388,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     }
 }
 
-// The same scan with FOUR candidate sets per wave (a task = 512 candidates) at two waves per SIMD:
-// a train tile read from LDS feeds 16 MFMAs instead of 8, and the four accumulator chains are
-// independent, so the matrix pipe is kept busy by one wave where the two-set form needs its
-// neighbours (47 % MFMA busy there: waves parked on the tile barrier and LDS reads).
-template <int SUB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void symexact_wg4_kernel(ExactArgs A)
-{
-    constexpr int KEY_INVALID = 0x7FFFFFFF;
-    constexpr int NSET = 4;
-    constexpr int PR = 32 * SUB;
-    __shared__ __attribute__((aligned(16))) int8_t s_tile[2][PR * D];
-    __shared__ __attribute__((aligned(16))) int32_t s_key[2][PR];      // key_t & 511
-    __shared__ __attribute__((aligned(16))) int32_t s_half[2][PR];     // key_t >> 9 = norm_t >> 1
-    const int total = A.task_total[1];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane & 31, g = lane >> 5;
-    const int lrow = threadIdx.x >> 3, lchunk = threadIdx.x & 7;
-    for (int t = blockIdx.x; t < total; t += gridDim.x) {
-        const v2i task = *reinterpret_cast<const v2i *>(A.tasks + 2 * ((int64_t)A.n_pairs + t));
-        const int p = __builtin_amdgcn_readfirstlane(task.x);
-        const int ttag = __builtin_amdgcn_readfirstlane(task.y);
-        if ((ttag >> 24) != 9) {        // cut for the other form of this stage: refuse loudly
-            if (threadIdx.x == 0) atomicAdd(A.zero_div + 1, 1);
-            continue;
-        }
-        const int tblk = ttag & 0xFFFFFF;
-        const int64_t cb = A.out_off[p];
-        const int cnt = __builtin_amdgcn_readfirstlane(A.cand_cnt[p]);
-        const int qimg = A.pairs[2 * p], timg = A.pairs[2 * p + 1];
-        const int qoff = __builtin_amdgcn_readfirstlane(A.img_off[qimg]);
-        const int toff = __builtin_amdgcn_readfirstlane(A.img_off[timg]);
-        const int nt = __builtin_amdgcn_readfirstlane(A.img_n[timg]);
-        const int k_wave = (tblk * 4 + wave) * (32 * NSET);      // 4 waves x NSET sets of 32
-        const int left = cnt - k_wave;
-        const int n_sets = left <= 0 ? 0 : (left >= 32 * NSET ? NSET : (left + 31) >> 5);
-        int kq[NSET], q[NSET], hmax[NSET];
-        v4i bq[NSET][4];
-#pragma unroll
-        for (int h = 0; h < NSET; ++h) {
-            kq[h] = k_wave + h * 32 + c;
-            q[h] = A.cand_q[cb + (kq[h] < cnt ? kq[h] : cnt - 1)];
-            const v4i *src = reinterpret_cast<const v4i *>(A.desc + (int64_t)(qoff + q[h]) * D);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) bq[h][s] = ~src[2 * s + g];
-            hmax[h] = (A.d2[2 * (cb + q[h]) + 1] - A.norm_q[qoff + q[h]]) >> 1;
-        }
-        bool dirty = false;
-        const int8_t *tbase = A.desc + (int64_t)toff * D;
-        const int32_t *tkey = A.key_t + toff;
-        const int ntiles = (nt + 31) / 32;
-        int m1[NSET], m2[NSET], bd1[NSET], bi1[NSET], bd2[NSET], bi2[NSET];
-#pragma unroll
-        for (int h = 0; h < NSET; ++h) {
-            m1[h] = m2[h] = bd1[h] = bd2[h] = KEY_INVALID;
-            bi1[h] = bi2[h] = 0;
-        }
-        auto fetch = [&](int ph, v4i (&row16)[SUB], int &key) {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j)
-                row16[j] = *reinterpret_cast<const v4i *>(tbase + (int64_t)(ph * PR + j * 32 + lrow) * D + 16 * lchunk);
-            key = threadIdx.x < PR ? tkey[ph * PR + threadIdx.x] : 0;
-        };
-        auto stage = [&](int buf, const v4i (&row16)[SUB], int key) {
-#pragma unroll
-            for (int j = 0; j < SUB; ++j)
-                *reinterpret_cast<v4i *>(&s_tile[buf][(j * 32 + lrow) * D + 16 * (lchunk ^ ((lrow >> 1) & 7))]) = row16[j];
-            if (threadIdx.x < PR) {
-                s_key[buf][threadIdx.x] = key & 511;
-                s_half[buf][threadIdx.x] = key >> 9;
-            }
-        };
-        v4i pre[SUB];
-        int pre_key;
-        const int nph = (ntiles + SUB - 1) / SUB;
-        __syncthreads();
-        fetch(0, pre, pre_key);
-        stage(0, pre, pre_key);
-        __syncthreads();
-        for (int ph = 0; ph < nph; ++ph) {
-            const int buf = ph & 1;
-            if (ph + 1 < nph) fetch(ph + 1, pre, pre_key);
-#pragma unroll
-            for (int j = 0; j < SUB; ++j) {
-                const int tile = ph * SUB + j;
-                if (n_sets == 0 || tile >= ntiles) continue;
-                v4i a[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    a[s] = *reinterpret_cast<const v4i *>(&s_tile[buf][(j * 32 + c) * D + 16 * ((2 * s + g) ^ ((c >> 1) & 7))]);
-                v16i cin;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    const v4i th = *reinterpret_cast<const v4i *>(&s_half[buf][j * 32 + 8 * kk + 4 * g]);
-                    cin[4 * kk] = th.x; cin[4 * kk + 1] = th.y; cin[4 * kk + 2] = th.z; cin[4 * kk + 3] = th.w;
-                }
-                // (a set past n_sets repeats the pair's last candidate: computed, never used)
-                v16i acc[NSET];
-#pragma unroll
-                for (int h = 0; h < NSET; ++h)
-                    acc[h] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0], bq[h][0], cin, 0, 0, 0);
-#pragma unroll
-                for (int s = 1; s < 4; ++s)
-#pragma unroll
-                    for (int h = 0; h < NSET; ++h)
-                        acc[h] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[h][s], acc[h], 0, 0, 0);
-                const bool ragged = tile * 32 + 32 > nt;
-#pragma unroll
-                for (int h = 0; h < NSET; ++h) {
-                    const v16i &x = acc[h];
-                    const int t0 = min(min(x[0], x[1]), x[2]), t1 = min(min(x[3], x[4]), x[5]);
-                    const int t2 = min(min(x[6], x[7]), x[8]), t3 = min(min(x[9], x[10]), x[11]);
-                    const int t4 = min(min(x[12], x[13]), x[14]);
-                    const int lo = min(min(min(t0, t1), t2), min(min(t3, t4), x[15]));
-                    if (h >= n_sets || __ballot(lo <= hmax[h]) == 0ull) continue;
-                    dirty = true;
-                    v4i tk[4];
-#pragma unroll
-                    for (int kk = 0; kk < 4; ++kk)
-                        tk[kk] = *reinterpret_cast<const v4i *>(&s_key[buf][j * 32 + 8 * kk + 4 * g]);
-                    if (!ragged) {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            const int key = lshl9_add(x[reg], tk[reg >> 2][reg & 3]);
-                            m2[h] = med3_key(m1[h], m2[h], key);
-                            m1[h] = min(m1[h], key);
-                        }
-                    } else {
-#pragma unroll
-                        for (int reg = 0; reg < 16; ++reg) {
-                            const int row = tile * 32 + 8 * (reg >> 2) + 4 * g + (reg & 3);
-                            int key = lshl9_add(x[reg], tk[reg >> 2][reg & 3]);
-                            key = row < nt ? key : KEY_INVALID;
-                            m2[h] = med3_key(m1[h], m2[h], key);
-                            m1[h] = min(m1[h], key);
-                        }
-                    }
-                }
-                const int grow = toff + tile * 32;
-                if (dirty && (((grow + 32) & 255) == 0 || tile == ntiles - 1)) {
-                    dirty = false;
-                    const int sbase = (grow & ~255) - toff;
-#pragma unroll
-                    for (int h = 0; h < NSET; ++h) {
-                        const int d1k = m1[h] >> 8, i1k = sbase + (m1[h] & 255);
-                        const int d2k = m2[h] >> 8, i2k = sbase + (m2[h] & 255);
-                        if (d1k < bd1[h]) {
-                            if (d2k < bd1[h]) { bd2[h] = d2k; bi2[h] = i2k; }
-                            else              { bd2[h] = bd1[h]; bi2[h] = bi1[h]; }
-                            bd1[h] = d1k; bi1[h] = i1k;
-                        } else if (d1k < bd2[h]) {
-                            bd2[h] = d1k; bi2[h] = i1k;
-                        }
-                        m1[h] = m2[h] = KEY_INVALID;
-                    }
-                }
-            }
-            if (ph + 1 < nph) stage(buf ^ 1, pre, pre_key);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int h = 0; h < NSET; ++h)
-            exact_finish(A, p, cb, cnt, qoff, q[h], kq[h], g, bd1[h], bi1[h], bd2[h], bi2[h]);
-    }
-}
-
 // ---------------------------------------------------------------------------------
 // narrow exact stage: a task = up to 256 items (candidate, class) of one ordered pair and ONE
 // class, four waves x two sets of 32 as in symexact_wg_kernel; the class's rows come from the
@@ -1958,9 +1429,7 @@ struct NarArgs {
 constexpr int NAR_HALF_INVALID = 1 << 25;
 constexpr int NAR_D_INVALID = 0x7FFFFFFF;
 
-// ABL != 0: timing ablations (IAMX_NARROW_ABL; results are meaningless): 1 = no tile passes the
-// pruning test, 2 = and no MFMA
-template <int WPE, int ABL = 0>
+template <int WPE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void symnarrow_kernel(NarArgs A)
 {
     constexpr int SUB = 2, PR = 32 * SUB;
@@ -2101,22 +1570,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         if (h == 1 && n_sets < 2) break;
-                        v16i acc;
-                        if constexpr (ABL == 2) {
-                            acc = cin;
+                        v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0], bq[h][0], cin, 0, 0, 0);
 #pragma unroll
-                            for (int s = 0; s < 4; ++s) acc[s] += a[s][0] ^ bq[h][s][1];
-                        } else {
-                            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0], bq[h][0], cin, 0, 0, 0);
-#pragma unroll
-                            for (int s = 1; s < 4; ++s)
-                                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[h][s], acc, 0, 0, 0);
-                        }
+                        for (int s = 1; s < 4; ++s)
+                            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[h][s], acc, 0, 0, 0);
                         const int t0 = min(min(acc[0], acc[1]), acc[2]), t1 = min(min(acc[3], acc[4]), acc[5]);
                         const int t2 = min(min(acc[6], acc[7]), acc[8]), t3 = min(min(acc[9], acc[10]), acc[11]);
                         const int t4 = min(min(acc[12], acc[13]), acc[14]);
                         const int lo = min(min(min(t0, t1), t2), min(min(t3, t4), acc[15]));
-                        if (__ballot(lo <= (ABL ? -0x7FFFFFF0 : hmax[h])) == 0ull) continue;
+                        if (__ballot(lo <= hmax[h]) == 0ull) continue;
                         v4i tk[4];
 #pragma unroll
                         for (int kk = 0; kk < 4; ++kk)
@@ -2414,21 +1876,6 @@ extern "C" int iamx_knn2sym_sweep(const int8_t *sdesc, const int32_t *sn2, const
     return iamx::check_launch("iamx_knn2sym_sweep");
 }
 
-// the workgroup form of the exact stage the two entry points below agree on
-// (default: two candidate sets per wave, tasks of 256; IAMX_EXACT_SETS=4: four, tasks of 512)
-// Both entry points read the environment when they are called (tests and A/B tools switch forms
-// inside one process).  What ties them together is the task list itself: symcand_kernel writes
-// the granularity it cut the tasks to into every workgroup task (bits 24.. of the block index),
-// and the exact kernels refuse a task cut for the other form -- they raise the "unresolved rows"
-// flag, which find_matches turns into an exception, instead of mapping tasks to the wrong
-// candidates.
-static bool exact_four_sets()
-{
-    const char *e = getenv("IAMX_EXACT_SETS"), *pr = getenv("IAMX_EXACT_PRUNE");
-    if (pr && pr[0] == '0') return false;
-    return e && e[0] == '4';
-}
-
 // IAMX_EXACT_NARROW=0: every candidate through the full scan (A/B, tests)
 static bool narrow_enabled()
 {
@@ -2460,7 +1907,7 @@ extern "C" int iamx_knn2sym_candidates(const int32_t *sn2, const int32_t *sperm,
     IAMX_REQUIRE(form >= 0 && form <= 2, "form must be 0, 1 or 2");
     if (n_pairs <= 0) return IAMX_OK;
     CandArgs a{sn2, sperm, img_off, img_n, pairs, osrc, wg_off, col_off, rowp_off, out_off, col, rowp,
-               thresh, keep, cand_cnt, cand_q, task_total, tasks, d2, exact_four_sets() ? 9 : 8,
+               thresh, keep, cand_cnt, cand_q, task_total, tasks, d2, 8,
                colmask, narrow_enabled() ? static_cast<int8_t *>(nar) : nullptr, rows_total, n_pairs,
                iamx_knn2sym_rows_per_wg(form)};
     IAMX_REQUIRE(rows_total > 0 && rows_total < (1ll << 31), "rows_total = rows of all ordered pairs");
@@ -2503,19 +1950,9 @@ extern "C" int iamx_knn2sym_exact(const int8_t *desc, const int32_t *norm_q, con
                 task_total, tasks, thresh, d2, cand_t, cand_metric, cand_keep, zero_div};
     hipLaunchKernelGGL(symexact_kernel, dim3(1024), dim3(256), 0, st, a);       // pairs with <= 64 candidates
     // the others, 256 per workgroup (IAMX_EXACT_PRUNE=0: the unpruned scan, for A/B and tests)
-    const char *prune = getenv("IAMX_EXACT_PRUNE"), *sub = getenv("IAMX_EXACT_SUB");
-    const int nsub = sub ? atoi(sub) : 2;
-    if (exact_four_sets()) {
-        if (nsub == 1)
-            hipLaunchKernelGGL((symexact_wg4_kernel<1>), dim3(2048), dim3(256), 0, st, a);
-        else
-            hipLaunchKernelGGL((symexact_wg4_kernel<2>), dim3(2048), dim3(256), 0, st, a);
-    } else if (prune && prune[0] == '0')
+    const char *prune = getenv("IAMX_EXACT_PRUNE");
+    if (prune && prune[0] == '0')
         hipLaunchKernelGGL((symexact_wg_kernel<false, 1>), dim3(2048), dim3(256), 0, st, a);
-    else if (nsub == 1)
-        hipLaunchKernelGGL((symexact_wg_kernel<true, 1>), dim3(2048), dim3(256), 0, st, a);
-    else if (nsub == 4)
-        hipLaunchKernelGGL((symexact_wg_kernel<true, 4>), dim3(2048), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((symexact_wg_kernel<true, 2>), dim3(2048), dim3(256), 0, st, a);
     NarArgs nfin{};                                      // (nar == NULL: symcompact_kernel has nothing to merge)
@@ -2527,80 +1964,10 @@ extern "C" int iamx_knn2sym_exact(const int8_t *desc, const int32_t *norm_q, con
         NarArgs na{desc, norm_q, img_off, pairs, osrc, out_off, cand_q, d2, sdesc, sn2, sct, sperm, img_off3,
                    img_n, static_cast<int8_t *>(nar), rows_total, n_pairs, iamx_knn2sym_rows_per_wg(form),
                    cand_cnt, thresh, d2, cand_t, cand_metric, cand_keep, zero_div};
-        const char *wpe = getenv("IAMX_NARROW_WPE");
-        const char *abl = getenv("IAMX_NARROW_ABL");
-        if (abl && abl[0] == '1')
-            hipLaunchKernelGGL((symnarrow_kernel<3, 1>), dim3(768), dim3(256), 0, st, na);
-        else if (abl && abl[0] == '2')
-            hipLaunchKernelGGL((symnarrow_kernel<3, 2>), dim3(768), dim3(256), 0, st, na);
-        else if (wpe && wpe[0] == '2')
-            hipLaunchKernelGGL(symnarrow_kernel<2>, dim3(512), dim3(256), 0, st, na);
-        else
-            hipLaunchKernelGGL(symnarrow_kernel<3>, dim3(768), dim3(256), 0, st, na);
+        hipLaunchKernelGGL(symnarrow_kernel<3>, dim3(768), dim3(256), 0, st, na);
         nfin = na;
     }
     hipLaunchKernelGGL(symcompact_kernel, dim3((unsigned)n_pairs), dim3(256), 0, st, out_off,
                        cand_cnt, cand_keep, cand_q, cand_t, cand_metric, surv_cnt, task_total, nfin);
     return iamx::check_launch("iamx_knn2sym_exact");
 }
-
-#ifdef IAMX_ABLATE
-// timing ablations of the 1024-row form (not part of the C ABI; tools/knn2sym_ablate.py)
-extern "C" int iamxdbg_knn2sym_variant(int variant, const int8_t *sdesc, const int32_t *sn2,
-                                       const int32_t *sct, const int32_t *img_off,
-                                       const int32_t *img_n, const int32_t *upairs,
-                                       const int32_t *wg_off, const int64_t *col_off,
-                                       const int64_t *rowp_off, int n_u, int total_wg, int32_t *col,
-                                       int32_t *rowp, void *stream)
-{
-    SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, wg_off, col_off, rowp_off, col, rowp, n_u, total_wg};
-    const dim3 g((unsigned)total_wg);
-    hipStream_t st = iamx::as_stream(stream);
-    switch (variant) {
-#define V(id) case id: hipLaunchKernelGGL((knn2sym_kernel<4, 8, id>), g, dim3(512), 0, st, a); break;
-        V(0) V(1) V(2) V(3) V(4) V(5) V(8) V(11)
-#undef V
-    case 330: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 256 + 3, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 331: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 256 + 64 + 3, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 332: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 256 + 64 + 32 + 16 + 3, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 320: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 128, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 400: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 64, 6, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 401: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 64 + 32, 6, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 402: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 64 + 32 + 16, 6, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 403: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 64 + 3, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 404: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 3, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 310: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 5, 4, 0, true, 256>), g, dim3(512), 0, st, a); break;
-    case 311: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 5, 4, 0, true, 128>), g, dim3(512), 0, st, a); break;
-    case 300: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    // 8 query blocks per wave, ONE wave per SIMD (512 registers): the butterfly and the LDS operand
-    // reads are shared by twice the MFMAs (5.3 instead of 6.3 VALU per MFMA), no second wave to
-    // hide stalls.  Same 1024 B rows per workgroup, same tables.  (round 3: compiled, not measured)
-    case 600: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 6, 2, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-    case 601: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 5, 2, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-    case 602: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 0, 2, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-    case 603: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 4, 2, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-    case 604: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 7, 2, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-    case 605: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 5, 4, 0, true, 256, 1>), g, dim3(256), 0, st, a); break;
-    case 606: hipLaunchKernelGGL((knn2sym_kernel<8, 4, 0, 5, 4, 0, true, 128, 1>), g, dim3(256), 0, st, a); break;
-#define X(id, pipe, lo, hi) case id: hipLaunchKernelGGL((knn2sym_x_kernel<4, 8, pipe, lo, hi>), g, dim3(512), 0, st, a); break;
-        X(500, 6, 4, 4) X(501, 6, 4, 0) X(502, 6, 0, 0) X(503, 6, 5, 1) X(504, 6, 2, 2) X(505, 6, 4, 1)
-        X(506, 5, 4, 0) X(507, 7, 4, 0) X(508, 6, 5, 2) X(509, 6, 3, 0)
-#undef X
-    case 301: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 0, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 302: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 4, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 303: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 5, 2, 0, true>), g, dim3(512), 0, st, a); break;
-    case 200: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 4, 0>), g, dim3(512), 0, st, a); break;
-    case 201: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 2, 2>), g, dim3(512), 0, st, a); break;
-    case 202: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 2, 5>), g, dim3(512), 0, st, a); break;
-    case 203: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 4, 3>), g, dim3(512), 0, st, a); break;
-    case 204: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6, 8, 0>), g, dim3(512), 0, st, a); break;
-    case 16: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 16, 6>), g, dim3(512), 0, st, a); break;
-    case 48: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 48, 6>), g, dim3(512), 0, st, a); break;
-    case 100: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 4>), g, dim3(512), 0, st, a); break;
-    case 101: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 6>), g, dim3(512), 0, st, a); break;
-    case 102: hipLaunchKernelGGL((knn2sym_kernel<4, 8, 0, 8>), g, dim3(512), 0, st, a); break;
-    default: return iamx::fail(IAMX_EINVAL, "unknown variant");
-    }
-    return iamx::check_launch("iamxdbg_knn2sym_variant");
-}
-#endif

@@ -229,14 +229,13 @@ struct Args2 {
     int n_pairs, total_wg;
 };
 
-// VARIANT != 0: timing ablations (iamxdbg_knn2v2_variant): bit0 no epilogue, bit1 no MFMA,
-// bit2 no re-staging / barriers, bit3 operands without LDS traffic, bit4 = cost model of a
-// single sweep that also serves the reverse direction (per-row minima over the queries:
-// shift-add of the query term, running min per accumulator register, cross-lane DPP reduction
-// per tile, one store per row and tile) -- timing only, results meaningless
+// VARIANT is 0: its timing ablations (no epilogue, no MFMA, no re-staging, operands without LDS
+// traffic, the cost model of a sweep that also serves the reverse direction) were measured and
+// removed (profiles/r1_ubench_mfma_clock.txt).
 template <int VARIANT, int QW, int OCC, int NW = WAVES, bool BOUND = false, bool DLDS = false>
 __global__ __launch_bounds__(NW * 64, OCC) void knn2v2_kernel(Args2 A)
 {
+    static_assert(VARIANT == 0, "the timing ablations were removed");
     constexpr int QB = NW * QW * 32;
     constexpr int NT = NW * 64;
     constexpr int PIECES = CHUNK * D / 16 / NT;
@@ -331,11 +330,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void knn2v2_kernel(Args2 A)
     __syncthreads();
     for (int ch = 0; ch < nchunks; ++ch) {
         const int buf = ch & 1;
-        if constexpr (!(VARIANT & 4)) {
-            if (ch + 1 < nchunks) {
-                if constexpr (DLDS) stage_direct(ch + 1, buf ^ 1);
-                else load_chunk(ch + 1);
-            }
+        if (ch + 1 < nchunks) {
+            if constexpr (DLDS) stage_direct(ch + 1, buf ^ 1);
+            else load_chunk(ch + 1);
         }
         if (ch == ne_ch) {                 // class boundary: park the even class
 #pragma unroll
@@ -344,57 +341,46 @@ __global__ __launch_bounds__(NW * 64, OCC) void knn2v2_kernel(Args2 A)
                 m1[qb] = m2[qb] = BIG;
             }
         }
-        const int8_t *tile_base = lds_tile + ((VARIANT & 4) ? 0 : buf) * (CHUNK * D);
-        const int *tb_base = lds_tb + ((VARIANT & 4) ? 0 : buf) * CHUNK;
+        const int8_t *tile_base = lds_tile + buf * (CHUNK * D);
+        const int *tb_base = lds_tb + buf * CHUNK;
         // operands of tile t+1 are fetched from LDS before the MFMAs of tile t are issued
         auto load_ops = [&](int tile, v4i (&a)[4], v4i (&tbv)[4]) {
             const int r = tile * 32 + c, swz = (r >> 1) & 7;
-            if constexpr (VARIANT & 8) {       // ablation: operands without LDS traffic
 #pragma unroll
-                for (int s = 0; s < 4; ++s) { a[s] = bq[0][s] + ch + tile; tbv[s] = bq[1][s]; }
-            } else {
+            for (int s = 0; s < 4; ++s)
+                a[s] = *reinterpret_cast<const v4i *>(tile_base + r * D + (((2 * s + g) ^ swz) * 16));
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    a[s] = *reinterpret_cast<const v4i *>(tile_base + r * D + (((2 * s + g) ^ swz) * 16));
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    tbv[k] = *reinterpret_cast<const v4i *>(tb_base + tile * 32 + 8 * k + 4 * g);
-            }
+            for (int k = 0; k < 4; ++k)
+                tbv[k] = *reinterpret_cast<const v4i *>(tb_base + tile * 32 + 8 * k + 4 * g);
         };
         // C operand + 4 MFMAs (K = 128) of one 32x32 block
         auto chain = [&](v16i &acc, const v4i (&a)[4], const v4i (&tbv)[4], int qb) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) acc[reg] = tbv[reg >> 2][reg & 3];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if constexpr (VARIANT & 2) acc[s] += a[s][0] ^ bq[qb][s][1];
-                else acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qb][s], acc, 0, 0, 0);
-            }
+            for (int s = 0; s < 4; ++s)
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], bq[qb][s], acc, 0, 0, 0);
         };
         auto epilogue = [&](const v16i &acc, int qb, int tile_id) {
-            if constexpr (VARIANT & 1) {
-                asm volatile("" ::"v"(acc));
+            const int before = m1[qb];
+            if constexpr (BOUND) {
+                // (m1, m2) = two smallest 16-row group minima: 8 + 2 ops per 16 distances
+                int tm = min(min(acc[0], acc[1]), acc[2]);
+#pragma unroll
+                for (int reg = 3; reg < 15; reg += 2) tm = min(min(tm, acc[reg]), acc[reg + 1]);
+                tm = min(tm, acc[15]);
+                const int lo1 = min(m1[qb], tm);
+                m2[qb] = med3_after(m1[qb], m2[qb], tm, lo1);
+                m1[qb] = lo1;
             } else {
-                const int before = m1[qb];
-                if constexpr (BOUND) {
-                    // (m1, m2) = two smallest 16-row group minima: 8 + 2 ops per 16 distances
-                    int tm = min(min(acc[0], acc[1]), acc[2]);
 #pragma unroll
-                    for (int reg = 3; reg < 15; reg += 2) tm = min(min(tm, acc[reg]), acc[reg + 1]);
-                    tm = min(tm, acc[15]);
-                    const int lo1 = min(m1[qb], tm);
-                    m2[qb] = med3_after(m1[qb], m2[qb], tm, lo1);
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int lo1 = min(m1[qb], acc[reg]);
+                    m2[qb] = med3_after(m1[qb], m2[qb], acc[reg], lo1);
                     m1[qb] = lo1;
-                } else {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int lo1 = min(m1[qb], acc[reg]);
-                        m2[qb] = med3_after(m1[qb], m2[qb], acc[reg], lo1);
-                        m1[qb] = lo1;
-                    }
                 }
-                t1[qb] = m1[qb] < before ? tile_id : t1[qb];
             }
+            t1[qb] = m1[qb] < before ? tile_id : t1[qb];
         };
         v4i a[4], tbv[4];
         load_ops(0, a, tbv);
@@ -403,54 +389,23 @@ __global__ __launch_bounds__(NW * 64, OCC) void knn2v2_kernel(Args2 A)
             v4i a_nx[4], tb_nx[4];
             if (tile + 1 < CHUNK / 32) load_ops(tile + 1, a_nx, tb_nx);
             const int tile_id = ch * (CHUNK / 32) + tile;
-            int rowmin[16];
-            if constexpr (VARIANT & 16) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) rowmin[reg] = BIG;
-            }
 #pragma unroll
             for (int qb = 0; qb < QW; ++qb) {
                 v16i acc;
                 chain(acc, a, tbv, qb);
                 epilogue(acc, qb, tile_id);
-                if constexpr (VARIANT & 16) {
-                    const int nqv = bq[qb][0][0];                  // stands for norm_q of the column
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) rowmin[reg] = min(rowmin[reg], (acc[reg] << 1) + nqv);
-                }
-            }
-            if constexpr (VARIANT & 16) {
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    int v = rowmin[reg];
-                    v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));     // quad xor 1
-                    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));     // quad xor 2
-                    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true));    // row_half_mirror
-                    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true));    // row_mirror
-                    v = min(v, __shfl_xor(v, 16));
-                    rowmin[reg] = v;
-                }
-                if (c == 0) {
-                    const unsigned slot = ((unsigned)(vid * NW + wave) * 977u + (unsigned)tile_id) & 0xFFFFu;
-                    int *dst = A.out_tile + slot * 32 + g * 16;
-#pragma unroll
-                    for (int reg = 0; reg < 16; reg += 4)
-                        *reinterpret_cast<v4i *>(dst + reg) = v4i{rowmin[reg], rowmin[reg + 1], rowmin[reg + 2], rowmin[reg + 3]};
-                }
             }
             if (tile + 1 < CHUNK / 32) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) { a[s] = a_nx[s]; tbv[s] = tb_nx[s]; }
             }
         }
-        if constexpr (!(VARIANT & 4)) {
-            if constexpr (DLDS) {
-                wait_direct();
-            } else {
-                if (ch + 1 < nchunks) store_chunk(buf ^ 1);
-            }
-            __syncthreads();
+        if constexpr (DLDS) {
+            wait_direct();
+        } else {
+            if (ch + 1 < nchunks) store_chunk(buf ^ 1);
         }
+        __syncthreads();
     }
     if (nchunks == ne_ch) {                // no odd chunks at all: the running class is the even one
 #pragma unroll
@@ -733,64 +688,6 @@ extern "C" int iamx_knn2v2_pairs(const int8_t *desc_q, const int32_t *norm_q,
     else hipLaunchKernelGGL((knn2v2_kernel<0, QW_PRODUCT, 2, WAVES, true>), g, b, 0, st, a);
     return iamx::check_launch("iamx_knn2v2_pairs");
 }
-
-#ifdef IAMX_ABLATE   // scaffolding of tools/*_ablate.py: built into libiamx_ablate.so only
-extern "C" int iamxdbg_knn2v2_variant(int variant, const int8_t *desc_q, const int32_t *norm_q,
-                                      const int32_t *qimg_off, const int32_t *qimg_n,
-                                      const int8_t *desc_t, const int32_t *cinit,
-                                      const int32_t *timg_off, const int32_t *tmeta,
-                                      const int32_t *pairs, const int32_t *wg_off,
-                                      const int64_t *out_off, int n_pairs, int total_wg,
-                                      int32_t *out_d2, int32_t *out_tile, void *stream)
-{
-    Args2 a{desc_q, norm_q, qimg_off, qimg_n, desc_t, cinit, timg_off, tmeta, pairs, wg_off,
-            out_off, out_d2, out_tile, n_pairs, total_wg};
-    dim3 g((unsigned)total_wg), b(WAVES * 64);
-    hipStream_t st = iamx::as_stream(stream);
-    switch (variant) {
-    case 0: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 2>), g, b, 0, st, a); break;
-    case 1: hipLaunchKernelGGL((knn2v2_kernel<1, 2, 2>), g, b, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((knn2v2_kernel<2, 2, 2>), g, b, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((knn2v2_kernel<4, 2, 2>), g, b, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((knn2v2_kernel<5, 2, 2>), g, b, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((knn2v2_kernel<6, 2, 2>), g, b, 0, st, a); break;
-    case 13: hipLaunchKernelGGL((knn2v2_kernel<13, 2, 2>), g, b, 0, st, a); break;
-    case 12: hipLaunchKernelGGL((knn2v2_kernel<12, 2, 2>), g, b, 0, st, a); break;
-    case 9: hipLaunchKernelGGL((knn2v2_kernel<9, 2, 2>), g, b, 0, st, a); break;
-    case 30: hipLaunchKernelGGL((knn2v2_kernel<0, 3, 2>), g, b, 0, st, a); break;
-    case 31: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 2>), g, b, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 1>), g, b, 0, st, a); break;
-    case 33: hipLaunchKernelGGL((knn2v2_kernel<0, 1, 4>), g, b, 0, st, a); break;
-    case 34: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 3>), g, b, 0, st, a); break;
-    case 35: hipLaunchKernelGGL((knn2v2_kernel<1, 4, 2>), g, b, 0, st, a); break;
-    case 40: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 2, 8>), g, dim3(512), 0, st, a); break;
-    case 41: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 2, 8>), g, dim3(512), 0, st, a); break;
-    case 42: hipLaunchKernelGGL((knn2v2_kernel<0, 3, 2, 8>), g, dim3(512), 0, st, a); break;
-    case 43: hipLaunchKernelGGL((knn2v2_kernel<0, 1, 4, 8>), g, dim3(512), 0, st, a); break;
-    case 50: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 2, 4, true>), g, b, 0, st, a); break;
-    case 51: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 52: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 2, 8, true>), g, dim3(512), 0, st, a); break;
-    case 53: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 1, 4, true>), g, b, 0, st, a); break;
-    case 54: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 4, 4, true>), g, b, 0, st, a); break;
-    case 55: hipLaunchKernelGGL((knn2v2_kernel<0, 3, 2, 4, true>), g, b, 0, st, a); break;
-    case 56: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 2, 4, true, true>), g, b, 0, st, a); break;
-    case 57: hipLaunchKernelGGL((knn2v2_kernel<0, 2, 2, 4, true, true>), g, b, 0, st, a); break;
-    case 58: hipLaunchKernelGGL((knn2v2_kernel<0, 4, 2, 8, true, true>), g, dim3(512), 0, st, a); break;
-    case 59: hipLaunchKernelGGL((knn2v2_kernel<0, 3, 2, 4, true, true>), g, b, 0, st, a); break;
-    case 60: hipLaunchKernelGGL((knn2v2_kernel<1, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 70: hipLaunchKernelGGL((knn2v2_kernel<16, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 71: hipLaunchKernelGGL((knn2v2_kernel<16, 4, 1, 4, true>), g, b, 0, st, a); break;
-    case 72: hipLaunchKernelGGL((knn2v2_kernel<16, 2, 2, 4, true>), g, b, 0, st, a); break;
-    case 61: hipLaunchKernelGGL((knn2v2_kernel<4, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 62: hipLaunchKernelGGL((knn2v2_kernel<12, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 63: hipLaunchKernelGGL((knn2v2_kernel<13, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 64: hipLaunchKernelGGL((knn2v2_kernel<5, 4, 2, 4, true>), g, b, 0, st, a); break;
-    case 65: hipLaunchKernelGGL((knn2v2_kernel<2, 4, 2, 4, true>), g, b, 0, st, a); break;
-    default: return iamx::fail(IAMX_EINVAL, "unknown variant");
-    }
-    return iamx::check_launch("iamxdbg_knn2v2_variant");
-}
-#endif
 
 extern "C" int iamx_knn2v2_resolve(const int8_t *desc_q, const int32_t *norm_q,
                                    const int32_t *qimg_off, const int8_t *desc_t,

@@ -270,24 +270,6 @@ __global__ __launch_bounds__(256) void blur_strip_kernel(const float *__restrict
     }
 }
 
-// IAMX_DESC_FORM (read once; A/B measurements): descriptor_kernel<FORM, WAVES> -- 0 = <0, 8> (rounds 2-5),
-// 1 = <1, 6>, 25 = <2, 5>, 9 = <9, 4> (TIMING ONLY: form 2 with every gather from the window centre: 429 us,
-// what the kernel would take with its loads cache resident), anything else <2, 4> (shipped).  Same box, 2189 x 1459 detect image, 37 k
-// keypoints (profiles/r6h_sift_desc_ab.txt): 791-824 / 653-667 / 637-646 / 614-628 us; forms 1 and 2 at
-// eight waves per SIMD spill (1.8 / 2.1 ms), form 2 at six keeps 36 B of scratch in the loop (763 us).
-inline int desc_form()
-{
-    static const int f = [] { const char *e = getenv("IAMX_DESC_FORM"); return e && e[0] ? atoi(e) : 24; }();
-    return f;
-}
-
-// IAMX_DESC_SORT=0 (read once; A/B): the descriptor pass walks the keypoint list as orient_kernel left it
-inline bool desc_sorted()
-{
-    static const bool on = [] { const char *e = getenv("IAMX_DESC_SORT"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 inline int xcd_enabled()
 {
     static const int on = [] { const char *e = getenv("IAMX_SIFT_NO_XCD"); return (e && e[0] == '1') ? 0 : 1; }();
@@ -995,28 +977,32 @@ __global__ __launch_bounds__(256) void desc_bucket_scatter_kernel(const int *__r
 }
 
 // one wave per keypoint: calcSIFTDescriptor
-// (form 0 ran 8 waves per SIMD -- 64 VGPRs and 32 B of scratch instead of 86 VGPRs / 5 waves: it waited
+// (a first form ran 8 waves per SIMD -- 64 VGPRs and 32 B of scratch instead of 86 VGPRs / 5 waves: it waited
 //  on LDS atomics and image gathers more than it issued; 1.645 / 1.626 / 1.596 ms per detection at
-//  5 / 6 / 8 waves on one box, round 5.  Forms 1 and 2 issue: the counters of the third session say
+//  5 / 6 / 8 waves on one box, round 5.  This form issues: the counters of the third session say
 //  SQ_WAIT_INST_LDS 1.06e9 -> 2.3e7 wave cycles per launch, LDS-active cycles 3.1e8 -> 1.5e8, VALU
 //  instructions unchanged (2.96e8 -> 2.89e8: eight f64 adds replace the address arithmetic of
 //  eight atomics), VALU issue ~0.78 of the slots -- four waves per SIMD with 96 VGPRs are enough.)
 //
-// FORM (round 6, third session):
-//   0  every sample sends its eight terms to the histogram with eight f64 LDS atomics (rounds 2-5)
-//   1  RUN COMBINING: a lane walks consecutive samples of a window row, and consecutive samples mostly
+// Round 6, third session:
+//   RUN COMBINING: a lane walks consecutive samples of a window row, and consecutive samples mostly
 //      fall into the same (row bin, column bin, orientation bin) cell -- 0.61 of them on the 2189 x
 //      1459 detect image (gradient orientation is smooth at the keypoint's scale, a bin is ~6 pixels
 //      wide).  The lane keeps the eight f64 sums of its current cell in registers and sends them to
 //      LDS when the cell changes: 8 atomics per RUN instead of per sample.  Sums of float32 terms in
 //      float64 are exact in either grouping (the convention of the oracle: each bin = the exact sum
 //      of its terms, rounded to float32 once), so the result is the same bit for bit.
-//   2  form 1 + the row tables of the interval walk in registers: the lane reads the ends of its
-//      first three rows once, before the loop; the loop itself touches LDS only for the histogram
-//      (forms 0/1 read rowpre / rowlo for every sample, and each of those reads waits for the
-//      atomics queued before it); a lane that needs a fourth row or meets an empty one takes the
-//      LDS path for that step.
-template <int FORM, int WAVES>
+//   ROW TABLES IN REGISTERS: the lane reads the ends of its first three rows of the interval walk
+//      once, before the loop; the loop itself touches LDS only for the histogram (each read of
+//      rowpre / rowlo would wait for the atomics queued before it); a lane that needs a fourth row
+//      or meets an empty one takes the LDS path for that step.
+// The earlier forms -- eight f64 LDS atomics per sample (rounds 2-5), run combining without the
+// register row tables, and a timing-only form gathering every sample from the window centre
+// (429 us: the kernel with its loads cache resident) -- were measured and removed
+// (profiles/r6h_sift_desc_ab.txt: 791-824 / 653-667 / 614-628 us for the two earlier forms and
+// this one; at eight waves per SIMD the combining forms spill, at six this one keeps 36 B of
+// scratch in the loop).
+template <int WAVES>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void descriptor_kernel(PyrTable T, const float *__restrict__ kp,
                                                          const int *__restrict__ n_kp, int cap_k,
                                                          uint8_t *__restrict__ desc, int xcd,
@@ -1081,7 +1067,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
         const float bins_per_rad = n / 360.f, exp_scale = -1.f / (d * d * 0.5f);
         const float hist_width = 3.f * scl;
         int radius = cv_round(hist_width * 1.4142135623730951f * (d + 1) * 0.5f);
-        const int diag = FORM == 0 ? (int)sqrt((double)w * w + (double)h * h) : P.diag;
+        const int diag = P.diag;
         radius = radius < diag ? radius : diag;
         cos_t /= hist_width;
         sin_t /= hist_width;
@@ -1095,7 +1081,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             const float *pc = img + (int64_t)(py + i) * w + (px + j);
             return Grad{pc[-1], pc[1], pc[-w], pc[w]};
         };
-        // (forms 1, 2) the lane's current cell and its eight partial sums
+        // the lane's current cell and its eight partial sums
         double run[8];
         int run_base = -1;
         auto flush_run = [&]() {
@@ -1115,7 +1101,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             const float dx = g.xr - g.xl;
             const float dy = g.yu - g.yd;
             // (-1 < rbin, cbin < d: |r_rot|, |c_rot| < 2.5, the argument of exp32 is > -1.6)
-            const float wgt = exp32<FORM == 0>((c_rot * c_rot + r_rot * r_rot) * exp_scale);
+            const float wgt = exp32<false>((c_rot * c_rot + r_rot * r_rot) * exp_scale);
             const float og = fast_atan2_cv(dy, dx);
             const float mag = sqrtf(dx * dx + dy * dy) * wgt;
             const float obin = (og - ori) * bins_per_rad;
@@ -1123,56 +1109,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             const int r0 = (int)fr0, c0 = (int)fc0;
             int o0 = (int)fo0;
             const float fr = rbin - fr0, fc = cbin - fc0, fo = obin - fo0;
-            if (FORM == 0) {
-                if (o0 < 0) o0 += n;
-                if (o0 >= n) o0 -= n;
-            } else {
-                o0 &= n - 1;           // (og, ori in [0, 360]: -8 <= o0 <= 8, the same wrap in one instruction)
-            }
+            o0 &= n - 1;               // (og, ori in [0, 360]: -8 <= o0 <= 8, OpenCV's wrap in one instruction)
             const float v_r1 = mag * fr, v_r0 = mag - v_r1;
+            // OpenCV's trilinear products and differences two at a time (v_pk_mul_f32 /
+            // v_pk_add_f32: separately rounded, like its scalar code)
+            typedef float f2 __attribute__((ext_vector_type(2)));
+            const f2 vr = {v_r0, v_r1};
+            const f2 c1 = vr * fc;                  // v_rc01, v_rc11
+            const f2 c0v = vr - c1;                 // v_rc00, v_rc10
+            const f2 c1o = c1 * fo, c0o = c0v * fo;
+            const f2 c1r = c1 - c1o, c0r = c0v - c0o;
             float vv[4], v1s[4];
-            if (FORM == 0) {
-                const float v_rc11 = v_r1 * fc, v_rc10 = v_r1 - v_rc11;
-                const float v_rc01 = v_r0 * fc, v_rc00 = v_r0 - v_rc01;
-                vv[0] = v_rc00; vv[1] = v_rc01; vv[2] = v_rc10; vv[3] = v_rc11;
-            } else {
-                // the same products and differences two at a time (v_pk_mul_f32 / v_pk_add_f32:
-                // separately rounded, like the scalar form)
-                typedef float f2 __attribute__((ext_vector_type(2)));
-                const f2 vr = {v_r0, v_r1};
-                const f2 c1 = vr * fc;                  // v_rc01, v_rc11
-                const f2 c0v = vr - c1;                 // v_rc00, v_rc10
-                const f2 c1o = c1 * fo, c0o = c0v * fo;
-                const f2 c1r = c1 - c1o, c0r = c0v - c0o;
-                vv[0] = c0r.x; vv[1] = c1r.x; vv[2] = c0r.y; vv[3] = c1r.y;        // vv[q] - v1
-                v1s[0] = c0o.x; v1s[1] = c1o.x; v1s[2] = c0o.y; v1s[3] = c1o.y;    // v1 = vv[q] * fo
-            }
-            if (FORM == 0) {
+            vv[0] = c0r.x; vv[1] = c1r.x; vv[2] = c0r.y; vv[3] = c1r.y;        // vv[q] - v1
+            v1s[0] = c0o.x; v1s[1] = c1o.x; v1s[2] = c0o.y; v1s[3] = c1o.y;    // v1 = vv[q] * fo
+            // (24-bit multiplies: full rate, the 32-bit v_mul_lo_u32 is a quarter of that)
+            const int base = __mul24(r0 + 1, (d + 2) * (n + 2)) + __mul24(c0 + 1, n + 2) + o0;
+            if (base != run_base) {
+                flush_run();
+                run_base = base;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
-                    const int rr = r0 + 1 + (q4 >> 1), cc = c0 + 1 + (q4 & 1);
-                    const int base = (rr * (d + 2) + cc) * (n + 2) + o0;
-                    const float v1 = vv[q4] * fo;
-                    atomicAdd(&hist[base], (double)(vv[q4] - v1));
-                    atomicAdd(&hist[base + 1], (double)v1);
+                    run[2 * q4] = (double)vv[q4];
+                    run[2 * q4 + 1] = (double)v1s[q4];
                 }
             } else {
-                // (24-bit multiplies: full rate, the 32-bit v_mul_lo_u32 is a quarter of that)
-                const int base = __mul24(r0 + 1, (d + 2) * (n + 2)) + __mul24(c0 + 1, n + 2) + o0;
-                if (base != run_base) {
-                    flush_run();
-                    run_base = base;
 #pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        run[2 * q4] = (double)vv[q4];
-                        run[2 * q4 + 1] = (double)v1s[q4];
-                    }
-                } else {
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        run[2 * q4] += (double)vv[q4];
-                        run[2 * q4 + 1] += (double)v1s[q4];
-                    }
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    run[2 * q4] += (double)vv[q4];
+                    run[2 * q4 + 1] += (double)v1s[q4];
                 }
             }
         };
@@ -1188,7 +1152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             int *rowlo = rowlo_s[wave], *rowpre = rowpre_s[wave];
             int carry = 0;
             const double cos_d = (double)cos_t, sin_d = (double)sin_t;
-            // (FORM >= 1: the bounds through one reciprocal per constraint instead of four f64
+            // (the bounds through one reciprocal per constraint instead of four f64
             //  divisions per row -- the interval only has to CONTAIN the samples that pass the float32
             //  test in accumulate(); floor / ceil leave a column of slack, an error of 1e-13 in a
             //  bound moves it by a column only where the bound is that close to an integer, and then
@@ -1208,14 +1172,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
 #pragma unroll
                         for (int e = 0; e < 2; ++e) {
                             if (fabs(aa[e]) < 1e-9) continue;          // no usable bound: keep all
-                            double x1, x2;
-                            if (FORM == 0) {
-                                x1 = (-1.0 - bb[e]) / aa[e];
-                                x2 = ((double)d - bb[e]) / aa[e];
-                            } else {
-                                x1 = (-1.0 - bb[e]) * inv_a[e];
-                                x2 = ((double)d - bb[e]) * inv_a[e];
-                            }
+                            double x1 = (-1.0 - bb[e]) * inv_a[e];
+                            double x2 = ((double)d - bb[e]) * inv_a[e];
                             if (x1 > x2) { const double t = x1; x1 = x2; x2 = t; }
                             lo = fmax(lo, floor(x1));
                             hi = fmin(hi, ceil(x2));
@@ -1247,25 +1205,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
             // listed position lies inside the image (the intervals are clipped), so the loads
             // need no test.
             int row = 0;
-            if (FORM < 2) {
             if (s0 < s1) {
-                while (s0 >= rowpre[row + 1]) ++row;
-                int ci = row - radius, cj = rowlo[row] + (s0 - rowpre[row]);
-                Grad cg = fetch(ci, cj);
-                for (int s = s0; s < s1; ++s) {
-                    int ni = ci, nj = cj;
-                    Grad ng = cg;
-                    if (s + 1 < s1) {
-                        while (s + 1 >= rowpre[row + 1]) ++row;
-                        ni = row - radius;
-                        nj = rowlo[row] + (s + 1 - rowpre[row]);
-                        ng = fetch(ni, nj);
-                    }
-                    accumulate(ci, cj, cg);
-                    ci = ni; cj = nj; cg = ng;
-                }
-            }
-            } else if (s0 < s1) {
                 // first row with rowpre[row + 1] > s0 (rows may be empty: rowpre is non-decreasing)
                 int lo = 0, hi = side - 1;
                 while (lo < hi) {
@@ -1314,10 +1254,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
                                 pn = img + (int64_t)(py + ni) * w + (px + nj);
                             }
                         }
-                        if (FORM == 9) {      // timing only: every gather from the window centre (cache resident)
-                            const float *pz = img + (int64_t)py * w + px;
-                            ng = Grad{pz[-1], pz[1], pz[-w], pz[w]};
-                        } else
                         ng = Grad{pn[-1], pn[1], pn[-w], pn[w]};
                     }
                     accumulate(ci, cj, cg);
@@ -1331,7 +1267,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
                 sample(i0 - radius, s - i0 * side - radius);
             }
         }
-        if (FORM >= 1) flush_run();
+        flush_run();
     }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xc07f);           // lgkmcnt(0): the LDS atomics have landed
@@ -1354,51 +1290,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_waitcnt(0xc07f);
         // the two norms are OpenCV's scalar loops: sequential float32 sums over k = 0 .. 127
-        if (FORM == 0) {
+        // ... of which only the ADDITIONS are sequential: every lane squares its own two values
+        // (the same float32 products), lane 0 adds the 128 squares in order -- 2 x 128 dependent
+        // additions instead of 2 x 128 x (compare, multiply, add) on one lane while 63 wait (a
+        // sixth of the kernel's instruction slots for a keypoint of the first layer)
+        float *sq = sq_s[wave];
+        sq[lane * 2] = v[0] * v[0];
+        sq[lane * 2 + 1] = v[1] * v[1];
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);
         if (lane == 0) {
             float nrm2 = 0.f;
-            for (int t = 0; t < d * d * n; ++t) nrm2 += raw[t] * raw[t];
-            const float thr = sqrtf(nrm2) * 0.2f;
-            nrm2 = 0.f;
-            for (int t = 0; t < d * d * n; ++t) {
-                const float val = raw[t] < thr ? raw[t] : thr;
-                nrm2 += val * val;
-            }
-            const float s2 = sqrtf(nrm2);
-            raw[d * d * n] = thr;
-            raw[d * d * n + 1] = 512.f / (s2 > 1.1920929e-07f ? s2 : 1.1920929e-07f);
+            for (int t = 0; t < d * d * n; ++t) nrm2 += sq[t];
+            raw[d * d * n] = sqrtf(nrm2) * 0.2f;
         }
-        } else {
-            // ... of which only the ADDITIONS are sequential: every lane squares its own two values
-            // (the same float32 products), lane 0 adds the 128 squares in order -- 2 x 128 dependent
-            // additions instead of 2 x 128 x (compare, multiply, add) on one lane while 63 wait (a
-            // sixth of the kernel's instruction slots for a keypoint of the first layer)
-            float *sq = sq_s[wave];
-            sq[lane * 2] = v[0] * v[0];
-            sq[lane * 2 + 1] = v[1] * v[1];
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (lane == 0) {
-                float nrm2 = 0.f;
-                for (int t = 0; t < d * d * n; ++t) nrm2 += sq[t];
-                raw[d * d * n] = sqrtf(nrm2) * 0.2f;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            const float thr0 = raw[d * d * n];
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        const float thr0 = raw[d * d * n];
 #pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float val = v[e] < thr0 ? v[e] : thr0;
-                sq[lane * 2 + e] = val * val;
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (lane == 0) {
-                float nrm2 = 0.f;
-                for (int t = 0; t < d * d * n; ++t) nrm2 += sq[t];
-                const float s2 = sqrtf(nrm2);
-                raw[d * d * n + 1] = 512.f / (s2 > 1.1920929e-07f ? s2 : 1.1920929e-07f);
-            }
+        for (int e = 0; e < 2; ++e) {
+            const float val = v[e] < thr0 ? v[e] : thr0;
+            sq[lane * 2 + e] = val * val;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        if (lane == 0) {
+            float nrm2 = 0.f;
+            for (int t = 0; t < d * d * n; ++t) nrm2 += sq[t];
+            const float s2 = sqrtf(nrm2);
+            raw[d * d * n + 1] = 512.f / (s2 > 1.1920929e-07f ? s2 : 1.1920929e-07f);
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -1709,48 +1629,10 @@ SideStream *side_stream()
 }
 }  // namespace
 
-// Everything of a detection behind the first kernel (which reads the caller's image), enqueued on
-// `st` and, for the small octaves, on this thread's side stream -- ~65 launches for a 3 MP frame.
-static int sift_enqueue_pyramid(const Layout &L, float contrast_threshold, float edge_threshold,
-                                float sigma, char *ws, float *kp, uint8_t *desc, int cap,
-                                int32_t *n_out, hipStream_t st);
-
-// The launch sequence of a frame size never changes (grids are sized by capacity, counts live
-// on the device) and every pointer in it belongs to the caller's per-detector workspace / output
-// buffers, so it CAN be captured once into a HIP graph per (frame size, parameters, buffers) and
-// replayed: one submission instead of ~65.  The first kernel (gray_up2x: the only reader of the
-// image, whose address changes from frame to frame) stays a plain launch in front of the graph.
-// OPT-IN (IAMX_SIFT_GRAPH=1), because it does not pay on MI355X / ROCm 7 (round 5,
-// profiles/r5_sift_graph_ab.txt): in steady state the ~65 plain launches cost the host 0.12 ms per
-// frame and the stream is kernel bound either way -- 1.773 ms per detection replayed against
-// 1.781 ms launched --, and with eight detector threads in flight the replayed graphs serialise
-// where plain launches of different frames interleave: 2.02 against 1.51 ms per detection.  (The
-// "0.6 ms of launch gaps per frame" of round 4 was an artefact of timing four cold detections.)
-namespace {
-struct GraphKey {
-    int height, width, cap, xcd;
-    float ct, et, sigma;
-    void *ws, *kp, *desc, *n_out;
-    int device;
-};
-struct GraphSlot {
-    GraphKey key;
-    hipGraphExec_t exec;
-    uint64_t stamp;
-    bool used;
-};
-constexpr int GRAPH_SLOTS = 12;
-
-inline bool graph_enabled()
-{
-    static const bool on = []() {
-        const char *e = getenv("IAMX_SIFT_GRAPH");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-}  // namespace
-
+// A detection: ~65 launches for a 3 MP frame, on `st` and, for the small octaves, on this thread's
+// side stream.  (Capturing everything behind the first kernel into a replayed graph was measured
+// and removed: no gain on one stream, 2.02 against 1.51 ms per detection with eight detector
+// threads in flight, where replayed graphs serialise -- profiles/r5_sift_graph_ab.txt.)
 extern "C" int iamx_sift_detect(const uint8_t *image, int height, int width, int channels,
                                 float contrast_threshold, float edge_threshold, float sigma,
                                 void *workspace, int64_t workspace_bytes, float *kp, uint8_t *desc,
@@ -1763,68 +1645,9 @@ extern "C" int iamx_sift_detect(const uint8_t *image, int height, int width, int
     IAMX_REQUIRE(workspace_bytes >= L.total, "workspace too small (iamx_sift_workspace_bytes)");
     hipStream_t st = iamx::as_stream(stream);
     char *ws = static_cast<char *>(workspace);
-    // base image, part 1: gray -> x2 (reads the caller's image: outside the graph)
+    // base image, part 1: gray -> x2
     hipLaunchKernelGGL(gray_up2x_kernel, dim3(blocks((int64_t)L.h[0] * L.w[0], 256)), dim3(256), 0, st,
                        image, height, width, channels, reinterpret_cast<float *>(ws + L.up_off));
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (!graph_enabled() || hipStreamIsCapturing(st, &cap_status) != hipSuccess ||
-        cap_status != hipStreamCaptureStatusNone)
-        return sift_enqueue_pyramid(L, contrast_threshold, edge_threshold, sigma, ws, kp, desc, cap,
-                                    n_out, st);
-    static thread_local GraphSlot slots[GRAPH_SLOTS];
-    static thread_local uint64_t clock_ = 0;
-    GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.height = height; key.width = width; key.cap = cap; key.xcd = xcd_enabled();
-    key.ct = contrast_threshold; key.et = edge_threshold; key.sigma = sigma;
-    key.ws = workspace; key.kp = kp; key.desc = desc; key.n_out = n_out;
-    (void)hipGetDevice(&key.device);
-    GraphSlot *hit = nullptr, *victim = &slots[0];
-    for (GraphSlot &g : slots) {
-        if (g.used && memcmp(&g.key, &key, sizeof(key)) == 0) { hit = &g; break; }
-        if (!g.used || (victim->used && g.stamp < victim->stamp)) victim = &g;
-    }
-    if (!hit) {
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            (void)hipGetLastError();
-            return sift_enqueue_pyramid(L, contrast_threshold, edge_threshold, sigma, ws, kp, desc,
-                                        cap, n_out, st);
-        }
-        const int rc = sift_enqueue_pyramid(L, contrast_threshold, edge_threshold, sigma, ws, kp, desc,
-                                            cap, n_out, st);
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        const hipError_t e1 = hipStreamEndCapture(st, &graph);
-        if (rc != IAMX_OK) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (e1 != hipSuccess || !graph ||
-            hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            // the runtime refused (the capture left nothing on the stream): plain launches
-            (void)hipGetLastError();
-            if (graph) (void)hipGraphDestroy(graph);
-            return sift_enqueue_pyramid(L, contrast_threshold, edge_threshold, sigma, ws, kp, desc,
-                                        cap, n_out, st);
-        }
-        (void)hipGraphDestroy(graph);
-        if (victim->used) (void)hipGraphExecDestroy(victim->exec);
-        victim->key = key;
-        victim->exec = exec;
-        victim->used = true;
-        hit = victim;
-    }
-    hit->stamp = ++clock_;
-    if (hipGraphLaunch(hit->exec, st) != hipSuccess)
-        return iamx::fail(IAMX_ELAUNCH, "iamx_sift_detect: hipGraphLaunch: %s",
-                          hipGetErrorString(hipGetLastError()));
-    return iamx::check_launch("iamx_sift_detect");
-}
-
-static int sift_enqueue_pyramid(const Layout &L, float contrast_threshold, float edge_threshold,
-                                float sigma, char *ws, float *kp, uint8_t *desc, int cap,
-                                int32_t *n_out, hipStream_t st)
-{
     PyrTable T;
     T.n_oct = L.n_oct;
     for (int o = 0; o < L.n_oct; ++o) {
@@ -1843,7 +1666,7 @@ static int sift_enqueue_pyramid(const Layout &L, float contrast_threshold, float
     // once refine_kernel has run); a capacity that does not fit there keeps the list order
     int *bucket_cnt = reinterpret_cast<int *>(ws + L.bucket_off);
     int *xcd_start = bucket_cnt + DB_BUCKETS;
-    const bool sorted_pass = desc_sorted() && (int64_t)cap * 20 <= (int64_t)CAP_CAND * (int64_t)sizeof(Cand);
+    const bool sorted_pass = (int64_t)cap * 20 <= (int64_t)CAP_CAND * (int64_t)sizeof(Cand);
     if (sorted_pass) (void)hipMemsetAsync(bucket_cnt, 0, (size_t)(DB_BUCKETS + 16) * 4, st);
 
     // OpenCV's sigma is a double (1.6); the ABI carries a float, whose widening (1.60000002...)
@@ -1980,13 +1803,7 @@ static int sift_enqueue_pyramid(const Layout &L, float contrast_threshold, float
                                bucket_cnt, kb, kr, pm);
             perm = pm;
         }
-        switch (desc_form()) {
-        case 0: hipLaunchKernelGGL((descriptor_kernel<0, 8>), dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp); break;
-        case 1: hipLaunchKernelGGL((descriptor_kernel<1, 6>), dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp); break;
-        case 9: hipLaunchKernelGGL((descriptor_kernel<9, 4>), dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp); break;
-        case 25: hipLaunchKernelGGL((descriptor_kernel<2, 5>), dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp); break;
-        default: hipLaunchKernelGGL((descriptor_kernel<2, 4>), dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp); break;
-        }
+        hipLaunchKernelGGL(descriptor_kernel<4>, dg, dim3(256), 0, st, T, kp, n_out, cap, desc, 0, perm, xcd_start, csp);
     }
     return iamx::check_launch("iamx_sift_detect");
 }

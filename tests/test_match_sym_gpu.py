@@ -408,10 +408,9 @@ def test_sym_keypoint_counts_of_full_resolution_frames():
         assert np.array_equal(res['d2'][res['off'][p] + keep], rd2)
 
 
-@pytest.mark.parametrize('prune,sets', [('1', '4'), ('1', '2'), ('0', '2')],
-                         ids=['pruned-4-sets', 'pruned-2-sets', 'unpruned'])
+@pytest.mark.parametrize('prune', ['1', '0'], ids=['pruned-2-sets', 'unpruned'])
 @pytest.mark.parametrize('sizes', [(5000, 4097), (700, 20000), (4096, 4096, 333)])
-def test_exact_stage_with_many_candidates(sizes, prune, sets, monkeypatch):
+def test_exact_stage_with_many_candidates(sizes, prune, monkeypatch):
     """Pairs whose rows mostly MATCH (real frames of one scene: a third to two thirds of a pair's
     rows are candidates) go through the workgroup form of the exact stage -- 256 candidates per
     task, train tiles shared through LDS -- and pairs with <= 64 candidates through the wave form;
@@ -420,10 +419,9 @@ def test_exact_stage_with_many_candidates(sizes, prune, sets, monkeypatch):
     exact duplicates (ties -> lowest train row), a candidate count that is not a multiple of 32.
     All scans of the workgroup form: the one that skips tiles no lane can have its best or second
     in (the candidate test's upper bound of the second distance) with two candidate sets per wave
-    and tasks of 256 (shipped) or four and 512, and the full scan."""
+    and tasks of 256 (shipped), and the full scan."""
     from imageanalysis_amd import kernels
     monkeypatch.setenv('IAMX_EXACT_PRUNE', prune)
-    monkeypatch.setenv('IAMX_EXACT_SETS', sets)
     rng = np.random.default_rng(sum(sizes))
     imgs = [_sift_like(rng, sizes[0])]
     for n in sizes[1:]:

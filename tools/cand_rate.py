@@ -55,9 +55,8 @@ for it in range(10):
     torch.cuda.synchronize()
     tt[0] += ev[0].elapsed_time(ev[1]) / 10
     tt[1] += ev[1].elapsed_time(ev[2]) / 10
-print('sweep %.3f ms, filter + exact stage %.3f ms (IAMX_EXACT_NARROW=%s IAMX_NARROW_ABL=%s IAMX_NARROW_WPE=%s)'
-      % (tt[0], tt[1], os.environ.get('IAMX_EXACT_NARROW', '1'), os.environ.get('IAMX_NARROW_ABL', '0'),
-         os.environ.get('IAMX_NARROW_WPE', '3')))
+print('sweep %.3f ms, filter + exact stage %.3f ms (IAMX_EXACT_NARROW=%s)'
+      % (tt[0], tt[1], os.environ.get('IAMX_EXACT_NARROW', '1')))
 cand = ws.seg_count[:pb.n_pairs].cpu().numpy()
 surv = ws.surv_cnt[:pb.n_pairs].cpu().numpy()
 rows = np.array([len(des[a]) for a, _b in ordered])
