@@ -98,6 +98,10 @@ SIGNATURES = {
     'iamx_ba_residual_jac': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                      c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    'iamx_ba_reproj_stats': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_int64] + [c_void_p] * 7),
+    'iamx_ba_mark_outliers': (c_int, [c_void_p, c_int64, c_double, c_int, c_double, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p]),
     'iamx_image_prep_workspace_bytes': (c_int64, [c_int, c_int]),
     'iamx_image_resized_dims': (c_int, [c_int, c_int, c_double, c_void_p, c_void_p]),
     'iamx_image_equalize_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_double,

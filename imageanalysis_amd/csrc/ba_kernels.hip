@@ -596,3 +596,353 @@ extern "C" int iamx_hbm_copy16(const void *src, void *dst, int64_t n16, int read
     }
     return iamx::check_launch("iamx_hbm_copy16");
 }
+
+// ------------------------------------------------------------------------------------------------
+// K3 report: reprojection-error statistics and outlier marking (scripts/4b-mre-by-image.py:60-150)
+//
+// Pass 1 (iamx_ba_reproj_stats): one workgroup per camera walks the camera's contiguous range of
+// the camera-major observation list, projects every observation exactly as ba_residual_kernel does
+// (residual_obs below, compiled under the same contraction rules as the residual kernel) and keeps
+// per thread sum / max of e = |(du, dv)|, sum / max of |du|, |dv| and a Welford (n, mean, M2) of
+// the signed residual.  The workgroup reduces them in a fixed tree order into the camera's row
+// and its partial; a single workgroup then reduces the camera partials in a fixed order (Chan's
+// pairwise merge for the variance).  No residual vector is written, no floating-point atomics.
+// Pass 2 (iamx_ba_mark_outliers): sum (mre - e)^2 per 2048-observation tile, reduce, threshold,
+// flag, count per tile, scan, scatter: the flagged observations in ascending order.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ double2 residual_obs(const double *__restrict__ cam,
+                                                const double *__restrict__ X, double2 obs,
+                                                const double (&cal)[9])
+{
+    Proj P;
+    project_obs(cam, X, cal, P);
+    return make_double2(obs.x - P.u, obs.y - P.v);        // = ba_residual_kernel
+}
+
+}  // namespace
+
+// the statistics restate numpy expressions: separately rounded multiply and add from here on
+// (the projection above keeps the residual kernel's arithmetic)
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int MRE_TILE = 2048;          // pass-2 observations per workgroup (8 per thread)
+
+__device__ __forceinline__ double nan_max(double a, double b)
+{
+    // np.amax: a NaN anywhere is the result
+    return a != a ? a : ((b != b || b > a) ? b : a);
+}
+
+__device__ __forceinline__ void welford_add(double &n, double &m, double &m2, double x)
+{
+    n += 1.0;
+    const double d = x - m;
+    m += d / n;
+    m2 += d * (x - m);
+}
+
+__device__ __forceinline__ void chan_merge(double &na, double &ma, double &m2a, double nb, double mb,
+                                           double m2b)
+{
+    if (nb == 0.0) return;
+    if (na == 0.0) { na = nb; ma = mb; m2a = m2b; return; }
+    const double n = na + nb, d = mb - ma;
+    ma = ma + d * (nb / n);
+    m2a = m2a + m2b + d * d * (na * nb / n);
+    na = n;
+}
+
+// fixed-order tree over the 256 threads of a workgroup: sums in s[0..2], max in s[3..4],
+// Welford triple in s[5..7]; the result lands in row 0
+__device__ __forceinline__ void reduce_stats(double (&s)[8][256], int t)
+{
+    for (int h = 128; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) {
+            s[0][t] += s[0][t + h];
+            s[1][t] += s[1][t + h];
+            s[2][t] += s[2][t + h];
+            s[3][t] = nan_max(s[3][t], s[3][t + h]);
+            s[4][t] = nan_max(s[4][t], s[4][t + h]);
+            double n = s[5][t], m = s[6][t], m2 = s[7][t];
+            chan_merge(n, m, m2, s[5][t + h], s[6][t + h], s[7][t + h]);
+            s[5][t] = n; s[6][t] = m; s[7][t] = m2;
+        }
+    }
+    __syncthreads();
+}
+
+// grid = n_cams workgroups.  part[c] = (sum e, count, sum |r|, max e, max |r|, n_r, mean_r, M2_r)
+__global__ __launch_bounds__(256) void ba_reproj_cam_kernel(
+    const double *__restrict__ cams, const double *__restrict__ pts,
+    const int32_t *__restrict__ cam_idx, const int32_t *__restrict__ pt_idx,
+    const double *__restrict__ uv, int64_t n_obs, const double *__restrict__ calib,
+    const int64_t *__restrict__ cam_ptr, double *__restrict__ cam_stats,
+    double *__restrict__ part, double *__restrict__ e_out)
+{
+    __shared__ double s[8][256];
+    const int c = blockIdx.x, t = threadIdx.x;
+    // (clamped: a malformed cam_ptr cannot send the walk outside [0, n_obs))
+    int64_t lo = cam_ptr[c], hi = cam_ptr[c + 1];
+    lo = lo < 0 ? 0 : (lo > n_obs ? n_obs : lo);
+    hi = hi < lo ? lo : (hi > n_obs ? n_obs : hi);
+    double cal[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cal[i] = calib[i];
+    double se = 0.0, sa = 0.0, me = 0.0, ma = 0.0, wn = 0.0, wm = 0.0, w2 = 0.0;
+    for (int64_t o = lo + t; o < hi; o += 256) {
+        const double2 obs = *reinterpret_cast<const double2 *>(uv + 2 * o);
+        const double2 r = residual_obs(cams + (int64_t)cam_idx[o] * 7, pts + (int64_t)pt_idx[o] * 3,
+                                       obs, cal);
+        const double e = sqrt(r.x * r.x + r.y * r.y);         // np.linalg.norm of the 2-vector
+        if (e_out) e_out[o] = e;
+        se += e;
+        me = nan_max(me, e);
+        sa += fabs(r.x);
+        sa += fabs(r.y);
+        ma = nan_max(ma, nan_max(fabs(r.x), fabs(r.y)));
+        welford_add(wn, wm, w2, r.x);
+        welford_add(wn, wm, w2, r.y);
+    }
+    s[0][t] = se; s[1][t] = 0.0; s[2][t] = sa; s[3][t] = me; s[4][t] = ma;
+    s[5][t] = wn; s[6][t] = wm; s[7][t] = w2;
+    reduce_stats(s, t);
+    if (t == 0) {
+        const double cnt = (double)(hi - lo);
+        cam_stats[3 * c + 0] = cnt > 0 ? s[0][0] / cnt : 0.0;
+        cam_stats[3 * c + 1] = cnt > 0 ? s[3][0] : 0.0;
+        cam_stats[3 * c + 2] = cnt;
+        double *p = part + 8 * (int64_t)c;
+        p[0] = s[0][0]; p[1] = cnt; p[2] = s[2][0]; p[3] = s[3][0]; p[4] = s[4][0];
+        p[5] = s[5][0]; p[6] = s[6][0]; p[7] = s[7][0];
+    }
+}
+
+// one workgroup: the camera partials in a fixed order -> summary[0..7]
+__global__ __launch_bounds__(256) void ba_reproj_final_kernel(const double *__restrict__ part, int n_cams,
+                                                              int64_t n_obs, double *__restrict__ summary)
+{
+    __shared__ double s[8][256];
+    const int t = threadIdx.x;
+    double se = 0.0, empty = 0.0, sa = 0.0, me = 0.0, ma = 0.0, wn = 0.0, wm = 0.0, w2 = 0.0;
+    for (int c = t; c < n_cams; c += 256) {
+        const double *p = part + 8 * (int64_t)c;
+        se += p[0];
+        empty += p[1] == 0.0 ? 1.0 : 0.0;
+        sa += p[2];
+        me = nan_max(me, p[3]);
+        ma = nan_max(ma, p[4]);
+        chan_merge(wn, wm, w2, p[5], p[6], p[7]);
+    }
+    s[0][t] = se; s[1][t] = empty; s[2][t] = sa; s[3][t] = me; s[4][t] = ma;
+    s[5][t] = wn; s[6][t] = wm; s[7][t] = w2;
+    reduce_stats(s, t);
+    if (t == 0) {
+        const double n = (double)n_obs;
+        summary[0] = n;
+        summary[1] = s[0][0];                     // sum e
+        summary[2] = s[0][0] / n;                 // mean e (mark_outliers' mre)
+        summary[3] = s[2][0] / (2.0 * n);         // np.mean(np.abs(r))
+        summary[4] = sqrt(s[7][0] / (2.0 * n));   // np.std(r)
+        summary[5] = n_obs > 0 ? s[4][0] : __builtin_nan("");   // np.amax(np.abs(r))
+        summary[6] = s[6][0];                     // np.mean(r)
+        summary[7] = s[1][0];                     // cameras without observations
+    }
+}
+
+__device__ __forceinline__ bool mre_flag(double e, double thr, int has_max, double max_error)
+{
+    return e > thr || (has_max && e > max_error);
+}
+
+// pass 2a: per tile sum of (mre - e)^2 (mark_outliers' stddev_sum, two-pass like the reference)
+__global__ __launch_bounds__(256) void ba_mre_sq_kernel(const double *__restrict__ e, int64_t n_obs,
+                                                        const double *__restrict__ summary,
+                                                        double *__restrict__ tile_sq)
+{
+    __shared__ double s[256];
+    const int t = threadIdx.x;
+    const double mre = summary[2];
+    const int64_t base = (int64_t)blockIdx.x * MRE_TILE;
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < MRE_TILE / 256; ++k) {
+        const int64_t o = base + k * 256 + t;
+        if (o < n_obs) {
+            const double d = mre - e[o];
+            acc += d * d;
+        }
+    }
+    s[t] = acc;
+    for (int h = 128; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) s[t] += s[t + h];
+    }
+    if (t == 0) tile_sq[blockIdx.x] = s[0];
+}
+
+// pass 2b (one workgroup): stddev and the threshold -> summary[8], summary[9]
+__global__ __launch_bounds__(256) void ba_mre_thr_kernel(const double *__restrict__ tile_sq, int64_t n_tiles,
+                                                         int64_t n_obs, double trim_stddev,
+                                                         double *__restrict__ summary)
+{
+    __shared__ double s[256];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (int64_t b = t; b < n_tiles; b += 256) acc += tile_sq[b];
+    s[t] = acc;
+    for (int h = 128; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) s[t] += s[t + h];
+    }
+    if (t == 0) {
+        const double stddev = sqrt(s[0] / (double)n_obs);
+        summary[8] = stddev;
+        summary[9] = summary[2] + stddev * trim_stddev;
+    }
+}
+
+// wave-local exclusive prefix of `f` over the lanes below, and the wave's total
+__device__ __forceinline__ int lane_prefix(bool f, int lane, int &total)
+{
+    const unsigned long long m = __ballot(f);
+    total = __popcll(m);
+    return __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// pass 2c: flagged observations per tile
+__global__ __launch_bounds__(256) void ba_mre_count_kernel(const double *__restrict__ e, int64_t n_obs,
+                                                           const double *__restrict__ summary,
+                                                           int has_max, double max_error,
+                                                           double *__restrict__ tile_cnt)
+{
+    __shared__ int s[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double thr = summary[9];
+    const int64_t base = (int64_t)blockIdx.x * MRE_TILE;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < MRE_TILE / 256; ++k) {
+        const int64_t o = base + k * 256 + t;
+        cnt += (o < n_obs && mre_flag(e[o], thr, has_max, max_error)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if (lane == 0) s[w] = cnt;
+    __syncthreads();
+    if (t == 0) tile_cnt[blockIdx.x] = (double)(s[0] + s[1] + s[2] + s[3]);
+}
+
+// pass 2d (one workgroup): exclusive scan of the tile counts -> tile_off; total -> summary[10]
+__global__ __launch_bounds__(256) void ba_mre_scan_kernel(const double *__restrict__ tile_cnt, int64_t n_tiles,
+                                                          double *__restrict__ tile_off,
+                                                          double *__restrict__ summary)
+{
+    __shared__ double s[257];
+    const int t = threadIdx.x;
+    const int64_t per = (n_tiles + 255) / 256, b0 = t * per, b1 = b0 + per < n_tiles ? b0 + per : n_tiles;
+    double acc = 0.0;
+    for (int64_t b = b0; b < b1; ++b) acc += tile_cnt[b];
+    s[t + 1] = acc;
+    __syncthreads();
+    if (t == 0) {
+        s[0] = 0.0;
+        for (int i = 1; i <= 256; ++i) s[i] += s[i - 1];     // (integers < 2^53: exact)
+        summary[10] = s[256];
+    }
+    __syncthreads();
+    acc = s[t];
+    for (int64_t b = b0; b < b1; ++b) {
+        tile_off[b] = acc;
+        acc += tile_cnt[b];
+    }
+}
+
+// pass 2e: the flagged observations of a tile, ascending, at the tile's offset (at most `cap`)
+__global__ __launch_bounds__(256) void ba_mre_scatter_kernel(const double *__restrict__ e, int64_t n_obs,
+                                                             const double *__restrict__ summary,
+                                                             int has_max, double max_error,
+                                                             const double *__restrict__ tile_off,
+                                                             int64_t *__restrict__ idx_out,
+                                                             double *__restrict__ e_sel, int64_t cap)
+{
+    __shared__ int s[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double thr = summary[9];
+    const int64_t base = (int64_t)blockIdx.x * MRE_TILE;
+    int64_t pos = (int64_t)tile_off[blockIdx.x];
+    for (int k = 0; k < MRE_TILE / 256; ++k) {
+        const int64_t o = base + k * 256 + t;
+        const double v = o < n_obs ? e[o] : 0.0;
+        const bool f = o < n_obs && mre_flag(v, thr, has_max, max_error);
+        int wt;
+        const int lp = lane_prefix(f, lane, wt);
+        __syncthreads();                          // s[] of the previous round has been read
+        if (lane == 0) s[w] = wt;
+        __syncthreads();
+        int before = lp;
+        for (int j = 0; j < w; ++j) before += s[j];
+        const int64_t p = pos + before;
+        if (f && p < cap) {
+            idx_out[p] = o;
+            e_sel[p] = v;
+        }
+        pos += s[0] + s[1] + s[2] + s[3];
+    }
+}
+
+}  // namespace
+
+extern "C" int iamx_ba_reproj_stats(const double *cams, int n_cams, const double *pts, int n_pts,
+                                    const int32_t *cam_idx, const int32_t *pt_idx, const double *uv,
+                                    int64_t n_obs, const double *calib, const int64_t *cam_ptr,
+                                    double *cam_stats, double *part, double *summary, double *e,
+                                    void *stream)
+{
+    IAMX_REQUIRE(cams && pts && cam_idx && pt_idx && uv && calib && cam_ptr && cam_stats && part &&
+                     summary, "null pointer");
+    IAMX_REQUIRE(n_cams > 0 && n_pts > 0 && n_obs >= 0, "bad size");
+    IAMX_REQUIRE((((uintptr_t)cam_stats | (uintptr_t)part | (uintptr_t)summary | (uintptr_t)e |
+                   (uintptr_t)cam_ptr) & 7) == 0 && ((uintptr_t)uv & 15) == 0,
+                 "uv must be 16-byte aligned, the other arrays 8-byte aligned");
+    hipStream_t st = iamx::as_stream(stream);
+    hipLaunchKernelGGL(ba_reproj_cam_kernel, dim3((unsigned)n_cams), dim3(256), 0, st, cams, pts,
+                       cam_idx, pt_idx, uv, n_obs, calib, cam_ptr, cam_stats, part, e);
+    int rc = iamx::check_launch("iamx_ba_reproj_stats");
+    if (rc != IAMX_OK) return rc;
+    hipLaunchKernelGGL(ba_reproj_final_kernel, dim3(1), dim3(256), 0, st, part, n_cams, n_obs, summary);
+    return iamx::check_launch("iamx_ba_reproj_stats");
+}
+
+extern "C" int iamx_ba_mark_outliers(const double *e, int64_t n_obs, double trim_stddev, int has_max,
+                                     double max_error, double *summary, double *work,
+                                     int64_t *idx_out, double *e_sel, int64_t cap, void *stream)
+{
+    IAMX_REQUIRE(summary && work && n_obs >= 0 && cap >= 0, "bad argument");
+    IAMX_REQUIRE(n_obs == 0 || e, "null pointer");
+    IAMX_REQUIRE(cap == 0 || (idx_out && e_sel), "null output with cap > 0");
+    IAMX_REQUIRE((((uintptr_t)e | (uintptr_t)summary | (uintptr_t)work | (uintptr_t)idx_out |
+                   (uintptr_t)e_sel) & 7) == 0, "8-byte alignment");
+    hipStream_t st = iamx::as_stream(stream);
+    const int64_t n_tiles = (n_obs + MRE_TILE - 1) / MRE_TILE;
+    double *tile_sq = work, *tile_cnt = work + n_tiles, *tile_off = work + 2 * n_tiles;
+    if (n_tiles)
+        hipLaunchKernelGGL(ba_mre_sq_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, e, n_obs, summary,
+                           tile_sq);
+    hipLaunchKernelGGL(ba_mre_thr_kernel, dim3(1), dim3(256), 0, st, tile_sq, n_tiles, n_obs, trim_stddev,
+                       summary);
+    if (n_tiles)
+        hipLaunchKernelGGL(ba_mre_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, e, n_obs, summary,
+                           has_max, max_error, tile_cnt);
+    hipLaunchKernelGGL(ba_mre_scan_kernel, dim3(1), dim3(256), 0, st, tile_cnt, n_tiles, tile_off, summary);
+    if (n_tiles)
+        hipLaunchKernelGGL(ba_mre_scatter_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, e, n_obs,
+                           summary, has_max, max_error, tile_off, idx_out, e_sel, cap);
+    return iamx::check_launch("iamx_ba_mark_outliers");
+}
+
+#pragma clang fp contract(fast)

@@ -534,6 +534,51 @@ def ba_residual_jac(cams, pts, cam_idx, pt_idx, uv, calib, with_calib=False):
     return r[:2 * n_obs], Jc[:n_obs], Jp[:n_obs], (Jk[:n_obs] if with_calib else None)
 
 
+# summary layout of iamx_ba_reproj_stats / iamx_ba_mark_outliers (include/iamx.h)
+REPROJ_N, REPROJ_SUM_E, REPROJ_MRE_E, REPROJ_MEAN_ABS_R, REPROJ_STD_R, REPROJ_MAX_ABS_R, \
+    REPROJ_MEAN_R, REPROJ_EMPTY_CAMS, REPROJ_STDDEV_E, REPROJ_THRESHOLD, REPROJ_COUNT = range(11)
+MRE_TILE = 2048
+
+
+def ba_reproj_stats(cams, pts, cam_idx, pt_idx, uv, calib, cam_ptr, with_e=True):
+    """Pass 1 of the reprojection-error report: device tensors in (as ba_residual, plus cam_ptr
+    int64 [C+1]); returns device tensors (cam_stats [C, 3] = mean e, max e, count; summary [16];
+    e [n_obs] or None).  Enqueued on the current stream, no synchronisation."""
+    dev = require_gpu()
+    n_obs = cam_idx.numel()
+    n_cams = cams.numel() // 7
+    if cam_ptr.numel() != n_cams + 1 or cam_ptr.dtype != torch.int64:
+        raise ValueError('cam_ptr must be int64 [n_cams + 1]')
+    cam_stats = torch.empty((n_cams, 3), dtype=F64, device=dev)
+    part = torch.empty((n_cams, 8), dtype=F64, device=dev)
+    summary = torch.full((16,), float('nan'), dtype=F64, device=dev)
+    e = torch.empty(max(n_obs, 1), dtype=F64, device=dev) if with_e else None
+    check(lib().iamx_ba_reproj_stats(_ptr(cams), n_cams, _ptr(pts), pts.numel() // 3,
+                                     _ptr(cam_idx), _ptr(pt_idx), _ptr(uv), n_obs, _ptr(calib),
+                                     _ptr(cam_ptr), _ptr(cam_stats), _ptr(part), _ptr(summary),
+                                     _ptr(e), stream_ptr()), 'iamx_ba_reproj_stats')
+    return cam_stats, summary, (e[:n_obs] if with_e else None)
+
+
+def ba_mark_outliers(e, summary, trim_stddev, max_error=None, cap=None):
+    """Pass 2: flags e > mre + stddev * trim_stddev (or e > max_error when max_error is not None)
+    with the device-side mre of `summary` (updated in place: stddev, threshold, count).  Returns
+    device tensors (idx int64 [cap], e_sel [cap]); the first int(summary[REPROJ_COUNT]) entries
+    (at most cap, default n_obs) are the flagged observations in ascending order."""
+    dev = require_gpu()
+    n_obs = e.numel()
+    cap = n_obs if cap is None else int(cap)
+    n_tiles = (n_obs + MRE_TILE - 1) // MRE_TILE
+    work = torch.empty(max(1, 3 * n_tiles), dtype=F64, device=dev)
+    idx = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+    e_sel = torch.empty(max(cap, 1), dtype=F64, device=dev)
+    check(lib().iamx_ba_mark_outliers(_ptr(e), n_obs, float(trim_stddev), int(max_error is not None),
+                                      float(max_error) if max_error is not None else 0.0,
+                                      _ptr(summary), _ptr(work), _ptr(idx), _ptr(e_sel), cap,
+                                      stream_ptr()), 'iamx_ba_mark_outliers')
+    return idx[:cap], e_sel[:cap]
+
+
 # --------------------------------------------------------------------------------------
 # a reusable, allocation-free batch of ordered pairs: knn2 -> metric -> scan -> compaction
 # --------------------------------------------------------------------------------------

@@ -1,0 +1,287 @@
+"""MI355X-native counterpart of the reference's scripts/lib/match_culling.py, plus the device-backed
+report that scripts/4b-mre-by-image.py builds from it.
+
+Same names and semantics as the reference:
+
+    mark_feature(matches, match_index, feat_index, error)      match_culling.py:133-137
+    mark_using_list(mark_list, matches)                        :139-141
+    delete_marked_features(matches, min_chain_len, strong=False)   :144-161
+    show_outliers(result_list, matches, image_list) / draw_match(...)   (interactive, cv2)
+
+New, for the 4b-mre-by-image.py twin (imageanalysis_amd/scripts/4b-mre-by-image.py):
+
+    mre_by_image(opt, matches, x=None, proj=None) -> MreReport
+        per-observation e = |observed - projected|, per-camera mean / max, the summary scalars of
+        the signed residual vector: one pass of iamx_ba_reproj_stats over the camera-major
+        observations Optimizer.setup() uploaded; only C rows and a few scalars reach the host
+    mark_outliers(matches, report, trim_stddev, max_error=None) -> mark count
+        the reference's mark_outliers(): iamx_ba_mark_outliers thresholds on the device, the
+        flagged observations (ascending) come back, are ordered by descending e on the host (ties
+        in observation order: the reference's stable sort) and marked
+
+`matches` is the reference's list of `[ned, group, [image, [u, v]], ...]` chains, or the
+array-backed match_cleanup.Chains: marks on an untouched Chains are kept in a member mask
+(`chains.marked`) and delete_marked_features() rebuilds its arrays with numpy.
+"""
+import numpy as np
+
+from .match_cleanup import Chains
+
+MARK = [-1, -1]
+
+
+# ---------------------------------------------------------------------------------------------
+# marking
+# ---------------------------------------------------------------------------------------------
+def _marks(chains):
+    m = getattr(chains, 'marked', None)
+    if m is None or len(m) != len(chains.img):
+        m = np.zeros(len(chains.img), bool)
+        chains.marked = m
+    return m
+
+
+def _arrays(matches):
+    return isinstance(matches, Chains) and matches.untouched()
+
+
+def mark_feature(matches, match_index, feat_index, error):
+    print('  outlier - match index:', match_index, 'feature index:', feat_index, 'error:', error)
+    if _arrays(matches):
+        lo, hi = int(matches.ptr[match_index]), int(matches.ptr[match_index + 1])
+        if not 0 <= feat_index < hi - lo:
+            raise IndexError('feature index %d out of range of match %d' % (feat_index, match_index))
+        _marks(matches)[lo + feat_index] = True
+        return
+    match = matches[match_index]
+    match[feat_index + 2] = [-1, -1]
+
+
+def mark_using_list(mark_list, matches):
+    for mark in mark_list:
+        mark_feature(matches, mark[0], mark[1], "-")
+
+
+# ---------------------------------------------------------------------------------------------
+# deletion
+# ---------------------------------------------------------------------------------------------
+def delete_marked_features(matches, min_chain_len, strong=False):
+    """Remove the marked members; a chain that had a marked member goes entirely with `strong`,
+    otherwise when fewer than min_chain_len members are left.  Chains without marks stay, however
+    short.  The reference's messages in the reference's order (last chain first)."""
+    print(" deleting marked items...")
+    if _arrays(matches):
+        _delete_arrays(matches, min_chain_len, strong)
+    else:
+        keep = np.ones(len(matches), bool)
+        for i in reversed(range(len(matches))):
+            match = matches[i]
+            members = [p for p in match[2:] if p != MARK]
+            if len(members) == len(match) - 2:
+                continue
+            match[2:] = members
+            if strong:
+                print("deleting entire match that contains a bad element", i)
+                keep[i] = False
+            elif len(members) < min_chain_len:
+                print("deleting match that is now in less than %d images:" % min_chain_len, match)
+                keep[i] = False
+        if not keep.all():
+            # one pass instead of a list.pop(i) per chain (quadratic when many chains go)
+            matches[:] = [m for m, k in zip(matches, keep.tolist()) if k]
+    print("final matches size:", len(matches))
+
+
+def _delete_arrays(ch, min_chain_len, strong):
+    marked = getattr(ch, 'marked', None)
+    n = len(ch.ptr) - 1
+    if marked is None or len(marked) != len(ch.img) or not marked.any():
+        return
+    chain_of = np.repeat(np.arange(n), np.diff(ch.ptr))
+    has_bad = np.bincount(chain_of[marked], minlength=n) > 0
+    new_len = np.bincount(chain_of[~marked], minlength=n)
+    drop = has_bad & (True if strong else (new_len < min_chain_len))
+    for i in np.nonzero(drop)[0][::-1].tolist():
+        if strong:
+            print("deleting entire match that contains a bad element", i)
+        else:
+            sel = np.arange(ch.ptr[i], ch.ptr[i + 1])
+            sel = sel[~marked[sel]]
+            row = [ch.ned[i].tolist() if ch.has_ned[i] else None, int(ch.group[i])] + \
+                [[a, b] for a, b in zip(ch.img[sel].tolist(), ch.uv[sel].tolist())]
+            print("deleting match that is now in less than %d images:" % min_chain_len, row)
+    keep_chain = ~drop
+    keep_mem = ~marked & keep_chain[chain_of]
+    ptr = np.zeros(int(keep_chain.sum()) + 1, np.int64)
+    np.cumsum(new_len[keep_chain], out=ptr[1:])
+    ch.img = ch.img[keep_mem]
+    ch.uv = ch.uv[keep_mem]
+    ch.ptr = ptr
+    ch.ned = ch.ned[keep_chain]
+    ch.has_ned = ch.has_ned[keep_chain]
+    ch.group = ch.group[keep_chain]
+    ch.marked = np.zeros(len(ch.img), bool)
+
+
+# ---------------------------------------------------------------------------------------------
+# observation -> (match index, feature index)
+# ---------------------------------------------------------------------------------------------
+def observation_features(matches, match_index, image_index):
+    """For every observation (its chain `match_index[i]`, its camera's image `image_index[i]`):
+    the index in match[2:] of the LAST member of the chain from that image (4b-mre-by-image.py:80-85
+    overwrites its match_index in the loop), 0 when there is none."""
+    match_index = np.asarray(match_index, np.int64)
+    image_index = np.asarray(image_index, np.int64)
+    out = np.zeros(len(match_index), np.int64)
+    if _arrays(matches):
+        ptr, img = matches.ptr, matches.img
+        lo = ptr[match_index]
+        ln = ptr[match_index + 1] - lo
+        rep = np.repeat(np.arange(len(match_index)), ln)
+        start = np.cumsum(ln) - ln
+        pos = np.arange(int(ln.sum())) - np.repeat(start, ln)
+        hit = img[lo[rep] + pos] == image_index[rep]
+        np.maximum.at(out, rep[hit], pos[hit])
+        return out
+    for i, (m, im) in enumerate(zip(match_index.tolist(), image_index.tolist())):
+        k = 0
+        for j, p in enumerate(matches[m][2:]):
+            if p[0] == im:
+                k = j
+        out[i] = k
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the report (4b-mre-by-image.py:55-110) and the marking (:112-150)
+# ---------------------------------------------------------------------------------------------
+class MreReport(object):
+    """n_error (= len(error) of the reference: 2 per observation), mre / std / max of the signed
+    residual vector (np.mean(np.abs(r)), np.std(r), np.amax(np.abs(r))), `by_cam`: per camera
+    [mean e, max e, name] in the reference's results_by_cam order (stable, descending mean;
+    9999.0 for a camera without observations), `e`: the per-observation errors (device tensor,
+    camera-major), `summary`: the device summary (kernels.REPROJ_*)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def mre_by_image(opt, matches, x=None, proj=None):
+    import torch
+    from . import kernels
+    C = opt.n_cameras
+    d = opt._device(opt.by_camera_point_indices, opt.by_camera_points_2d)
+    x = opt._x0() if x is None else np.asarray(x, np.float64)
+    cams, pts, calib = opt._upload(x, C, opt.n_points)
+    if pts.numel() == 0:
+        pts = torch.zeros(3, dtype=torch.float64, device=cams.device)
+    counts = np.bincount(d['cam_idx_host'], minlength=C).astype(np.int64)
+    cam_ptr = np.zeros(C + 1, np.int64)
+    np.cumsum(counts, out=cam_ptr[1:])
+    cam_stats, summary, e = kernels.ba_reproj_stats(
+        cams, pts, d['cam_idx'], d['pt_idx'], d['uv'], calib,
+        torch.from_numpy(cam_ptr).to(cams.device))
+    host = torch.cat([cam_stats.reshape(-1), summary]).cpu().numpy()     # the one synchronisation
+    rows_np, s = host[:3 * C].reshape(C, 3), host[3 * C:]
+    rows = []
+    for i in range(C):
+        name = proj.image_list[opt.camera_map_fwd[i]].name if proj is not None \
+            else opt.camera_map_fwd[i]
+        if rows_np[i, 2] > 0:
+            rows.append([float(rows_np[i, 0]), float(rows_np[i, 1]), name])
+        else:
+            rows.append([9999.0, 9999.0, name])
+    by_cam = sorted(rows, key=lambda fields: fields[0], reverse=True)
+    return MreReport(n_obs=d['n_obs'], n_error=2 * d['n_obs'],
+                     mre=float(s[kernels.REPROJ_MEAN_ABS_R]), std=float(s[kernels.REPROJ_STD_R]),
+                     max=float(s[kernels.REPROJ_MAX_ABS_R]), by_cam=by_cam, e=e, summary=summary,
+                     cam_idx=d['cam_idx_host'], pt_idx=d['pt_idx_host'],
+                     camera_map_fwd=np.array([opt.camera_map_fwd[i] for i in range(C)], np.int64),
+                     feat_map_rev=opt.feat_map_rev, matches=matches)
+
+
+def flagged(report, trim_stddev, max_error=None):
+    """Device pass 2: (observation indices in the reference's marking order, their e, mre of e,
+    stddev of e).  max_error follows the reference's `args.max and e > args.max` (0 / None: off)."""
+    from . import kernels
+    idx, e_sel = kernels.ba_mark_outliers(report.e, report.summary, trim_stddev,
+                                          max_error=max_error if max_error else None)
+    s = report.summary.cpu().numpy()                                       # the one synchronisation
+    n = int(s[kernels.REPROJ_COUNT])
+    idx = idx[:n].cpu().numpy()
+    e_sel = e_sel[:n].cpu().numpy()
+    order = np.argsort(-e_sel, kind='stable')          # descending e; ties stay ascending
+    return idx[order], e_sel[order], float(s[kernels.REPROJ_MRE_E]), float(s[kernels.REPROJ_STDDEV_E])
+
+
+def mark_outliers(matches, report, trim_stddev, max_error=None):
+    print("Marking outliers...")
+    print(" computing stats...")
+    obs, err, mre, stddev = flagged(report, trim_stddev, max_error)
+    print("mre = %.4f stddev = %.4f" % (mre, stddev))
+    print(" marking outliers...")
+    fmap = report.feat_map_rev
+    match_index = np.fromiter((fmap[j] for j in report.pt_idx[obs].tolist()), np.int64, len(obs))
+    image_index = report.camera_map_fwd[report.cam_idx[obs]]
+    feat_index = observation_features(matches, match_index, image_index)
+    for m, f, e in zip(match_index.tolist(), feat_index.tolist(), err.tolist()):
+        mark_feature(matches, m, f, e)
+    return len(obs)
+
+
+# ---------------------------------------------------------------------------------------------
+# interactive review (cv2 windows; no device path)
+# ---------------------------------------------------------------------------------------------
+def _cv2():
+    try:
+        import cv2
+    except ImportError:
+        raise RuntimeError("interactive outlier review needs OpenCV (cv2), which is not installed; "
+                           "run without --interactive to mark outliers by the stddev / max rule")
+    return cv2
+
+
+def draw_match(i, index, matches, image_list):
+    """Show a crop of every image of chain i (at most 21) around its member; member `index` (or
+    both members of a pair) in red, the others green.  Returns the key pressed."""
+    cv2 = _cv2()
+    half = 300
+    match = matches[i]
+    print('match:', match, 'index:', index)
+    for j, m in enumerate(match[2:22]):
+        img = image_list[m[0]]
+        print(' ', m, img)
+        rgb = img.load_rgb()
+        h, w = rgb.shape[:2]
+        cx = min(max(int(round(m[1][0])), half), w - half)
+        cy = min(max(int(round(m[1][1])), half), h - half)
+        crop = rgb[cy - half:cy + half, cx - half:cx + half]
+        color = (0, 0, 255) if (j == index or len(match) == 3) else (0, 255, 0)
+        mark = (int(round(m[1][0])) - cx + half, int(round(m[1][1])) - cy + half)
+        cv2.circle(crop, mark, 2, color, thickness=2)
+        cv2.imshow(img.name + ' (%d)' % m[0], crop)
+    print('waiting for keyboard input...')
+    key = cv2.waitKey() & 0xff
+    cv2.destroyAllWindows()
+    return key
+
+
+def show_outliers(result_list, matches, image_list):
+    """result_list: [e, match index, feature index] rows, worst first.  'd' marks the shown
+    member for deletion, 'q' / Esc ends the review.  Returns the [match, feature] list."""
+    _cv2()
+    print("Show outliers...")
+    e = np.array([r[0] for r in result_list], np.float64)
+    print(" computing stats...")
+    mre = float(np.sum(e[::-1])) / len(e) if len(e) else float('nan')
+    stddev = float(np.sqrt(np.sum((mre - e) ** 2) / len(e))) if len(e) else float('nan')
+    print("avg error = %.4f stddev = %.4f" % (mre, stddev))
+    mark_list = []
+    for line in result_list:
+        print("  outlier index %d-%d err=%.2f" % (line[1], line[2], line[0]))
+        key = draw_match(line[1], line[2], matches, image_list)
+        if key == ord('d'):
+            mark_list.append([line[1], line[2]])
+        elif key in (27, ord('q')):
+            break
+    return mark_list

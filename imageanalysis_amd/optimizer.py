@@ -9,7 +9,8 @@ adjustment).  Same class, methods, argument meaning and return values:
       .update_camera_poses(proj)                                                          :543-575
       .refit(proj, matches, groups, group_index)                                          :583-683
 so scripts/process.py:380-401, scripts/4a-optimize.py and scripts/4b-mre-by-image.py run
-unchanged (INTEGRATION.md).
+unchanged; the device-backed cull step is match_culling.mre_by_image /
+mark_outliers and the twin imageanalysis_amd/scripts/4b-mre-by-image.py.
 
 What moves to the GPU: every residual evaluation (the reference loops over cameras calling
 cv2.projectPoints) is one launch of csrc/ba_kernels.hip over all observations, and the

@@ -554,6 +554,43 @@ int iamx_ba_residual_jac(const double *cams, int n_cams, const double *pts, int 
                          int64_t n_obs, const double *calib, double *r,
                          double *Jc, double *Jp, double *Jk, void *stream);
 
+/* Reprojection-error report (scripts/4b-mre-by-image.py:60-110), pass 1 of 2.  Inputs as for
+ * iamx_ba_residual (camera-major observations), plus
+ *   cam_ptr   DEV [n_cams+1] int64   camera c owns observations [cam_ptr[c], cam_ptr[c+1])
+ *             (non-decreasing, cam_ptr[n_cams] = n_obs; values are clamped to [0, n_obs])
+ * Per observation (du, dv) is formed with the arithmetic of iamx_ba_residual and
+ * e = sqrt(du*du + dv*dv) with a separately rounded multiply and add (np.linalg.norm).
+ * The residual vector itself is not written.  Outputs:
+ *   cam_stats DEV [n_cams][3] float64  (mean e, max e, count); a camera without observations
+ *             has count 0 and mean = max = 0 (the reference reports it as 9999.0)
+ *   part      DEV [n_cams][8] float64  workspace (per-camera partials)
+ *   summary   DEV [16] float64: [0] n_obs  [1] sum e  [2] sum e / n_obs  [3] mean |r|
+ *             [4] std r (population)  [5] max |r|  [6] mean r  [7] cameras without observations
+ *             (r = the 2*n_obs signed residuals; [8..10] belong to iamx_ba_mark_outliers)
+ *   e         DEV [n_obs] float64 or NULL
+ * Sums are reduced in a fixed order (no floating-point atomics): results are identical run to
+ * run.  n_obs = 0 is legal (summary [2..6] NaN or 0/0).  uv 16-byte aligned, the other arrays
+ * 8-byte aligned.  Two launches, no host synchronisation. */
+int iamx_ba_reproj_stats(const double *cams, int n_cams, const double *pts, int n_pts,
+                         const int32_t *cam_idx, const int32_t *pt_idx, const double *uv,
+                         int64_t n_obs, const double *calib, const int64_t *cam_ptr,
+                         double *cam_stats, double *part, double *summary, double *e,
+                         void *stream);
+
+/* Pass 2 (mark_outliers, 4b-mre-by-image.py:112-150): from e DEV [n_obs] and summary[2] (the
+ * device-side mre) of pass 1,
+ *   stddev = sqrt(sum (mre - e)^2 / n_obs)            -> summary[8]
+ *   thr    = mre + stddev * trim_stddev               -> summary[9]
+ * an observation is flagged when e > thr, or has_max != 0 and e > max_error.  The flagged
+ * observation indices are written in ascending order to idx_out DEV [cap] int64, their e to
+ * e_sel DEV [cap] float64 (the first min(count, cap) of them); count -> summary[10] (a float64,
+ * exact).  work DEV [max(1, 3 * ceil(n_obs / 2048))] float64.  Every odd, small or empty n_obs
+ * is legal (n_obs = 0: count 0, stddev NaN).  All pointers 8-byte aligned; idx_out / e_sel may
+ * be NULL when cap = 0.  Five launches, no host synchronisation, fixed-order reductions. */
+int iamx_ba_mark_outliers(const double *e, int64_t n_obs, double trim_stddev, int has_max,
+                          double max_error, double *summary, double *work, int64_t *idx_out,
+                          double *e_sel, int64_t cap, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Image preparation -- replaces the cv2 calls of Image.load_rgb(equalize=True) and the resize
  * in detect_features (scripts/lib/image.py:105-112,313): BGR->HSV, CLAHE(clip_limit, 8x8) on
