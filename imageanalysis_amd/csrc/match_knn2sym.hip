@@ -418,6 +418,68 @@ __device__ __forceinline__ void half_wave_min16(int (&r)[16], int lo, int &m0, i
     m1 = w[1];
 }
 
+// half_wave_min16<true> cut into four pieces that can ride in four different MFMA gaps (the sweep
+// runs them in the steps of the next tile): 0 and 1 the level "xor 8" on register pairs 0-3 and
+// 4-7, 2 the level "xor 4" and the floor `lo`, 3 the levels "xor 16" and inside the quads and the
+// two stores dst[0] = m0, dst[16] = m1.  Each asm block opens with its own s_nop 1 (DPP reads).
+template <int P>
+__device__ __forceinline__ void row_min16_piece(int (&r)[16], int (&u)[4], int lo, int *dst)
+{
+    if constexpr (P == 0) {
+        asm("s_nop 1\n\t"
+            "v_min_i32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %0, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %1, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %2, %6, %6 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %3, %3, %3 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %3, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc"
+            : "+v"(r[0]), "+v"(r[2]), "+v"(r[4]), "+v"(r[6])
+            : "v"(r[1]), "v"(r[3]), "v"(r[5]), "v"(r[7]));
+    } else if constexpr (P == 1) {
+        asm("s_nop 1\n\t"
+            "v_min_i32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %0, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %1, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %2, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %2, %6, %6 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %3, %3, %3 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %3, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xc"
+            : "+v"(r[8]), "+v"(r[10]), "+v"(r[12]), "+v"(r[14])
+            : "v"(r[9]), "v"(r[11]), "v"(r[13]), "v"(r[15]));
+    } else if constexpr (P == 2) {
+        asm("s_nop 1\n\t"
+            "v_min_i32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %0, %4, %4 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_min_i32_dpp %1, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %1, %5, %5 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_min_i32_dpp %2, %2, %2 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %2, %6, %6 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_min_i32_dpp %3, %3, %3 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %3, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xa"
+            : "+v"(r[0]), "+v"(r[4]), "+v"(r[8]), "+v"(r[12])
+            : "v"(r[2]), "v"(r[6]), "v"(r[10]), "v"(r[14]));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = r[4 * k] + lo;
+    } else {
+        int w[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const v2u x = __builtin_amdgcn_permlane16_swap((unsigned)u[2 * k], (unsigned)u[2 * k + 1], false, false);
+            w[k] = min((int)x[0], (int)x[1]);
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            w[k] = min(w[k], __builtin_amdgcn_update_dpp(0, w[k], 0xB1, 0xF, 0xF, true));    // quad_perm:[1,0,3,2]
+            w[k] = min(w[k], __builtin_amdgcn_update_dpp(0, w[k], 0x4E, 0xF, 0xF, true));    // quad_perm:[2,3,0,1]
+        }
+        dst[0] = w[0];
+        dst[16] = w[1];
+    }
+}
+
 // PIPE: the MFMAs of a pair of query blocks are issued while the minima of the previous pair are
 // taken (software pipeline across the 8 steps of a chunk, sched_group_barrier interleave); PIPE
 // epilogue VALU instructions go beside every MFMA.
@@ -437,12 +499,15 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     constexpr int WGROWS = NW * QW * 32;
     constexpr int NT = NW * 64;
     constexpr int PIECES = CHUNK * D / 16 / NT;
-    __shared__ __attribute__((aligned(16))) int8_t lds[2 * CHUNK * D + 2 * CHUNK * 4 + 2 * NW * CHUNK * 4 + 2 * NW * 4 + NW * 256 * 4];   // (lds_cq: NW used)
+    // (R_w: three buffers -- a chunk's last row minima are stored while the next chunk runs, and its
+    //  merge follows the next chunk's barrier; the dump area takes a lane's stores at the same buffer
+    //  offsets as the row area)
+    __shared__ __attribute__((aligned(16))) int8_t lds[2 * CHUNK * D + 2 * CHUNK * 4 + 3 * NW * CHUNK * 4 + 2 * NW * 4 + (2 * NW * CHUNK + NW * 256) * 4];   // (lds_cq: NW used)
     int8_t *lds_tile = lds;
     int *lds_tb = reinterpret_cast<int *>(lds + 2 * CHUNK * D);      // [2][CHUNK]     Ct
-    int *lds_row = lds_tb + 2 * CHUNK;                               // [2][NW][CHUNK] R_w
-    int *lds_cq = lds_row + 2 * NW * CHUNK;                          // [NW] (2 NW reserved) S_w
-    int *lds_dump = lds_cq + 2 * NW;                                 // [NW][256]      unused stores
+    int *lds_row = lds_tb + 2 * CHUNK;                               // [3][NW][CHUNK] R_w
+    int *lds_cq = lds_row + 3 * NW * CHUNK;                          // [NW] (2 NW reserved) S_w
+    int *lds_dump = lds_cq + 2 * NW;                                 // [NW][256] (+ 2 buffer strides) unused stores
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, g = lane >> 5;
 
@@ -507,8 +572,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     }
     if (!wave_valid) {
 #pragma unroll
-        for (int k = 0; k < 2 * CHUNK / 64; ++k)
-            lds_row[((k >> 1) * NW + wave) * CHUNK + (k & 1) * 64 + lane] = BIG;
+        for (int k = 0; k < 3 * CHUNK / 64; ++k)
+            lds_row[((k / (CHUNK / 64)) * NW + wave) * CHUNK + (k % (CHUNK / 64)) * 64 + lane] = BIG;
     }
     int m[QW][4];
 #pragma unroll
@@ -528,125 +593,190 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
             int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
             __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
         }
-        if (wave < CHUNK / 64)
-            __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + tid,
-                                             (lds_ptr)(lds_tb + buf * CHUNK + wave * 64), 4, 0, 0);
+        // (Ct: every wave, the waves past CHUNK / 64 repeat the same words -- no branch in the step)
+        __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + (tid & (CHUNK - 1)),
+                                         (lds_ptr)(lds_tb + buf * CHUNK + (wave & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
     };
     auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
-    // per train row: the waves' group minima -> (L, U1, U2)
+    // per train row: the waves' group minima -> (L, U1, U2).  Every wave runs the merge (no branch in
+    // the step it rides in); only waves < MERGEW store, through a buffer resource over this
+    // workgroup's partials: an offset past num_records drops the store
     constexpr int MROWS = CHUNK / MERGEW;                // rows a merging wave takes
-    const int mrow = wave * MROWS + lane;                // (valid for wave < MERGEW, lane < MROWS)
-    const bool merger = wave < MERGEW && lane < MROWS;
+    static_assert(MROWS == 64 && NW % MERGEW == 0, "one merge row per lane");
+    const int mrow = (wave % MERGEW) * MROWS + lane;
+    const bool merger = wave < MERGEW;
+    // Buffer resource over this workgroup's capA partials (8 bytes each): stride 0 (a raw buffer),
+    // num_records = capA * 8 bytes.  Word 3 of a gfx9 descriptor: DATA_FORMAT = 4 (32 bits) in bits
+    // 15-18, every other field 0 -- the value the gfx9 buffer stores of LLVM and composable_kernel
+    // use for untyped dword access (the untyped store ignores the format, but DATA_FORMAT 0 is
+    // "invalid").  A raw buffer store whose offset + size exceeds num_records is dropped by the
+    // hardware's range check: RANGE_DROP is such an offset for any capA (below 2^31, so offset + 8
+    // does not wrap).
+    constexpr int RSRC_WORD3_DATA_FORMAT_32 = 4 << 15;
+    constexpr int RANGE_DROP = 0x7FFFFFF0;
+    const __amdgpu_buffer_rsrc_t rowp_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(A.rowp + 2 * rbase, (short)0, capA * 8, RSRC_WORD3_DATA_FORMAT_32);
     // (the waves' spreads S_w, read once behind the first barrier into scalar registers: the merge
     //  sits on the critical path of its waves -- one wave per SIMD, nothing hides its LDS reads)
     int spread_w[NW];
-    auto merge_rows = [&](int ch, int buf) {
-        const int tid = mrow;
+    auto merge_rows = [&](int ch, int rbo, bool store) {
         int L = BIG, U1 = BIG, U2 = BIG;
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
-            const int R = lds_row[(buf * NW + w) * CHUNK + tid];
+            const int R = lds_row[rbo + w * CHUNK + mrow];
             const int lw = R, uw = R + spread_w[w];
             L = min(L, lw);
             U2 = min(max(U1, uw), U2);
             U1 = min(U1, uw);
         }
-        *reinterpret_cast<v2i *>(A.rowp + 2 * (rbase + ch * CHUNK + tid)) = v2i{L, pack_row_bounds(L, U1, U2)};
+        __builtin_amdgcn_raw_buffer_store_b64(v2i{L, pack_row_bounds(L, U1, U2)}, rowp_rsrc,
+                                              store ? (ch * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
+    };
+
+    // The tile loop is one software pipeline across the chunks (8 MFMAs a step, PP = QW / 2 steps a
+    // tile, 4 tiles a chunk): step s issues the MFMAs of step s + 1 while it takes the minima of
+    // step s; the row butterfly of a tile is cut into four pieces that ride in the steps of the NEXT
+    // tile (a second r set); the operands of tile t + 2 are read two per step from the last step of
+    // tile t on.  The chunk's barrier sits in front of the last step of tile NT4 - 2: every read of
+    // the chunk's LDS stage has been issued by then, so the stage of chunk + 2 goes behind it and the
+    // reads of the next chunk's first two tiles, the first MFMAs of the next chunk, the last tile's
+    // butterfly and the merge of the previous chunk all ride in MFMA gaps.  The last chunk issues
+    // (and drops) one step of MFMAs on a repeated stage: no branch in the loop body.
+    constexpr int PP = QW / 2, NT4 = CHUNK / 32, NS = NT4 * PP;
+    static_assert(NT4 % 2 == 0 && NT4 >= 2, "tile parity must carry across chunks");
+    // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3); after the
+    // butterfly a quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per quad
+    // stores them; the others store into a dump area (no branch in the tile loop: a branch
+    // there makes the compiler sink the column minima below it and keep the accumulators alive).
+    // A wave past the end of the B image (only in the last workgroup of a pair whose B image is not
+    // a multiple of the workgroup's rows) runs the loop too -- it shares the barriers and the merge
+    // -- on repeats of the last B row, with every row store in the dump area and no column result:
+    // MFMA work on a SIMD that would otherwise idle, the price of a branch-free step.
+    int *const row_dst = (lane & 3) == 0 && wave_valid
+        ? lds_row + wave * CHUNK + 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1)
+        : lds_dump + wave * 256 + lane;                 // (+ row buffer offset + tile*32 + 16: inside the dump area)
+    v4i aop[2][4], tbop[2][4];
+    v16i accs[2][2];
+    int r[2][16], bu[4];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) r[1][k] = BIG;
+    // read k (0..7) of a tile's operands: the C operand Ct first (the first MFMA needs all of it)
+    auto load_op = [&](int buf, int tile, int k, v4i (&a)[4], v4i (&tbv)[4]) {
+        if (k < 4) {
+            tbv[k] = *reinterpret_cast<const v4i *>(lds_tb + buf * CHUNK + tile * 32 + 8 * k + 4 * g);
+        } else {
+            const int s = k - 4, rr = tile * 32 + c, swz = (rr >> 1) & 7;
+            a[s] = *reinterpret_cast<const v4i *>(lds_tile + buf * (CHUNK * D) + rr * D + (((2 * s + g) ^ swz) * 16));
+        }
+    };
+    auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
+        }
+        if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
     };
 
     stage_direct(0, 0);
+    stage_direct(nchunks > 1 ? 1 : 0, 1);
     wait_direct();
     __syncthreads();
 #pragma unroll
     for (int w = 0; w < NW; ++w) spread_w[w] = __builtin_amdgcn_readfirstlane(lds_cq[w]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) load_op(0, 0, k, aop[0], tbop[0]);
+#pragma unroll
+    for (int k = 0; k < 8 / PP; ++k) load_op(0, 1, k, aop[1], tbop[1]);
+    issue(0, 0, accs[0][0], accs[0][1]);
+    __builtin_amdgcn_sched_barrier(0);
+    // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
+    // (meaningless) last tile into the buffer chunk 2 overwrites
+    int rbo = 0, rbo_prev = 2 * NW * CHUNK;
     for (int ch = 0; ch < nchunks; ++ch) {
         const int buf = ch & 1;
-        if (ch + 1 < nchunks) stage_direct(ch + 1, buf ^ 1);
-        if (ch > 0 && merger) merge_rows(ch - 1, buf ^ 1);
-        if (wave_valid) {
-            const int8_t *tile_base = lds_tile + buf * (CHUNK * D);
-            const int *tb_base = lds_tb + buf * CHUNK;
-            auto load_ops = [&](int tile, v4i (&a)[4], v4i (&tbv)[4]) {
-                const int r = tile * 32 + c, swz = (r >> 1) & 7;
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    a[s] = *reinterpret_cast<const v4i *>(tile_base + r * D + (((2 * s + g) ^ swz) * 16));
+        for (int st = 0; st < NS; ++st) {
+            const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
+            if (st == (NT4 - 1) * PP - 1) {
+                // every read of this chunk's stage is done (lgkmcnt), the next chunk's stage has landed
+                // (vmcnt): the stage of chunk + 2 may overwrite this one
+                __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
+                __syncthreads();
+                stage_direct(ch + 2 < nchunks ? ch + 2 : nchunks - 1, buf);
+                merge_rows(ch - 1, rbo_prev, merger && ch > 0);
+            }
+            // the MFMAs of the next step (the next chunk's first step from the last one)
+            if (st + 1 < NS) issue((st + 1) / PP, 2 * ((st + 1) % PP), accs[cur ^ 1][0], accs[cur ^ 1][1]);
+            else issue(0, 0, accs[cur ^ 1][0], accs[cur ^ 1][1]);
+            // the operand reads of tile T (flattened across chunks) run from the last step of tile T - 2
+            // to the step before T's first MFMAs, 8 / PP a step: here those of tile T = (st + 1) / PP + 1
+            {
+                const int T = (st + 1) / PP + 1, i = (st + 1) % PP;
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    tbv[k] = *reinterpret_cast<const v4i *>(tb_base + tile * 32 + 8 * k + 4 * g);
-            };
-            // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3); after the
-            // butterfly a quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per quad
-            // stores them; the others store into a dump area (no branch in the tile loop: a branch
-            // there makes the compiler sink the column minima below it and keep the accumulators alive)
-            int *row_dst = (lane & 3) == 0
-                ? lds_row + (buf * NW + wave) * CHUNK + 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1)
-                : lds_dump + wave * 256 + lane;                 // + tile*32 (+16) stays inside [0, 256)
-            constexpr int PP = QW / 2, NS = (CHUNK / 32) * PP;
-            v4i aop[2][4], tbop[2][4];
-            v16i accs[2][2];
-            int r[16];
-            auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
+                for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k)
+                    load_op(T < NT4 ? buf : buf ^ 1, T % NT4, k, aop[T & 1], tbop[T & 1]);
+            }
+            // minima of this step
+            const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
+            int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
+            int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
 #pragma unroll
-                for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
+            for (int reg = 2; reg < 16; reg += 2) {
+                t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
+                t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
+            }
+            m[qp][t & 3] = t0;
+            m[qp + 1][t & 3] = t1m;
+            int (&rc_)[16] = r[t & 1];
+            if (qp == 0) {
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
-                }
-                if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
-            };
-            load_ops(0, aop[0], tbop[0]);
-            issue(0, 0, accs[0][0], accs[0][1]);
-            load_ops(1, aop[1], tbop[1]);
-            __builtin_amdgcn_sched_barrier(0);
+                for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(acc0[reg], acc1[reg]);
+            } else {
 #pragma unroll
-            for (int st = 0; st < NS; ++st) {
-                const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
-                if (st + 1 < NS) {
-                    const int t1 = (st + 1) / PP, qp1 = 2 * ((st + 1) % PP);
-                    issue(t1, qp1, accs[cur ^ 1][0], accs[cur ^ 1][1]);
-                    if (t1 != t && t1 + 1 < CHUNK / 32) load_ops(t1 + 1, aop[t & 1], tbop[t & 1]);
-                }
-                const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
-                int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
-                int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
-#pragma unroll
-                for (int reg = 2; reg < 16; reg += 2) {
-                    t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
-                    t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
-                }
-                m[qp][t & 3] = t0;
-                m[qp + 1][t & 3] = t1m;
-                if (qp == 0) {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(acc0[reg], acc1[reg]);
-                } else {
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) r[reg] = min(min(r[reg], acc0[reg]), acc1[reg]);
-                }
-                if (qp == QW - 2) {
+                for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(min(rc_[reg], acc0[reg]), acc1[reg]);
+            }
+            // pieces of the previous tile's row butterfly (tile NT4 - 1 of the previous chunk for t = 0)
+            {
+                int (&rp)[16] = r[(t + 1) & 1];
+                const int tp = t > 0 ? t - 1 : NT4 - 1;
+                int *dst = row_dst + (t > 0 ? rbo : rbo_prev) + tp * 32;
+                if constexpr (PP == 1) {                         // (one step a tile: the whole butterfly)
                     int m0, m1;
-                    half_wave_min16<true>(r, lo_lane, m0, m1);
-                    int *dst = row_dst + t * 32;
+                    half_wave_min16<true>(rp, lo_lane, m0, m1);
                     dst[0] = m0;
                     dst[16] = m1;
+                } else {
+                    if (0 * PP / 4 == st % PP) row_min16_piece<0>(rp, bu, lo_lane, dst);
+                    if (1 * PP / 4 == st % PP) row_min16_piece<1>(rp, bu, lo_lane, dst);
+                    if (2 * PP / 4 == st % PP) row_min16_piece<2>(rp, bu, lo_lane, dst);
+                    if (3 * PP / 4 == st % PP) row_min16_piece<3>(rp, bu, lo_lane, dst);
                 }
-                if (st + 1 < NS) {
-                    // one MFMA, then the VALU work that fits beside it
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
             }
+            // one MFMA, then the VALU work (and an operand read) that fits beside it
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
-        wait_direct();
-        __syncthreads();
+        rbo_prev = rbo;
+        rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
     }
-    if (merger) merge_rows(nchunks - 1, (nchunks - 1) & 1);
+    // the last chunk's last tile, its merge
+    {
+        int m0, m1;
+        half_wave_min16<true>(r[(NT4 - 1) & 1], lo_lane, m0, m1);
+        int *dst = row_dst + rbo_prev + (NT4 - 1) * 32;
+        dst[0] = m0;
+        dst[16] = m1;
+    }
+    wait_direct();
+    __syncthreads();
+    merge_rows(nchunks - 1, rbo_prev, merger);
 
     // ---- column results: two smallest of the 4 x 2 group minima of every query, and the groups
     // whose minimum is <= the second smallest (bit k + 4 g: tiles with (tile & 3) == k, lane half g):
