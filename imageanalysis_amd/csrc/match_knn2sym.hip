@@ -333,6 +333,13 @@ struct SymArgs {
                                  //      that can be the query's best or second (narrow exact stage)
 };
 
+__device__ __forceinline__ int uniform32(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ int64_t uniform64(int64_t x)
+{
+    return (int64_t)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) |
+                     (unsigned)__builtin_amdgcn_readfirstlane((int)x));
+}
+
 // min over the 32 lanes of a half wave (lanes 0-31: g = 0, lanes 32-63: g = 1) of 16 registers
 // in 40 VALU instructions (32 half-rate slots) instead of 80: a DPP bank mask selects QUADS
 // (lane bits 3:2) and a row mask 16-lane rows, so the levels "xor 8", "xor 4" and "xor 16" can
@@ -490,11 +497,21 @@ __device__ __forceinline__ void row_min16_piece(int (&r)[16], int (&u)[4], int l
 // The timing ablations (VARIANT), the de-phasing sleep (SLEEP), the Cq floor in the C operand
 // (GROUPLO = false), 256-row chunks (CH), other merge splits and the unpipelined tile loop were
 // measured and removed (profiles/r2_knn2sym_ablate*.txt); the parameters stay in the kernel's name.
+// VARIANT = 1 (ITEMS, form 2: iamx_knn2sym_sweep_items): a workgroup walks an ITEM instead of one
+// (pair, slice) found by a binary search.  A.wg_off is then the item table ([total_wg][3]: first
+// unordered pair, pair count, B slice -- kernels.sym_items), one read per workgroup.  The pairs of
+// an item share their B image (the pairs are sorted by B), so the B slice stays in registers from
+// one pair to the next and is reloaded only where the image changes; per pair the workgroup
+// switches the A stream, the row partials' buffer resource and the column results, and the
+// pipeline drains and refills (a barrier, the pair's first two stages).  One wave launch, one
+// table read and one B load per item instead of per pair.  VARIANT = 0 compiles to the same
+// instructions as before the item walk existed (the pair loop folds away).
 template <int QW, int NW, int VARIANT, int PIPE, int MERGEW, int SLEEP, bool GROUPLO, int CH, int WPE>
 __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
 {
-    static_assert(VARIANT == 0 && PIPE > 0 && MERGEW == 2 && SLEEP == 0 && GROUPLO && CH == 128,
+    static_assert((VARIANT == 0 || VARIANT == 1) && PIPE > 0 && MERGEW == 2 && SLEEP == 0 && GROUPLO && CH == 128,
                   "only the shipped sweep is implemented");
+    constexpr bool ITEMS = VARIANT == 1;
     constexpr int CHUNK = CH;        // train rows per LDS stage
     constexpr int WGROWS = NW * QW * 32;
     constexpr int NT = NW * 64;
@@ -518,314 +535,371 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
         vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
     }
     int lo = 0, hi = A.n_u;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (A.wg_off[mid] <= vid) lo = mid; else hi = mid;
+    if constexpr (!ITEMS)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (A.wg_off[mid] <= vid) lo = mid; else hi = mid;
+        }
+    int u = lo, u_end = 0, item_wgi = 0;
+    if constexpr (ITEMS) {
+        u = A.wg_off[3 * vid];
+        u_end = u + A.wg_off[3 * vid + 1];
+        item_wgi = A.wg_off[3 * vid + 2];
     }
-    const int u = lo;
-    const int bimg = A.upairs[2 * u], aimg = A.upairs[2 * u + 1];
-    const int boff = A.img_off[bimg], nb = A.img_n[bimg];
-    const int aoff = A.img_off[aimg], na = A.img_n[aimg];
-    const int capA = (na + CHUNK - 1) / CHUNK * CHUNK;
-    const int nchunks = capA / CHUNK;
-    const int wgi = vid - A.wg_off[u];
-    const int q0 = wgi * WGROWS + wave * (QW * 32);
-    const bool wave_valid = q0 < nb;
-    const int64_t rbase = A.rowp_off[u] + (int64_t)wgi * capA;
-
-    // B operand: lane (c, g) holds bytes [32s+16g, +16) of the QW consecutive (sorted) B rows
-    // q0 + QW*c + qb; rows past the end repeat the last row (it belongs to this wave, so the
-    // group minimum is unchanged).  Cq of a lane's rows lies in [lo_lane, lo_lane + spread]:
-    // lo_lane rides into the sweep with the C operand, the wave's largest spread S_w (a few
-    // hundred for SIFT-like rows, the rows are sorted) widens the upper bound afterwards.
-    // (GROUPLO: lane c holds the row quadruple rc, c's bits 3:2 moved to the bottom, so that
-    //  the lanes that differ in bits 3:2 hold 4 QW CONSECUTIVE rows)
-    const int rc = (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3);
     v4i bq[QW][4];
-#pragma unroll
-    for (int qb = 0; qb < QW; ++qb) {
-        int row = q0 + QW * rc + qb;
-        row = row < nb ? row : nb - 1;
-        const v4i *src = reinterpret_cast<const v4i *>(A.sdesc + (int64_t)(boff + row) * D);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            bq[qb][s] = ~src[2 * s + g];
-            // one wave per SIMD (512 registers): the B operand -- only ever an MFMA source -- belongs
-            // in the AGPR half, the accumulators the VALU reads in the VGPR half; left alone the
-            // allocator does the opposite and pays a v_accvgpr_read per accumulator element
-            if constexpr (WPE == 1) asm volatile("" : "+a"(bq[qb][s]));
-        }
+    int lo_lane;
+    int bimg_held = -1;              // (ITEMS: the B image whose slice bq holds)
+    // (ITEMS: the item's loop state lives in vector registers and is read back through readfirstlane
+    //  where it is used: the chunk loop already holds 96 scalar registers, and with this state in
+    //  scalar registers too its barrier step spread over three MFMA gaps of 22-27 instructions)
+    if constexpr (ITEMS) asm volatile("" : "+v"(u_end), "+v"(item_wgi), "+v"(bimg_held));
+    // ITEMS: the table entries of the pair the loop runs next, read one pair ahead -- its images and
+    // offsets in front of the current pair's first stages (they land with them), the images' store
+    // offsets and rows behind that pair's first barrier (they land during its chunk loop) -- and
+    // taken through readfirstlane: behind the pair's stores they are vector loads, and the row
+    // partials' buffer resource must stay in scalar registers (no waterfall loop around the merge)
+    int nx_b = 0, nx_a = 0, nx_boff = 0, nx_nb = 0, nx_aoff = 0, nx_na = 0;
+    int64_t nx_rowp = 0;
+    if constexpr (ITEMS) {
+        nx_b = A.upairs[2 * u];
+        nx_a = A.upairs[2 * u + 1];
+        nx_boff = A.img_off[nx_b];
+        nx_nb = A.img_n[nx_b];
+        nx_aoff = A.img_off[nx_a];
+        nx_na = A.img_n[nx_a];
+        nx_rowp = A.rowp_off[u];
     }
-    int lo_lane = 0;
-    {
-        int spread = 0;
-        if (wave_valid) {
-            const int g_lo = rc & ~3, g_hi = rc | 3;
-            const int r_lo = q0 + QW * g_lo < nb ? q0 + QW * g_lo : nb - 1;
-            const int r_hi = q0 + QW * g_hi + QW - 1 < nb ? q0 + QW * g_hi + QW - 1 : nb - 1;
-            lo_lane = A.sn2[boff + r_lo] >> 1;
-            spread = (A.sn2[boff + r_hi] >> 1) - lo_lane;
-        }
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
-        if (lane == 0) lds_cq[wave] = spread;
-    }
-    if (!wave_valid) {
-#pragma unroll
-        for (int k = 0; k < 3 * CHUNK / 64; ++k)
-            lds_row[((k / (CHUNK / 64)) * NW + wave) * CHUNK + (k % (CHUNK / 64)) * 64 + lane] = BIG;
-    }
-    int m[QW][4];
-#pragma unroll
-    for (int qb = 0; qb < QW; ++qb)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) m[qb][k] = BIG;
+    for (;;) {
+        const int bimg = ITEMS ? uniform32(nx_b) : A.upairs[2 * u], aimg = ITEMS ? uniform32(nx_a) : A.upairs[2 * u + 1];
+        const int boff = ITEMS ? uniform32(nx_boff) : A.img_off[bimg], nb = ITEMS ? uniform32(nx_nb) : A.img_n[bimg];
+        const int aoff = ITEMS ? uniform32(nx_aoff) : A.img_off[aimg], na = ITEMS ? uniform32(nx_na) : A.img_n[aimg];
+        const int capA = (na + CHUNK - 1) / CHUNK * CHUNK;
+        const int nchunks = capA / CHUNK;
+        const int wgi = ITEMS ? uniform32(item_wgi) : vid - A.wg_off[u];
+        const int q0 = wgi * WGROWS + wave * (QW * 32);
+        const bool wave_valid = q0 < nb;
+        const int64_t rbase = (ITEMS ? uniform64(nx_rowp) : A.rowp_off[u]) + (int64_t)wgi * capA;
+        // (ITEMS, from the item's second pair on: every wave is past the previous pair's last merge
+        //  -- its lds_row reads -- before an invalid wave refills its rows with BIG below)
+        if constexpr (ITEMS)
+            if (uniform32(bimg_held) >= 0) __syncthreads();
 
-    const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
-    const int32_t *tci = A.sct + aoff;
-    // global -> LDS directly; the XOR swizzle of the 16-byte slots is applied on the source side
-    typedef __attribute__((address_space(3))) void *lds_ptr;
-    auto stage_direct = [&](int ch, int buf) {
+        // B operand: lane (c, g) holds bytes [32s+16g, +16) of the QW consecutive (sorted) B rows
+        // q0 + QW*c + qb; rows past the end repeat the last row (it belongs to this wave, so the
+        // group minimum is unchanged).  Cq of a lane's rows lies in [lo_lane, lo_lane + spread]:
+        // lo_lane rides into the sweep with the C operand, the wave's largest spread S_w (a few
+        // hundred for SIFT-like rows, the rows are sorted) widens the upper bound afterwards.
+        // (GROUPLO: lane c holds the row quadruple rc, c's bits 3:2 moved to the bottom, so that
+        //  the lanes that differ in bits 3:2 hold 4 QW CONSECUTIVE rows)
+        const int rc = (c & 16) | ((c & 3) << 2) | ((c >> 2) & 3);
+        if (!ITEMS || bimg != uniform32(bimg_held)) {
+            bimg_held = bimg;
 #pragma unroll
-        for (int j = 0; j < PIECES; ++j) {
-            const int e = j * NT + tid, row = e >> 3, slot = (e & 7) ^ ((row >> 1) & 7);
-            const int8_t *gsrc = tbase + (int64_t)(ch * CHUNK + row) * D + slot * 16;
-            int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
-            __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
-        }
-        // (Ct: every wave, the waves past CHUNK / 64 repeat the same words -- no branch in the step)
-        __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + (tid & (CHUNK - 1)),
-                                         (lds_ptr)(lds_tb + buf * CHUNK + (wave & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
-    };
-    auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
-    // per train row: the waves' group minima -> (L, U1, U2).  Every wave runs the merge (no branch in
-    // the step it rides in); only waves < MERGEW store, through a buffer resource over this
-    // workgroup's partials: an offset past num_records drops the store
-    constexpr int MROWS = CHUNK / MERGEW;                // rows a merging wave takes
-    static_assert(MROWS == 64 && NW % MERGEW == 0, "one merge row per lane");
-    const int mrow = (wave % MERGEW) * MROWS + lane;
-    const bool merger = wave < MERGEW;
-    // Buffer resource over this workgroup's capA partials (8 bytes each): stride 0 (a raw buffer),
-    // num_records = capA * 8 bytes.  Word 3 of a gfx9 descriptor: DATA_FORMAT = 4 (32 bits) in bits
-    // 15-18, every other field 0 -- the value the gfx9 buffer stores of LLVM and composable_kernel
-    // use for untyped dword access (the untyped store ignores the format, but DATA_FORMAT 0 is
-    // "invalid").  A raw buffer store whose offset + size exceeds num_records is dropped by the
-    // hardware's range check: RANGE_DROP is such an offset for any capA (below 2^31, so offset + 8
-    // does not wrap).
-    constexpr int RSRC_WORD3_DATA_FORMAT_32 = 4 << 15;
-    constexpr int RANGE_DROP = 0x7FFFFFF0;
-    const __amdgpu_buffer_rsrc_t rowp_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(A.rowp + 2 * rbase, (short)0, capA * 8, RSRC_WORD3_DATA_FORMAT_32);
-    // (the waves' spreads S_w, read once behind the first barrier into scalar registers: the merge
-    //  sits on the critical path of its waves -- one wave per SIMD, nothing hides its LDS reads)
-    int spread_w[NW];
-    auto merge_rows = [&](int ch, int rbo, bool store) {
-        int L = BIG, U1 = BIG, U2 = BIG;
+            for (int qb = 0; qb < QW; ++qb) {
+                int row = q0 + QW * rc + qb;
+                row = row < nb ? row : nb - 1;
+                const v4i *src = reinterpret_cast<const v4i *>(A.sdesc + (int64_t)(boff + row) * D);
 #pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const int R = lds_row[rbo + w * CHUNK + mrow];
-            const int lw = R, uw = R + spread_w[w];
-            L = min(L, lw);
-            U2 = min(max(U1, uw), U2);
-            U1 = min(U1, uw);
-        }
-        __builtin_amdgcn_raw_buffer_store_b64(v2i{L, pack_row_bounds(L, U1, U2)}, rowp_rsrc,
-                                              store ? (ch * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
-    };
-
-    // The tile loop is one software pipeline across the chunks (8 MFMAs a step, PP = QW / 2 steps a
-    // tile, 4 tiles a chunk): step s issues the MFMAs of step s + 1 while it takes the minima of
-    // step s; the row butterfly of a tile is cut into four pieces that ride in the steps of the NEXT
-    // tile (a second r set); the operands of tile t + 2 are read two per step from the last step of
-    // tile t on.  The chunk's barrier sits in front of the last step of tile NT4 - 2: every read of
-    // the chunk's LDS stage has been issued by then, so the stage of chunk + 2 goes behind it and the
-    // reads of the next chunk's first two tiles, the first MFMAs of the next chunk, the last tile's
-    // butterfly and the merge of the previous chunk all ride in MFMA gaps.  The last chunk issues
-    // (and drops) one step of MFMAs on a repeated stage: no branch in the loop body.
-    constexpr int PP = QW / 2, NT4 = CHUNK / 32, NS = NT4 * PP;
-    static_assert(NT4 % 2 == 0 && NT4 >= 2, "tile parity must carry across chunks");
-    // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3); after the
-    // butterfly a quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per quad
-    // stores them; the others store into a dump area (no branch in the tile loop: a branch
-    // there makes the compiler sink the column minima below it and keep the accumulators alive).
-    // A wave past the end of the B image (only in the last workgroup of a pair whose B image is not
-    // a multiple of the workgroup's rows) runs the loop too -- it shares the barriers and the merge
-    // -- on repeats of the last B row, with every row store in the dump area and no column result:
-    // MFMA work on a SIMD that would otherwise idle, the price of a branch-free step.
-    int *const row_dst = (lane & 3) == 0 && wave_valid
-        ? lds_row + wave * CHUNK + 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1)
-        : lds_dump + wave * 256 + lane;                 // (+ row buffer offset + tile*32 + 16: inside the dump area)
-    v4i aop[2][4], tbop[2][4];
-    v16i accs[2][2];
-    int r[2][16], bu[4];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r[1][k] = BIG;
-    // read k (0..7) of a tile's operands: the C operand Ct first (the first MFMA needs all of it)
-    auto load_op = [&](int buf, int tile, int k, v4i (&a)[4], v4i (&tbv)[4]) {
-        if (k < 4) {
-            tbv[k] = *reinterpret_cast<const v4i *>(lds_tb + buf * CHUNK + tile * 32 + 8 * k + 4 * g);
-        } else {
-            const int s = k - 4, rr = tile * 32 + c, swz = (rr >> 1) & 7;
-            a[s] = *reinterpret_cast<const v4i *>(lds_tile + buf * (CHUNK * D) + rr * D + (((2 * s + g) ^ swz) * 16));
-        }
-    };
-    auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
-        }
-        if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
-    };
-
-    stage_direct(0, 0);
-    stage_direct(nchunks > 1 ? 1 : 0, 1);
-    wait_direct();
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < NW; ++w) spread_w[w] = __builtin_amdgcn_readfirstlane(lds_cq[w]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) load_op(0, 0, k, aop[0], tbop[0]);
-#pragma unroll
-    for (int k = 0; k < 8 / PP; ++k) load_op(0, 1, k, aop[1], tbop[1]);
-    issue(0, 0, accs[0][0], accs[0][1]);
-    __builtin_amdgcn_sched_barrier(0);
-    // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
-    // (meaningless) last tile into the buffer chunk 2 overwrites
-    int rbo = 0, rbo_prev = 2 * NW * CHUNK;
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const int buf = ch & 1;
-#pragma unroll
-        for (int st = 0; st < NS; ++st) {
-            const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
-            if (st == (NT4 - 1) * PP - 1) {
-                // every read of this chunk's stage is done (lgkmcnt), the next chunk's stage has landed
-                // (vmcnt): the stage of chunk + 2 may overwrite this one
-                __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
-                __syncthreads();
-                stage_direct(ch + 2 < nchunks ? ch + 2 : nchunks - 1, buf);
-                merge_rows(ch - 1, rbo_prev, merger && ch > 0);
+                for (int s = 0; s < 4; ++s) {
+                    bq[qb][s] = ~src[2 * s + g];
+                    // one wave per SIMD (512 registers): the B operand -- only ever an MFMA source -- belongs
+                    // in the AGPR half, the accumulators the VALU reads in the VGPR half; left alone the
+                    // allocator does the opposite and pays a v_accvgpr_read per accumulator element
+                    if constexpr (WPE == 1) asm volatile("" : "+a"(bq[qb][s]));
+                }
             }
-            // the MFMAs of the next step (the next chunk's first step from the last one)
-            if (st + 1 < NS) issue((st + 1) / PP, 2 * ((st + 1) % PP), accs[cur ^ 1][0], accs[cur ^ 1][1]);
-            else issue(0, 0, accs[cur ^ 1][0], accs[cur ^ 1][1]);
-            // the operand reads of tile T (flattened across chunks) run from the last step of tile T - 2
-            // to the step before T's first MFMAs, 8 / PP a step: here those of tile T = (st + 1) / PP + 1
+            lo_lane = 0;
             {
-                const int T = (st + 1) / PP + 1, i = (st + 1) % PP;
+                int spread = 0;
+                if (wave_valid) {
+                    const int g_lo = rc & ~3, g_hi = rc | 3;
+                    const int r_lo = q0 + QW * g_lo < nb ? q0 + QW * g_lo : nb - 1;
+                    const int r_hi = q0 + QW * g_hi + QW - 1 < nb ? q0 + QW * g_hi + QW - 1 : nb - 1;
+                    lo_lane = A.sn2[boff + r_lo] >> 1;
+                    spread = (A.sn2[boff + r_hi] >> 1) - lo_lane;
+                }
 #pragma unroll
-                for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k)
-                    load_op(T < NT4 ? buf : buf ^ 1, T % NT4, k, aop[T & 1], tbop[T & 1]);
+                for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
+                if (lane == 0) lds_cq[wave] = spread;
             }
-            // minima of this step
-            const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
-            int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
-            int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
+        }
+        if (!wave_valid) {
 #pragma unroll
-            for (int reg = 2; reg < 16; reg += 2) {
-                t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
-                t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
+            for (int k = 0; k < 3 * CHUNK / 64; ++k)
+                lds_row[((k / (CHUNK / 64)) * NW + wave) * CHUNK + (k % (CHUNK / 64)) * 64 + lane] = BIG;
+        }
+        int m[QW][4];
+#pragma unroll
+        for (int qb = 0; qb < QW; ++qb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m[qb][k] = BIG;
+
+        const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
+        const int32_t *tci = A.sct + aoff;
+        // global -> LDS directly; the XOR swizzle of the 16-byte slots is applied on the source side
+        typedef __attribute__((address_space(3))) void *lds_ptr;
+        auto stage_direct = [&](int ch, int buf) {
+#pragma unroll
+            for (int j = 0; j < PIECES; ++j) {
+                const int e = j * NT + tid, row = e >> 3, slot = (e & 7) ^ ((row >> 1) & 7);
+                const int8_t *gsrc = tbase + (int64_t)(ch * CHUNK + row) * D + slot * 16;
+                int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
+                __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
             }
-            m[qp][t & 3] = t0;
-            m[qp + 1][t & 3] = t1m;
-            int (&rc_)[16] = r[t & 1];
-            if (qp == 0) {
+            // (Ct: every wave, the waves past CHUNK / 64 repeat the same words -- no branch in the step)
+            __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + (tid & (CHUNK - 1)),
+                                             (lds_ptr)(lds_tb + buf * CHUNK + (wave & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
+        };
+        auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
+        // per train row: the waves' group minima -> (L, U1, U2).  Every wave runs the merge (no branch in
+        // the step it rides in); only waves < MERGEW store, through a buffer resource over this
+        // workgroup's partials: an offset past num_records drops the store
+        constexpr int MROWS = CHUNK / MERGEW;                // rows a merging wave takes
+        static_assert(MROWS == 64 && NW % MERGEW == 0, "one merge row per lane");
+        const int mrow = (wave % MERGEW) * MROWS + lane;
+        const bool merger = wave < MERGEW;
+        // Buffer resource over this workgroup's capA partials (8 bytes each): stride 0 (a raw buffer),
+        // num_records = capA * 8 bytes.  Word 3 of a gfx9 descriptor: DATA_FORMAT = 4 (32 bits) in bits
+        // 15-18, every other field 0 -- the value the gfx9 buffer stores of LLVM and composable_kernel
+        // use for untyped dword access (the untyped store ignores the format, but DATA_FORMAT 0 is
+        // "invalid").  A raw buffer store whose offset + size exceeds num_records is dropped by the
+        // hardware's range check: RANGE_DROP is such an offset for any capA (below 2^31, so offset + 8
+        // does not wrap).
+        constexpr int RSRC_WORD3_DATA_FORMAT_32 = 4 << 15;
+        constexpr int RANGE_DROP = 0x7FFFFFF0;
+        const __amdgpu_buffer_rsrc_t rowp_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(A.rowp + 2 * rbase, (short)0, capA * 8, RSRC_WORD3_DATA_FORMAT_32);
+        // (the waves' spreads S_w, read once behind the first barrier into scalar registers: the merge
+        //  sits on the critical path of its waves -- one wave per SIMD, nothing hides its LDS reads)
+        int spread_w[NW];
+        auto merge_rows = [&](int ch, int rbo, bool store) {
+            int L = BIG, U1 = BIG, U2 = BIG;
 #pragma unroll
-                for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(acc0[reg], acc1[reg]);
+            for (int w = 0; w < NW; ++w) {
+                const int R = lds_row[rbo + w * CHUNK + mrow];
+                const int lw = R, uw = R + spread_w[w];
+                L = min(L, lw);
+                U2 = min(max(U1, uw), U2);
+                U1 = min(U1, uw);
+            }
+            __builtin_amdgcn_raw_buffer_store_b64(v2i{L, pack_row_bounds(L, U1, U2)}, rowp_rsrc,
+                                                  store ? (ch * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
+        };
+
+        // The tile loop is one software pipeline across the chunks (8 MFMAs a step, PP = QW / 2 steps a
+        // tile, 4 tiles a chunk): step s issues the MFMAs of step s + 1 while it takes the minima of
+        // step s; the row butterfly of a tile is cut into four pieces that ride in the steps of the NEXT
+        // tile (a second r set); the operands of tile t + 2 are read two per step from the last step of
+        // tile t on.  The chunk's barrier sits in front of the last step of tile NT4 - 2: every read of
+        // the chunk's LDS stage has been issued by then, so the stage of chunk + 2 goes behind it and the
+        // reads of the next chunk's first two tiles, the first MFMAs of the next chunk, the last tile's
+        // butterfly and the merge of the previous chunk all ride in MFMA gaps.  The last chunk issues
+        // (and drops) one step of MFMAs on a repeated stage: no branch in the loop body.
+        constexpr int PP = QW / 2, NT4 = CHUNK / 32, NS = NT4 * PP;
+        static_assert(NT4 % 2 == 0 && NT4 >= 2, "tile parity must carry across chunks");
+        // accumulator register reg of lane half g is tile row 8*(reg>>2) + 4*g + (reg&3); after the
+        // butterfly a quad holds reg = 4*b4 + 2*b2 + b3 (m0) and 8 + that (m1).  One lane per quad
+        // stores them; the others store into a dump area (no branch in the tile loop: a branch
+        // there makes the compiler sink the column minima below it and keep the accumulators alive).
+        // A wave past the end of the B image (only in the last workgroup of a pair whose B image is not
+        // a multiple of the workgroup's rows) runs the loop too -- it shares the barriers and the merge
+        // -- on repeats of the last B row, with every row store in the dump area and no column result:
+        // MFMA work on a SIMD that would otherwise idle, the price of a branch-free step.
+        int *const row_dst = (lane & 3) == 0 && wave_valid
+            ? lds_row + wave * CHUNK + 8 * ((lane >> 4) & 1) + 4 * g + 2 * ((lane >> 2) & 1) + ((lane >> 3) & 1)
+            : lds_dump + wave * 256 + lane;                 // (+ row buffer offset + tile*32 + 16: inside the dump area)
+        v4i aop[2][4], tbop[2][4];
+        v16i accs[2][2];
+        int r[2][16], bu[4];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) r[1][k] = BIG;
+        // read k (0..7) of a tile's operands: the C operand Ct first (the first MFMA needs all of it)
+        auto load_op = [&](int buf, int tile, int k, v4i (&a)[4], v4i (&tbv)[4]) {
+            if (k < 4) {
+                tbv[k] = *reinterpret_cast<const v4i *>(lds_tb + buf * CHUNK + tile * 32 + 8 * k + 4 * g);
             } else {
+                const int s = k - 4, rr = tile * 32 + c, swz = (rr >> 1) & 7;
+                a[s] = *reinterpret_cast<const v4i *>(lds_tile + buf * (CHUNK * D) + rr * D + (((2 * s + g) ^ swz) * 16));
+            }
+        };
+        auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
 #pragma unroll
-                for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(min(rc_[reg], acc0[reg]), acc1[reg]);
-            }
-            // pieces of the previous tile's row butterfly (tile NT4 - 1 of the previous chunk for t = 0)
-            {
-                int (&rp)[16] = r[(t + 1) & 1];
-                const int tp = t > 0 ? t - 1 : NT4 - 1;
-                int *dst = row_dst + (t > 0 ? rbo : rbo_prev) + tp * 32;
-                if constexpr (PP == 1) {                         // (one step a tile: the whole butterfly)
-                    int m0, m1;
-                    half_wave_min16<true>(rp, lo_lane, m0, m1);
-                    dst[0] = m0;
-                    dst[16] = m1;
-                } else {
-                    if (0 * PP / 4 == st % PP) row_min16_piece<0>(rp, bu, lo_lane, dst);
-                    if (1 * PP / 4 == st % PP) row_min16_piece<1>(rp, bu, lo_lane, dst);
-                    if (2 * PP / 4 == st % PP) row_min16_piece<2>(rp, bu, lo_lane, dst);
-                    if (3 * PP / 4 == st % PP) row_min16_piece<3>(rp, bu, lo_lane, dst);
-                }
-            }
-            // one MFMA, then the VALU work (and an operand read) that fits beside it
+            for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
+            for (int s = 0; s < 4; ++s) {
+                acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
             }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        rbo_prev = rbo;
-        rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
-    }
-    // the last chunk's last tile, its merge
-    {
-        int m0, m1;
-        half_wave_min16<true>(r[(NT4 - 1) & 1], lo_lane, m0, m1);
-        int *dst = row_dst + rbo_prev + (NT4 - 1) * 32;
-        dst[0] = m0;
-        dst[16] = m1;
-    }
-    wait_direct();
-    __syncthreads();
-    merge_rows(nchunks - 1, rbo_prev, merger);
+            if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
+        };
 
-    // ---- column results: two smallest of the 4 x 2 group minima of every query, and the groups
-    // whose minimum is <= the second smallest (bit k + 4 g: tiles with (tile & 3) == k, lane half g):
-    // the only train rows that can be the query's best or second (narrow exact stage).  The masks of
-    // a lane's QW queries travel as ONE word (4 bits each: one lane exchange, one store for QW = 8).
-    if (wave_valid) {
-        unsigned ownpack = 0;
-        int v1s[QW], v2s[QW];
-#pragma unroll
-        for (int qb = 0; qb < QW; ++qb) {
-            const int lo01 = min(m[qb][0], m[qb][1]), hi01 = max(m[qb][0], m[qb][1]);
-            const int lo23 = min(m[qb][2], m[qb][3]), hi23 = max(m[qb][2], m[qb][3]);
-            const int a1 = min(lo01, lo23), a2 = min(max(lo01, lo23), min(hi01, hi23));
-            const int b1 = __shfl_xor(a1, 32), b2 = __shfl_xor(a2, 32);
-            const int v1 = min(a1, b1), v2 = min(max(a1, b1), min(a2, b2));
-            v1s[qb] = v1;
-            v2s[qb] = v2;
-#if !defined(IAMX_T_NOMASK)
-            const unsigned own = (m[qb][0] <= v2 ? 1u : 0u) | (m[qb][1] <= v2 ? 2u : 0u) |
-                                 (m[qb][2] <= v2 ? 4u : 0u) | (m[qb][3] <= v2 ? 8u : 0u);
-            ownpack |= own << (4 * qb);
-#endif
+        if constexpr (ITEMS) {           // (the last pair of the item reads its own entries again)
+            const int un = u + 1 < u_end ? u + 1 : u;
+            nx_b = A.upairs[2 * un];
+            nx_a = A.upairs[2 * un + 1];
+            nx_rowp = A.rowp_off[un];
         }
-        const unsigned othpack = A.colmask ? (unsigned)__shfl_xor((int)ownpack, 32) : 0u;
-        const int row0 = q0 + QW * rc;
-        if (g == 0) {
+        stage_direct(0, 0);
+        stage_direct(nchunks > 1 ? 1 : 0, 1);
+        wait_direct();
+        __syncthreads();
 #pragma unroll
-            for (int qb = 0; qb < QW; ++qb)
-                if (row0 + qb < nb)
-                    *reinterpret_cast<v2i *>(A.col + 2 * (A.col_off[u] + row0 + qb)) = v2i{v1s[qb], v2s[qb]};
-            if (A.colmask) {
-                // byte qb = own nibble | other half's nibble << 4
-                uint8_t *dst = A.colmask + A.col_off[u] + row0;
-                if (QW == 8 && row0 + QW <= nb) {
-                    auto spread = [](unsigned nib4) {    // four nibbles -> the low nibbles of four bytes
-                        const unsigned x = (nib4 | (nib4 << 8)) & 0x00FF00FFu;
-                        return (x | (x << 4)) & 0x0F0F0F0Fu;
-                    };
-                    const unsigned lo = spread(ownpack & 0xFFFFu) | (spread(othpack & 0xFFFFu) << 4);
-                    const unsigned hi = spread(ownpack >> 16) | (spread(othpack >> 16) << 4);
-                    *reinterpret_cast<v2u *>(dst) = v2u{lo, hi};
+        for (int w = 0; w < NW; ++w) spread_w[w] = __builtin_amdgcn_readfirstlane(lds_cq[w]);
+        if constexpr (ITEMS) {
+            const int b = uniform32(nx_b), a = uniform32(nx_a);
+            nx_boff = A.img_off[b];
+            nx_nb = A.img_n[b];
+            nx_aoff = A.img_off[a];
+            nx_na = A.img_n[a];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) load_op(0, 0, k, aop[0], tbop[0]);
+#pragma unroll
+        for (int k = 0; k < 8 / PP; ++k) load_op(0, 1, k, aop[1], tbop[1]);
+        issue(0, 0, accs[0][0], accs[0][1]);
+        __builtin_amdgcn_sched_barrier(0);
+        // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
+        // (meaningless) last tile into the buffer chunk 2 overwrites
+        int rbo = 0, rbo_prev = 2 * NW * CHUNK;
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const int buf = ch & 1;
+#pragma unroll
+            for (int st = 0; st < NS; ++st) {
+                const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
+                if (st == (NT4 - 1) * PP - 1) {
+                    // every read of this chunk's stage is done (lgkmcnt), the next chunk's stage has landed
+                    // (vmcnt): the stage of chunk + 2 may overwrite this one
+                    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
+                    __syncthreads();
+                    stage_direct(ch + 2 < nchunks ? ch + 2 : nchunks - 1, buf);
+                    merge_rows(ch - 1, rbo_prev, merger && ch > 0);
+                }
+                // the MFMAs of the next step (the next chunk's first step from the last one)
+                if (st + 1 < NS) issue((st + 1) / PP, 2 * ((st + 1) % PP), accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                else issue(0, 0, accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                // the operand reads of tile T (flattened across chunks) run from the last step of tile T - 2
+                // to the step before T's first MFMAs, 8 / PP a step: here those of tile T = (st + 1) / PP + 1
+                {
+                    const int T = (st + 1) / PP + 1, i = (st + 1) % PP;
+#pragma unroll
+                    for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k)
+                        load_op(T < NT4 ? buf : buf ^ 1, T % NT4, k, aop[T & 1], tbop[T & 1]);
+                }
+                // minima of this step
+                const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
+                int t0 = min(min(m[qp][t & 3], acc0[0]), acc0[1]);
+                int t1m = min(min(m[qp + 1][t & 3], acc1[0]), acc1[1]);
+#pragma unroll
+                for (int reg = 2; reg < 16; reg += 2) {
+                    t0 = min(min(t0, acc0[reg]), acc0[reg + 1]);
+                    t1m = min(min(t1m, acc1[reg]), acc1[reg + 1]);
+                }
+                m[qp][t & 3] = t0;
+                m[qp + 1][t & 3] = t1m;
+                int (&rc_)[16] = r[t & 1];
+                if (qp == 0) {
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(acc0[reg], acc1[reg]);
                 } else {
 #pragma unroll
-                    for (int qb = 0; qb < QW; ++qb)
-                        if (row0 + qb < nb)
-                            dst[qb] = (uint8_t)(((ownpack >> (4 * qb)) & 15u) | (((othpack >> (4 * qb)) & 15u) << 4));
+                    for (int reg = 0; reg < 16; ++reg) rc_[reg] = min(min(rc_[reg], acc0[reg]), acc1[reg]);
+                }
+                // pieces of the previous tile's row butterfly (tile NT4 - 1 of the previous chunk for t = 0)
+                {
+                    int (&rp)[16] = r[(t + 1) & 1];
+                    const int tp = t > 0 ? t - 1 : NT4 - 1;
+                    int *dst = row_dst + (t > 0 ? rbo : rbo_prev) + tp * 32;
+                    if constexpr (PP == 1) {                         // (one step a tile: the whole butterfly)
+                        int m0, m1;
+                        half_wave_min16<true>(rp, lo_lane, m0, m1);
+                        dst[0] = m0;
+                        dst[16] = m1;
+                    } else {
+                        if (0 * PP / 4 == st % PP) row_min16_piece<0>(rp, bu, lo_lane, dst);
+                        if (1 * PP / 4 == st % PP) row_min16_piece<1>(rp, bu, lo_lane, dst);
+                        if (2 * PP / 4 == st % PP) row_min16_piece<2>(rp, bu, lo_lane, dst);
+                        if (3 * PP / 4 == st % PP) row_min16_piece<3>(rp, bu, lo_lane, dst);
+                    }
+                }
+                // one MFMA, then the VALU work (and an operand read) that fits beside it
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            rbo_prev = rbo;
+            rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
+        }
+        // (ITEMS: this pair's first column-result row, read here -- it lands with the vmcnt(0) below --
+        //  rather than carried through the chunk loop in scalar registers, which the loop needs)
+        int64_t col_v = 0;
+        if constexpr (ITEMS) col_v = A.col_off[u];
+        // the last chunk's last tile, its merge
+        {
+            int m0, m1;
+            half_wave_min16<true>(r[(NT4 - 1) & 1], lo_lane, m0, m1);
+            int *dst = row_dst + rbo_prev + (NT4 - 1) * 32;
+            dst[0] = m0;
+            dst[16] = m1;
+        }
+        wait_direct();
+        __syncthreads();
+        merge_rows(nchunks - 1, rbo_prev, merger);
+
+        const int64_t col_u = ITEMS ? uniform64(col_v) : 0;
+        // ---- column results: two smallest of the 4 x 2 group minima of every query, and the groups
+        // whose minimum is <= the second smallest (bit k + 4 g: tiles with (tile & 3) == k, lane half g):
+        // the only train rows that can be the query's best or second (narrow exact stage).  The masks of
+        // a lane's QW queries travel as ONE word (4 bits each: one lane exchange, one store for QW = 8).
+        if (wave_valid) {
+            unsigned ownpack = 0;
+            int v1s[QW], v2s[QW];
+#pragma unroll
+            for (int qb = 0; qb < QW; ++qb) {
+                const int lo01 = min(m[qb][0], m[qb][1]), hi01 = max(m[qb][0], m[qb][1]);
+                const int lo23 = min(m[qb][2], m[qb][3]), hi23 = max(m[qb][2], m[qb][3]);
+                const int a1 = min(lo01, lo23), a2 = min(max(lo01, lo23), min(hi01, hi23));
+                const int b1 = __shfl_xor(a1, 32), b2 = __shfl_xor(a2, 32);
+                const int v1 = min(a1, b1), v2 = min(max(a1, b1), min(a2, b2));
+                v1s[qb] = v1;
+                v2s[qb] = v2;
+#if !defined(IAMX_T_NOMASK)
+                const unsigned own = (m[qb][0] <= v2 ? 1u : 0u) | (m[qb][1] <= v2 ? 2u : 0u) |
+                                     (m[qb][2] <= v2 ? 4u : 0u) | (m[qb][3] <= v2 ? 8u : 0u);
+                ownpack |= own << (4 * qb);
+#endif
+            }
+            const unsigned othpack = A.colmask ? (unsigned)__shfl_xor((int)ownpack, 32) : 0u;
+            const int row0 = q0 + QW * rc;
+            if (g == 0) {
+#pragma unroll
+                for (int qb = 0; qb < QW; ++qb)
+                    if (row0 + qb < nb)
+                        *reinterpret_cast<v2i *>(A.col + 2 * ((ITEMS ? col_u : A.col_off[u]) + row0 + qb)) = v2i{v1s[qb], v2s[qb]};
+                if (A.colmask) {
+                    // byte qb = own nibble | other half's nibble << 4
+                    uint8_t *dst = A.colmask + (ITEMS ? col_u : A.col_off[u]) + row0;
+                    if (QW == 8 && row0 + QW <= nb) {
+                        auto spread = [](unsigned nib4) {    // four nibbles -> the low nibbles of four bytes
+                            const unsigned x = (nib4 | (nib4 << 8)) & 0x00FF00FFu;
+                            return (x | (x << 4)) & 0x0F0F0F0Fu;
+                        };
+                        const unsigned lo = spread(ownpack & 0xFFFFu) | (spread(othpack & 0xFFFFu) << 4);
+                        const unsigned hi = spread(ownpack >> 16) | (spread(othpack >> 16) << 4);
+                        *reinterpret_cast<v2u *>(dst) = v2u{lo, hi};
+                    } else {
+#pragma unroll
+                        for (int qb = 0; qb < QW; ++qb)
+                            if (row0 + qb < nb)
+                                dst[qb] = (uint8_t)(((ownpack >> (4 * qb)) & 15u) | (((othpack >> (4 * qb)) & 15u) << 4));
+                    }
                 }
             }
         }
+        if constexpr (!ITEMS) break;
+        else if (++u == uniform32(u_end)) break;
     }
 }
 
@@ -1968,13 +2042,14 @@ extern "C" int iamx_desc3_pack_batch_u8(const uint8_t *src, const int64_t *src_o
 #define SWEEP_FORM2 8, 4, 0, 5, 2, 0, true, 128, 1
 #define SWEEP_FORM1 4, 4, 0, 6, 2, 0, true, 128, 2
 #define SWEEP_FORM0 2, 4, 0, 6, 2, 0, true, 128, 2
+#define SWEEP_ITEMS2 8, 4, 1, 5, 2, 0, true, 128, 1      // form 2 walking items (VARIANT 1)
 #define SWEEP_STR2(...) #__VA_ARGS__
 #define SWEEP_STR(...) SWEEP_STR2(__VA_ARGS__)
 
 extern "C" const char *iamx_knn2sym_kernel_id(int form)
 {
     switch (form) {
-    case 2: return "knn2sym_kernel<" SWEEP_STR(SWEEP_FORM2) ">";
+    case 2: return "knn2sym_kernel<" SWEEP_STR(SWEEP_ITEMS2) ">";     // (PairBatch: the item entry)
     case 1: return "knn2sym_kernel<" SWEEP_STR(SWEEP_FORM1) ">";
     case 0: return "knn2sym_kernel<" SWEEP_STR(SWEEP_FORM0) ">";
     default: return "";
@@ -2004,6 +2079,26 @@ extern "C" int iamx_knn2sym_sweep(const int8_t *sdesc, const int32_t *sn2, const
     else if (form == 1) hipLaunchKernelGGL((knn2sym_kernel<SWEEP_FORM1>), g, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((knn2sym_kernel<SWEEP_FORM0>), g, dim3(256), 0, st, a);
     return iamx::check_launch("iamx_knn2sym_sweep");
+}
+
+extern "C" int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2, const int32_t *sct,
+                                        const int32_t *img_off, const int32_t *img_n,
+                                        const int32_t *upairs, const int32_t *items,
+                                        const int64_t *col_off, const int64_t *rowp_off, int n_u,
+                                        int n_items, int32_t *col, int32_t *rowp, uint8_t *colmask,
+                                        void *stream)
+{
+    IAMX_REQUIRE(sdesc && sn2 && sct && img_off && img_n && upairs && items && col_off && rowp_off &&
+                     col && rowp,
+                 "null pointer");
+    IAMX_REQUIRE(n_u >= 0 && n_items >= 0, "negative count");
+    if (n_u == 0 || n_items == 0) return IAMX_OK;
+    // (the item walk reads its table through wg_off, its count through total_wg)
+    SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, items, col_off, rowp_off, col, rowp, n_u, n_items,
+              colmask};
+    hipLaunchKernelGGL((knn2sym_kernel<SWEEP_ITEMS2>), dim3((unsigned)n_items), dim3(256), 0,
+                       iamx::as_stream(stream), a);
+    return iamx::check_launch("iamx_knn2sym_sweep_items");
 }
 
 // IAMX_EXACT_NARROW=0: every candidate through the full scan (A/B, tests)

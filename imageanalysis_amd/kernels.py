@@ -370,7 +370,13 @@ def sym_tables(pairs, counts, caps3):
     image pair exactly once.  Unordered pair u = (B image, A image): B = the query image of the
     first of its two ordered pairs; the list is sorted by A so that consecutive workgroups
     re-read the same streamed rows from L2.  osrc[p] = (u, role) with role 0 when the query image
-    of ordered pair p is B (its bounds come from the lane-local column direction), 1 when it is A."""
+    of ordered pair p is B (its bounds come from the lane-local column direction), 1 when it is A.
+
+    Where the form-2 item walk takes more than one pair per workgroup (sym_item_pairs > 1: short
+    images), B is instead the TRAIN image of the first ordered pair and the list is sorted by
+    (B, A): in a train-major schedule consecutive pairs then share B, which the walk keeps in
+    registers (sym_items).  S (1 for forms 0 and 1) is returned with the tables, so that the order
+    and the item table follow one rule.  The bounds are valid whichever side is B."""
     pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
     P = len(pairs)
     if P == 0 or P % 2 or (pairs[:, 0] == pairs[:, 1]).any():
@@ -389,14 +395,20 @@ def sym_tables(pairs, counts, caps3):
         return None                                   # a pair without its mirror
     mirror = order[where]
     first = np.nonzero(np.arange(P) < mirror)[0]      # one ordered pair per unordered pair
-    first = first[np.argsort(pairs[first, 1], kind='stable')]
-    up = pairs[first]                                 # (B, A)
-    n_u = len(up)
-    nb = counts[up[:, 0]]
-    mn = int(min(nb.min(), counts[up[:, 1]].min()))
+    mn = int(counts[pairs[first]].min())
     if mn < 2:
         return None
     form = 0 if mn < 2048 else (2 if mn >= 4096 else 1)
+    S = sym_item_pairs(counts[pairs[first].ravel()]) if form == 2 else 1
+    items = S > 1
+    if items:                                         # B = train image, sorted by (B, A)
+        first = first[np.lexsort((pairs[first, 0], pairs[first, 1]))]
+        up = np.ascontiguousarray(pairs[first, ::-1])
+    else:                                             # B = query image, sorted by A
+        first = first[np.argsort(pairs[first, 1], kind='stable')]
+        up = pairs[first]
+    n_u = len(up)
+    nb = counts[up[:, 0]]
     rows_wg = SYM_ROWS_PER_WG[form]
     nwg = (nb + rows_wg - 1) // rows_wg
     wg = np.zeros(n_u + 1, np.int64)
@@ -410,8 +422,44 @@ def sym_tables(pairs, counts, caps3):
     osrc = np.zeros((P, 2), np.int32)
     osrc[first, 0] = np.arange(n_u)
     osrc[mirror[first], 0] = np.arange(n_u)
-    osrc[mirror[first], 1] = 1
-    return dict(upairs=up, form=form, wg=wg, col_off=col_off, rowp_off=rowp_off, osrc=osrc)
+    osrc[first if items else mirror[first], 1] = 1
+    return dict(upairs=up, form=form, wg=wg, col_off=col_off, rowp_off=rowp_off, osrc=osrc, S=S)
+
+
+def sym_item_pairs(counts_a):
+    """S, the unordered pairs a form-2 workgroup walks (iamx_knn2sym_sweep_items), from the rows of
+    the batch's images (either side of a pair may become A).  A workgroup pays its start-up (wave launch, table reads, B slice load)
+    once per item: S > 1 only where that start-up is a sizeable share of a pair's work -- at
+    4096-row A images (32 chunks) S = 4 saves about 5 % of the sweep (profiles/r8_sweep_startup.txt),
+    at 16 384 rows and more (128+ chunks) S = 1.  Rule: S = 16384 // (largest A cap), within 1..4."""
+    cap = (int(np.max(counts_a)) + 127) // 128 * 128
+    return int(min(4, max(1, 16384 // cap)))
+
+
+def sym_items(upairs, counts, S, rows_wg=1024):
+    """Item table [n_items][3] int32 of iamx_knn2sym_sweep_items: (first unordered pair, pair count,
+    B slice).  Items of S consecutive pairs of `upairs` ((B, A), sorted by B: sym_tables); an item
+    may cross a change of B image (the kernel reloads B there), which keeps every item S pairs long
+    -- the item count of a launch a multiple of the CU count where the pair count allows it -- but
+    it never mixes pairs of different slice counts (nwg).  The slices of one run of pairs are the
+    fastest-moving index: they get consecutive workgroup ids (one XCD, the A rows from L2)."""
+    upairs = np.asarray(upairs, np.int64).reshape(-1, 2)
+    counts = np.asarray(counts, np.int64)
+    n_u = len(upairs)
+    if n_u == 0:
+        return np.zeros((0, 3), np.int32)
+    nwg = (counts[upairs[:, 0]] + rows_wg - 1) // rows_wg
+    # runs of pairs with equal nwg, each cut into pieces of at most S pairs
+    brk = np.flatnonzero(np.diff(nwg)) + 1
+    starts, ends = np.concatenate([[0], brk]), np.concatenate([brk, [n_u]])
+    first = np.concatenate([np.arange(a, b, S) for a, b in zip(starts, ends)])
+    cnt = np.minimum(S, ends[np.searchsorted(ends, first, side='right')] - first)
+    k = nwg[first]
+    it = np.zeros((int(k.sum()), 3), np.int32)
+    it[:, 0] = np.repeat(first, k)
+    it[:, 1] = np.repeat(cnt, k)
+    it[:, 2] = np.arange(len(it)) - np.repeat(np.cumsum(k) - k, k)
+    return it
 
 
 def knn2_pairs(store, pairs):
@@ -757,10 +805,25 @@ class PairBatch(object):
         self.d_col_off = up(t['col_off'][:-1].copy())
         self.d_rowp_off = up(t['rowp_off'][:-1].copy())
         self.d_osrc = up(t['osrc'])
+        self.sym_items_s = t['S']
+        # form 2 with S > 1 walks items of S pairs that share their B image; at S = 1 (long images) the
+        # one-pair kernel runs: the item kernel with one pair per item measured 0.6-0.9 % slower there
+        # (profiles/r8_sweep_time.txt)
+        if self.sym_items_s > 1:
+            items = sym_items(t['upairs'], self.store.counts, self.sym_items_s)
+            self.n_sym_items = len(items)
+            self.d_sym_items = up(items)
 
     def run_sym_sweep(self, ws):
         st = self.store
         ws.ensure_sym(self.sym_col_rows, self.sym_rowp_rows)
+        if self.sym_items_s > 1:
+            check(lib().iamx_knn2sym_sweep_items(_ptr(st.desc3), _ptr(st.sn2), _ptr(st.sct), _ptr(st.img_off3),
+                                                 _ptr(st.img_n), _ptr(self.d_upairs), _ptr(self.d_sym_items),
+                                                 _ptr(self.d_col_off), _ptr(self.d_rowp_off), self.n_u,
+                                                 self.n_sym_items, _ptr(ws.col), _ptr(ws.rowp),
+                                                 _ptr(ws.colmask), stream_ptr()), 'iamx_knn2sym_sweep_items')
+            return
         check(lib().iamx_knn2sym_sweep(_ptr(st.desc3), _ptr(st.sn2), _ptr(st.sct), _ptr(st.img_off3),
                                        _ptr(st.img_n), _ptr(self.d_upairs), _ptr(self.d_sym_wg),
                                        _ptr(self.d_col_off), _ptr(self.d_rowp_off), self.n_u,

@@ -266,6 +266,17 @@ int iamx_knn2sym_sweep(const int8_t *sdesc, const int32_t *sn2, const int32_t *s
                        const int32_t *wg_off, const int64_t *col_off, const int64_t *rowp_off,
                        int n_u, int total_wg, int form, int32_t *col, int32_t *rowp,
                        uint8_t *colmask /* may be NULL */, void *stream);
+/* iamx_knn2sym_sweep for form 2 with the pairs dealt as ITEMS: items DEV [n_items][3] int32 =
+ * (first unordered pair, pair count, B slice = workgroup index within the pair), one workgroup per
+ * item; every pair of an item has the same number of 1024-row B slices, and the pairs should be
+ * sorted by B image (the B slice is loaded again only where the image changes).  col, rowp and
+ * colmask are those of iamx_knn2sym_sweep with form 2 for the same upairs / col_off / rowp_off,
+ * bit for bit (kernels.sym_items builds the table). */
+int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2, const int32_t *sct,
+                             const int32_t *img_off, const int32_t *img_n, const int32_t *upairs,
+                             const int32_t *items, const int64_t *col_off, const int64_t *rowp_off,
+                             int n_u, int n_items, int32_t *col, int32_t *rowp,
+                             uint8_t *colmask /* may be NULL */, void *stream);
 int iamx_knn2sym_candidates(const int32_t *sn2, const int32_t *sperm, const int32_t *img_off,
                             const int32_t *img_n, const int32_t *pairs, const int32_t *osrc,
                             const int32_t *wg_off, const int64_t *col_off, const int64_t *rowp_off,
