@@ -111,6 +111,11 @@ SIGNATURES = {
     'iamx_jpeg_decode_coefficients': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'iamx_jpeg_workspace_bytes': (c_int64, [c_void_p]),
     'iamx_jpeg_reconstruct': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    'iamx_jpeg_entropy_header_bytes': (c_int64, []),
+    'iamx_jpeg_entropy_prepare': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64]),
+    'iamx_jpeg_entropy_workspace_bytes': (c_int64, [c_void_p]),
+    'iamx_jpeg_entropy_decode': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_void_p, c_int64, c_void_p, c_void_p]),
     'iamx_gzip_f32_from_u8_bound': (c_int64, [c_int64, c_int64]),
     'iamx_gzip_f32_from_u8': (c_int64, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64]),
     'iamx_gzip_members_bound': (c_int64, [c_int64, c_int64]),

@@ -8,12 +8,12 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 OUT="$HERE/../libiamx.so"
 OBJDIR="$HERE/obj"
-SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/jpeg.hip $HERE/cache_codec.hip"
+SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip"
 mkdir -p "$OBJDIR"
 OBJS=""
 for f in $SRCS; do
     o="$OBJDIR/$(basename ${f%.hip}).o"
-    if [ -n "$IAMX_REBUILD" ] || [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/iamx_common.h" -nt "$o" ] || [ "$HERE/../../include/iamx.h" -nt "$o" ]; then
+    if [ -n "$IAMX_REBUILD" ] || [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/iamx_common.h" -nt "$o" ] || [ "$HERE/jpeg_entropy.h" -nt "$o" ] || [ "$HERE/../../include/iamx.h" -nt "$o" ]; then
         EXTRA=""
         # the TRF helpers restate numpy expressions: separately rounded multiply and add
         [ "$(basename $f)" = "trf_vec.hip" ] && EXTRA="-ffp-contract=off"

@@ -17,6 +17,7 @@
 // cameras write) are handled; anything else (progressive, arithmetic, 12 bit, CMYK, 4:4:0) is
 // reported as IAMX_EUNSUPPORTED and the caller reads the file the host way.
 #include "iamx_common.h"
+#include "jpeg_entropy.h"
 
 #include <cstring>
 #include <vector>
@@ -328,14 +329,8 @@ inline int decode_symbol(BitReader &br, const HuffTable &T)
 
 inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
-}  // namespace
-
-extern "C" int iamx_jpeg_info(const uint8_t *data, int64_t len, int32_t *info /* [16] */)
+void fill_info(const Header &H, int32_t *info)
 {
-    IAMX_REQUIRE(data && info && len > 0, "null pointer");
-    Header H;
-    const int rc = parse(data, (size_t)len, H);
-    if (rc != IAMX_OK) return rc;
     info[0] = H.width; info[1] = H.height; info[2] = H.ncomp;
     info[3] = H.hmax; info[4] = H.vmax;
     int64_t off = 0;
@@ -348,6 +343,37 @@ extern "C" int iamx_jpeg_info(const uint8_t *data, int64_t len, int32_t *info /*
     info[11] = (int32_t)off;                                 // total blocks
     info[12] = H.restart;
     info[13] = info[14] = info[15] = 0;
+}
+
+void flat_table(const HuffTable &T, iamx_jpeg::Table &F)
+{
+    static_assert(HuffTable::LOOK == iamx_jpeg::LOOK, "one look-ahead width on both sides");
+    std::memcpy(F.fast, T.fast, sizeof F.fast);
+    for (int l = 0; l < 18; ++l) {
+        F.maxcode[l] = l >= 1 ? T.maxcode[l] : -1;
+        F.valoffset[l] = (l >= 1 && l <= 16) ? T.valoffset[l] : 0;
+    }
+    std::memcpy(F.huffval, T.huffval, sizeof F.huffval);
+}
+
+// a code of all ones (the standard reserves it, a table may still hold it): the padding in front
+// of a restart marker would then decode as a symbol
+bool has_all_ones_code(const HuffTable &T)
+{
+    for (int l = 1; l <= 16; ++l)
+        if (T.maxcode[l] == (1 << l) - 1) return true;
+    return false;
+}
+
+}  // namespace
+
+extern "C" int iamx_jpeg_info(const uint8_t *data, int64_t len, int32_t *info /* [16] */)
+{
+    IAMX_REQUIRE(data && info && len > 0, "null pointer");
+    Header H;
+    const int rc = parse(data, (size_t)len, H);
+    if (rc != IAMX_OK) return rc;
+    fill_info(H, info);
     return IAMX_OK;
 }
 
@@ -425,6 +451,85 @@ extern "C" int iamx_jpeg_decode_coefficients(const uint8_t *data, int64_t len, i
             if (H.restart) --to_restart;
         }
     }
+    return IAMX_OK;
+}
+
+// ---- host front of the device entropy decoder (csrc/jpeg_entropy.hip): markers and tables -------
+extern "C" int64_t iamx_jpeg_entropy_header_bytes(void) { return (int64_t)sizeof(iamx_jpeg::ScanHeader); }
+
+extern "C" int iamx_jpeg_entropy_prepare(const uint8_t *data, int64_t len, int32_t *info /* [16] */,
+                                         uint16_t *quant /* [3][64] */, void *header,
+                                         int64_t header_bytes)
+{
+    IAMX_REQUIRE(data && info && quant && header && len > 0, "null pointer");
+    IAMX_REQUIRE(header_bytes >= (int64_t)sizeof(iamx_jpeg::ScanHeader),
+                 "header buffer too small (iamx_jpeg_entropy_header_bytes)");
+    Header H;
+    const int rc = parse(data, (size_t)len, H);
+    if (rc != IAMX_OK) return rc;
+    // the entropy-coded data ends at the first marker that is not a restart marker of this file
+    // (FF followed by neither a stuffed 00 nor, with a restart interval, D0..D7): the host half
+    // feeds zeros from there on and never looks at what follows (EOI, then often previews, maker
+    // blobs, other images).  The lanes cover the bytes in front of it only.
+    {
+        const uint8_t *q = H.scan, *end = H.scan + H.scan_len;
+        while (q < end) {
+            q = static_cast<const uint8_t *>(std::memchr(q, 0xFF, (size_t)(end - q)));
+            if (!q) { q = end; break; }
+            const int nx = q + 1 < end ? q[1] : 0x100;
+            if (nx == 0 || (H.restart && nx >= 0xD0 && nx <= 0xD7)) q += 2; else break;
+        }
+        H.scan_len = (size_t)((q < end ? q : end) - H.scan);
+    }
+    // (a file that ends right behind SOS is the host half's: it writes the zero-bit blocks)
+    if (H.scan_len < 1) return iamx::fail(IAMX_EUNSUPPORTED, "jpeg: no entropy-coded data for the device decoder");
+    if (H.scan_len > iamx_jpeg::MAX_SCAN_BYTES || (uint64_t)len > 0xffffff00ull)
+        return iamx::fail(IAMX_EUNSUPPORTED, "jpeg: scan of %zu bytes is too long for the device decoder", H.scan_len);
+    fill_info(H, info);
+    for (int c = 0; c < H.ncomp; ++c)
+        for (int i = 0; i < 64; ++i) quant[c * 64 + i] = H.quant[H.comp[c].tq][i];
+    iamx_jpeg::ScanHeader F;
+    std::memset(&F, 0, sizeof F);
+    F.magic = iamx_jpeg::HEADER_MAGIC;
+    F.ncomp = H.ncomp;
+    F.restart = H.restart;
+    F.mcus_x = H.mcus_x;
+    F.mcus_y = H.mcus_y;
+    F.n_mcus = H.mcus_x * H.mcus_y;
+    F.file_len = (uint32_t)len;
+    F.scan_off = (uint32_t)(H.scan - data);
+    F.scan_len = (uint32_t)H.scan_len;
+    // sub-sequences of at least two average MCUs (jpeg_entropy.h)
+    const size_t n_mcus = (size_t)H.mcus_x * H.mcus_y;
+    size_t S = iamx_jpeg::MIN_SUBSEQ_BYTES;
+    while (S < iamx_jpeg::MAX_SUBSEQ_BYTES && S * n_mcus < 2 * H.scan_len) S *= 2;
+    F.subseq_bytes = (int32_t)S;
+    F.n_subseq = (int32_t)((H.scan_len + S - 1) / S);
+    F.max_passes = iamx_jpeg::MAX_PASSES;
+    int b = 0;
+    int64_t base = 0;
+    for (int c = 0; c < H.ncomp; ++c) {
+        const Component &C = H.comp[c];
+        F.comp_h[c] = C.h;
+        F.comp_v[c] = C.v;
+        F.comp_bw[c] = C.blocks_w;
+        F.comp_base[c] = (int32_t)base;
+        base += (int64_t)C.blocks_w * C.blocks_h;
+        for (int by = 0; by < C.v; ++by)
+            for (int bx = 0; bx < C.h; ++bx, ++b) {
+                F.mcu_comp[b] = c;
+                F.mcu_bx[b] = bx;
+                F.mcu_by[b] = by;
+            }
+        flat_table(H.dc[C.td], F.dc[c]);
+        flat_table(H.ac[C.ta], F.ac[c]);
+        if (H.restart && (has_all_ones_code(H.dc[C.td]) || has_all_ones_code(H.ac[C.ta])))
+            return iamx::fail(IAMX_EUNSUPPORTED, "jpeg: a Huffman code of all ones beside restart markers");
+    }
+    F.blocks_per_mcu = b;
+    F.total_blocks = (int32_t)base;
+    for (int k = 0; k < 64; ++k) F.natural[k] = kZigzag[k];
+    std::memcpy(header, &F, sizeof F);
     return IAMX_OK;
 }
 

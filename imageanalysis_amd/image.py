@@ -86,6 +86,8 @@ def make_keypoints(x, y, size, angle, response, octave, class_id=None):
 ASYNC_CACHE_WRITES = True      # cache files are written by background threads (cacheio.wait())
 USE_DESC_SIDECAR = True        # <image>.desc.u8.npy: raw uint8 descriptors beside the reference's .desc
 USE_DEVICE_JPEG = True         # split decoder: Huffman on the host, IDCT / upsampling / colour on the GPU
+DEVICE_JPEG_ENTROPY = False    # ... and the Huffman decode on the GPU too (kernels.jpeg_device_decode; the
+                               # host half for files it refuses).  Off: DESIGN.md section 8 item 6
 SIDECAR_MARGIN_S = 30.0        # a .desc / .feat newer than the sidecar by more than this is not ours
 DES_LIST_U8 = False            # True: image.des_list stays uint8 [N,128] (the same integer values; 6 MB
                                # instead of 25 MB per 50 k-keypoint frame -- 47 GB instead of 190 GB of host
@@ -402,8 +404,9 @@ def _prefetch_job(self):
         # handle are decoded whole
         if USE_DEVICE_JPEG:
             from . import kernels
-            jc = kernels.jpeg_host_decode(self.image_file)
-            if jc is not None:
+            # (DEVICE_JPEG_ENTROPY: the Huffman decode happens below, on the worker's stream)
+            jc = None if DEVICE_JPEG_ENTROPY else kernels.jpeg_host_decode(self.image_file)
+            if jc is not None or DEVICE_JPEG_ENTROPY:
                 # ... and the device half right behind it, on this worker's own stream: the 80 MB of
                 # coefficients go up and become pixels while the detector works on an earlier
                 # frame; the main thread receives a finished frame in HBM
@@ -413,6 +416,10 @@ def _prefetch_job(self):
                 dev = getattr(self, '_iamx_prefetch_device', None)
                 with torch.cuda.device(dev if dev is not None else torch.cuda.current_device()), \
                         torch.cuda.stream(_worker_stream()), kernels.polite_waits():
+                    if jc is None:
+                        jc = _device_entropy_decode(self.image_file)
+                        if jc is None:                       # not a file of the split decoder's kind
+                            return ('bgr', _decode_bgr(self.image_file, writable=False))
                     bgr = kernels.jpeg_reconstruct(jc)       # (waits for this stream only)
                     scale = getattr(self, '_iamx_prefetch_scale', None)
                     if scale is not None:
@@ -425,6 +432,14 @@ def _prefetch_job(self):
         return ('bgr', _decode_bgr(self.image_file, writable=False))
     except Exception:                     # noqa: BLE001  (detect_features repeats it and reports)
         return None
+
+
+def _device_entropy_decode(image_file):
+    """DEVICE_JPEG_ENTROPY: the file's coefficients decoded on the device (current stream); the
+    host half for a file the device refuses; None for a file neither half handles"""
+    from . import kernels
+    jc = kernels.jpeg_device_decode(image_file)
+    return jc if jc is not None else kernels.jpeg_host_decode(image_file)
 
 
 _worker_streams = __import__('threading').local()
@@ -516,7 +531,12 @@ def detect_features(self, scale, use_cache=True):
         bgr = None
         if USE_DEVICE_JPEG:
             from . import kernels
-            jc = pre[1] if pre is not None and pre[0] == 'coef' else kernels.jpeg_host_decode(self.image_file)
+            if pre is not None and pre[0] == 'coef':
+                jc = pre[1]
+            elif DEVICE_JPEG_ENTROPY:
+                jc = _device_entropy_decode(self.image_file)
+            else:
+                jc = kernels.jpeg_host_decode(self.image_file)
             if jc is not None:
                 bgr = kernels.jpeg_reconstruct(jc)
         if bgr is None:

@@ -1155,7 +1155,8 @@ def _sift_pinned(dev, n):
 class JpegCoefficients(object):
     """A JPEG after the host half of the decoder: info (int32 [16], iamx_jpeg_info), the
     quantised coefficients in a page-locked buffer (int16 [blocks, 64]) and the quantisation
-    tables (uint16 [3, 64]).  release() hands the buffer back to the pool."""
+    tables (uint16 [3, 64]).  release() hands the buffer back to the pool.  After
+    jpeg_device_decode the coefficients are a device tensor and there is no buffer to hand back."""
     __slots__ = ('info', 'coef', 'quant', '_slot')
 
     def release(self):
@@ -1225,8 +1226,11 @@ def jpeg_reconstruct(jc, release=True):
     w, h = int(info[0]), int(info[1])
     # (the 384-byte table first: a pageable copy waits for what is in front of it on the stream)
     d_quant = torch.from_numpy(jc.quant.astype(np.int16)).to(dev)        # (bit pattern; read as uint16)
-    d_coef = torch.empty(jc.coef.shape, dtype=torch.int16, device=dev)
-    d_coef.copy_(jc.coef, non_blocking=True)
+    if jc.coef.is_cuda:                                  # jpeg_device_decode: already in HBM
+        d_coef = jc.coef
+    else:
+        d_coef = torch.empty(jc.coef.shape, dtype=torch.int16, device=dev)
+        d_coef.copy_(jc.coef, non_blocking=True)
     need = int(L.iamx_jpeg_workspace_bytes(info.ctypes.data_as(ctypes.c_void_p)))
     ws = torch.empty(need, dtype=U8, device=dev)
     out = torch.empty((h, w, 3), dtype=U8, device=dev)
@@ -1238,9 +1242,89 @@ def jpeg_reconstruct(jc, release=True):
     return out
 
 
-def jpeg_decode(source):
-    """file name or bytes -> BGR uint8 [h, w, 3] on the device, or None for an unsupported file"""
-    jc = jpeg_host_decode(source)
+# what became of the files given to jpeg_device_decode: decoded on the device / not a file of the
+# split decoder's kind / refused because the sub-sequences did not synchronise inside the pass
+# bound / damaged (data ended early, marker out of place) -- the last three return None
+jpeg_device_stats = {'device': 0, 'unsupported': 0, 'refused': 0, 'damaged': 0, 'passes': 0}
+_jpeg_status = []                # page-locked landing places of the status words and the free ones' numbers
+
+
+def jpeg_device_decode(source):
+    """The host half's work done on the device (csrc/jpeg_entropy.hip): file name or bytes ->
+    JpegCoefficients whose coefficients are already in HBM (no page-locked slot; jpeg_reconstruct
+    takes it as it takes the host half's), or None for "go the host way": a file the split decoder
+    does not handle, one whose sub-sequences did not synchronise (flat images), a damaged one
+    (data that ends before the last block, a stray marker in the scan).
+    jpeg_device_stats says which.  Only the file's bytes cross PCIe.  Runs on the current stream
+    and waits for it once, to read the status word.  Raises IamxError for a broken file."""
+    import ctypes
+    dev = require_gpu()
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        data = bytes(source)
+    else:
+        with open(source, 'rb') as fp:
+            data = fp.read()
+    L = lib()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    n = len(data)
+    raw = np.zeros((n + 15) // 16 * 16, np.uint8)        # (the kernels load whole 16-byte pieces)
+    raw[:n] = np.frombuffer(data, np.uint8)
+    jc = JpegCoefficients()
+    jc.info = np.zeros(16, np.int32)
+    jc.quant = np.zeros((3, 64), np.uint16)
+    jc._slot = None
+    header = np.zeros(int(L.iamx_jpeg_entropy_header_bytes()), np.uint8)
+    rc = L.iamx_jpeg_entropy_prepare(p(raw), n, p(jc.info), p(jc.quant), p(header), len(header))
+    if rc == -4:
+        with _jpeg_lock:
+            jpeg_device_stats['unsupported'] += 1
+        return None
+    check(rc, 'iamx_jpeg_entropy_prepare')
+    blocks = int(jc.info[11])
+    need = int(L.iamx_jpeg_entropy_workspace_bytes(p(header)))
+    d_header = torch.from_numpy(header).to(dev)
+    d_raw = torch.from_numpy(raw).to(dev)
+    ws = torch.empty(need, dtype=U8, device=dev)
+    coef = torch.empty((blocks, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    check(L.iamx_jpeg_entropy_decode(_ptr(d_raw), raw.size, p(header), _ptr(d_header), _ptr(ws), need,
+                                     _ptr(coef), blocks, _ptr(status), stream_ptr()),
+          'iamx_jpeg_entropy_decode')
+    with _jpeg_lock:
+        if not _jpeg_status:                             # one page-locked allocation for every thread
+            _jpeg_status.append(torch.zeros((64, 4), dtype=torch.int32).pin_memory())
+            _jpeg_status.append(list(range(64)))
+        slot = _jpeg_status[1].pop() if _jpeg_status[1] else None
+    host = _jpeg_status[0][slot] if slot is not None else torch.zeros(4, dtype=torch.int32).pin_memory()
+    try:
+        host.copy_(status, non_blocking=True)
+        wait_stream()                                    # (this stream only; politely on a worker)
+        st, passes = int(host[0]), int(host[1])
+    finally:
+        if slot is not None:
+            with _jpeg_lock:
+                _jpeg_status[1].append(slot)
+    key = {1: 'device', 2: 'refused', 3: 'damaged'}.get(st)
+    if key is None:
+        raise _lib.IamxError('iamx_jpeg_entropy_decode left status %d' % st)
+    with _jpeg_lock:
+        jpeg_device_stats[key] += 1
+        jpeg_device_stats['passes'] = max(jpeg_device_stats['passes'], passes)
+    if st != 1:
+        return None
+    jc.coef = coef
+    return jc
+
+
+def jpeg_decode(source, entropy='host'):
+    """file name or bytes -> BGR uint8 [h, w, 3] on the device, or None for an unsupported file.
+    entropy='device': the Huffman decode runs on the device too (jpeg_device_decode), with the host
+    half as the fallback for the files it refuses."""
+    if entropy not in ('host', 'device'):
+        raise ValueError("entropy must be 'host' or 'device'")
+    jc = jpeg_device_decode(source) if entropy == 'device' else None
+    if jc is None:
+        jc = jpeg_host_decode(source)
     return None if jc is None else jpeg_reconstruct(jc)
 
 

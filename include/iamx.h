@@ -683,6 +683,56 @@ int64_t iamx_jpeg_workspace_bytes(const int32_t *info);
 int iamx_jpeg_reconstruct(const int16_t *coef, const uint16_t *quant, const int32_t *info,
                           void *workspace, int64_t workspace_bytes, uint8_t *bgr, void *stream);
 
+/* Entropy decoding on the device (csrc/jpeg_entropy.hip, method in csrc/jpeg_entropy.h): the
+ * Huffman-coded scan of the same class of file becomes the same coefficients, in device memory,
+ * without the host decode and without the upload of blocks x 128 bytes -- only the file goes up.
+ * The scan is decoded as sub-sequences of 128 bytes or more (two average MCUs), one lane each, that
+ * fall into step with the true decode (self-synchronisation); the result is exact or refused,
+ * never approximately right.
+ *   iamx_jpeg_entropy_prepare: HOST (markers and tables only, microseconds).  info [16] and quant
+ *     [3][64] as iamx_jpeg_info / iamx_jpeg_decode_coefficients fill them; header HOST
+ *     [header_bytes >= iamx_jpeg_entropy_header_bytes()]: tables in look-up form, geometry, offset
+ *     and length of the scan.  Errors are the host parser's (IAMX_EUNSUPPORTED / IAMX_EINVAL);
+ *     additionally IAMX_EUNSUPPORTED for a scan above 128 MiB, for a file without entropy-coded
+ *     data and for tables that hold a code of all ones in a file with restart markers.  The scan
+ *     the header describes ends at the first marker that is not a restart marker of the file, as
+ *     it does for the host half: bytes behind EOI (previews, maker blobs) are never decoded.
+ *   iamx_jpeg_entropy_workspace_bytes(header HOST): bytes of DEV workspace one call needs (0 for
+ *     a pointer that is not such a header).  The workspace belongs to one call at a time.
+ *   iamx_jpeg_entropy_decode: asynchronous on `stream`; no allocation, no synchronisation.
+ *     data DEV: the whole file, 16-byte aligned, data_bytes >= its length rounded up to 16 (the
+ *     padding is loaded, never used); header HOST and d_header DEV (a 16-byte aligned copy of
+ *     it); workspace DEV, 16-byte aligned; coef DEV [coef_blocks >= info[11]][64] int16, written
+ *     as iamx_jpeg_decode_coefficients writes it; status DEV int32 [4], valid once the stream
+ *     has passed the call: [0] one of IAMX_JPEG_*, [1] the synchronisation passes it took, [2] the
+ *     sub-sequences those passes decoded, all together (each reads its share of the scan once;
+ *     the write pass reads every one once more), [3] 0.
+ *     Bad arguments return IAMX_EINVAL before anything touches the device.  The call trusts what
+ *     it cannot check from the host: `header` must be what iamx_jpeg_entropy_prepare wrote,
+ *     unchanged (its geometry is validated, the six tables are not), and d_header a copy of it.
+ *     Every lane makes at most 8 x sub-sequence bytes + 64 decode steps, whatever frame size the
+ *     file claims.
+ * status[0]:
+ *   IAMX_JPEG_SYNCED      every sub-sequence start was verified, coef holds the host half's values
+ *   IAMX_JPEG_NOT_SYNCED  no fixed point inside the pass bound (flat images never synchronise, a flat
+ *                         stretch of more than 47 sub-sequences inside an image does not either): coef
+ *                         is zero, decode this file with iamx_jpeg_decode_coefficients
+ *   IAMX_JPEG_DAMAGED     verified, but the data ended before the last block (truncation, a stray
+ *                         marker such as FF FF Dn) or a restart marker stood inside an MCU: coef
+ *                         holds what was decoded and zeros behind it; the host half, which goes on
+ *                         with zero bits, is the reference for such a file */
+#define IAMX_JPEG_PENDING     0
+#define IAMX_JPEG_SYNCED      1
+#define IAMX_JPEG_NOT_SYNCED  2
+#define IAMX_JPEG_DAMAGED     3
+int64_t iamx_jpeg_entropy_header_bytes(void);
+int iamx_jpeg_entropy_prepare(const uint8_t *data, int64_t len, int32_t *info, uint16_t *quant,
+                              void *header, int64_t header_bytes);
+int64_t iamx_jpeg_entropy_workspace_bytes(const void *header);
+int iamx_jpeg_entropy_decode(const uint8_t *data, int64_t data_bytes, const void *header,
+                             const void *d_header, void *workspace, int64_t workspace_bytes,
+                             int16_t *coef, int64_t coef_blocks, int32_t *status, void *stream);
+
 /* The reference's descriptor cache file (gzip of np.save(float32 [N, 128]),
  * scripts/lib/image.py:205-217) written straight from the detector's uint8 descriptors: HOST,
  * no device involved, thread safe.  out receives ONE gzip member whose payload is `header` (the

@@ -4,7 +4,9 @@ the reference's cache files, (a) one image after the other with synchronous writ
 straight port of scripts/lib/image.py:287-350 does -- and (b) with imageanalysis_amd.cacheio:
 decode prefetched on worker threads, cache files written in the background.
 
-    python tools/detect_rate.py [n_images]"""
+    python tools/detect_rate.py [n_images] [--no-serial] [--device-entropy]
+
+--device-entropy sets image.DEVICE_JPEG_ENTROPY: the JPEG Huffman decode runs on the device too."""
 import os
 import sys
 import tempfile
@@ -42,6 +44,9 @@ def main():
         for f in futs:
             f.result()
     print('%d synthetic 5472x3648 JPEGs written in %.1f s' % (n, time.time() - t0))
+    if '--device-entropy' in sys.argv:
+        iimg.DEVICE_JPEG_ENTROPY = True
+        print('JPEG entropy decode on the device')
     if '--feat-zlib' in sys.argv:
         iimg.FEAT_GZIP_STRATEGY = 1                            # round 4's .feat members: zlib level 4, Z_FILTERED
         print('.feat through zlib (level %d, Z_FILTERED)' % iimg.FEAT_GZIP_LEVEL)
@@ -117,6 +122,9 @@ def main():
     tc = time.perf_counter() - t0
     pf.close()
     print('cache load: %.2f s = %.2f images/s' % (tc, n / tc))
+    if iimg.DEVICE_JPEG_ENTROPY:
+        from imageanalysis_amd import kernels
+        print('device entropy decode:', kernels.jpeg_device_stats)
 
 
 if __name__ == '__main__':
