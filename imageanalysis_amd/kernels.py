@@ -1351,3 +1351,29 @@ def equalize_resize(bgr, scale, equalize=True, clip_limit=3.0):
     if not isinstance(bgr, torch.Tensor):
         torch.cuda.current_stream().synchronize()      # (the upload's staging copy has been read)
     return out
+
+
+def resize_area(img, fx, fy):
+    """cv2.resize(img, (0, 0), fx=fx, fy=fy, interpolation=cv2.INTER_AREA) on the device
+    (csrc/image_area.hip; downscale only).  img uint8 [h,w,3] or [h,w] (numpy or device) ->
+    device tensor [round(h*fy), round(w*fx)(, 3)] uint8."""
+    dev = require_gpu()
+    src = _dev(img, U8)
+    if src.dim() == 2:
+        h, w, ch = src.shape[0], src.shape[1], 1
+    elif src.dim() == 3 and src.shape[2] in (1, 3):
+        h, w, ch = src.shape
+    else:
+        raise ValueError("expected a uint8 [h,w,3] or [h,w] image")
+    import ctypes
+    oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().iamx_image_area_dims(h, w, float(fx), float(fy), ctypes.byref(oh), ctypes.byref(ow)),
+          'iamx_image_area_dims')
+    # (argument errors -- an upscale, an empty result -- are reported by the call before it launches)
+    shape = (max(oh.value, 0), max(ow.value, 0)) + ((ch,) if src.dim() == 3 else ())
+    out = torch.empty(shape, dtype=U8, device=dev)
+    check(lib().iamx_image_resize_area(_ptr(src), h, w, ch, float(fx), float(fy), _ptr(out), stream_ptr()),
+          'iamx_image_resize_area')
+    if not isinstance(img, torch.Tensor):
+        torch.cuda.current_stream().synchronize()      # (the upload's staging copy has been read)
+    return out

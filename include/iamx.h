@@ -616,6 +616,24 @@ int iamx_image_equalize_resize(const uint8_t *bgr, int height, int width, int eq
                                int64_t workspace_bytes, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Area downscale -- replaces cv2.resize(src, (0,0), fx, fy, interpolation=cv2.INTER_AREA) of the
+ * texture step (scripts/lib/panda3d.py:38-41,69-72) for interleaved uint8 images.
+ *   src  DEV [height][width][channels] uint8, channels 1 or 3;
+ *   out  DEV [out_h][out_w][channels] uint8 with (out_h, out_w) = iamx_image_area_dims =
+ *        round-half-even(height*fy), round-half-even(width*fx).
+ * Per axis scale = 1.0/f (double).  OpenCV's published area algorithm for uint8 with a float work
+ * type: float32 tap weights, x taps summed in order from 0 into a row buffer, rows combined in
+ * order, multiply and add rounded separately, result rounded half to even; the integer branch
+ * (block sum * float32(1/area), (sum + 2) >> 2 for 2x2, (float)sum / count over an edge) when
+ * both scales are integers within DBL_EPSILON.  tests/area_restatement.py states it in numpy.
+ * Downscale only: 1/fx < 1 or 1/fy < 1 is IAMX_EINVAL, and so is a scale above 4096.  One launch
+ * on `stream`, no workspace, no host synchronisation.
+ * ------------------------------------------------------------------------------------ */
+int iamx_image_area_dims(int height, int width, double fx, double fy, int *out_h, int *out_w);
+int iamx_image_resize_area(const uint8_t *src, int height, int width, int channels, double fx,
+                           double fy, uint8_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * K1: SIFT detect + describe -- replaces cv2.SIFT_create().detectAndCompute(scaled, None)
  *   scripts/lib/image.py:235-237,324 (OpenCV defaults: 3 layers/octave, sigma 1.6, image
  *   doubled, contrastThreshold 0.04, edgeThreshold 10, no feature cap).
