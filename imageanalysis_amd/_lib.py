@@ -110,6 +110,11 @@ SIGNATURES = {
     'iamx_image_area_dims': (c_int, [c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     'iamx_image_resize_area': (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
                                        c_void_p]),
+    'iamx_surface_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'iamx_surface_interp': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'iamx_surface_grid': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4
+                          + [c_int, c_void_p, c_int, c_int, c_int, c_double, c_int] + [c_void_p] * 5),
     'iamx_jpeg_info': (c_int, [c_void_p, c_int64, c_void_p]),
     'iamx_jpeg_decode_coefficients': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'iamx_jpeg_workspace_bytes': (c_int64, [c_void_p]),

@@ -1377,3 +1377,120 @@ def resize_area(img, fx, fy):
     if not isinstance(img, torch.Tensor):
         torch.cuda.current_stream().synchronize()      # (the upload's staging copy has been read)
     return out
+
+
+# --------------------------------------------------------------------------------------
+# Step 5 surface grids (csrc/surface_grid.hip)
+# --------------------------------------------------------------------------------------
+SURFACE_SKY, SURFACE_HIGH_ANGLE, SURFACE_FALLBACK = 1, 2, 4
+SURFACE_RECORD_BYTES = 128
+SURFACE_MAX_SEED_GRID = 4096
+
+
+def surface_seed_grid(tri, G):
+    """The G x G table of start triangles over the points' bounding box (host): find_simplex of the
+    cell centres; a centre outside the hull takes vertex_to_simplex of the nearest point.
+    -> (seed int32 [G, G] (row = y), bbox float64 [xmin, ymin, xmax, ymax])"""
+    from scipy.spatial import cKDTree
+    G = int(G)
+    if not 1 <= G <= SURFACE_MAX_SEED_GRID:
+        raise ValueError("seed grid of %d cells a side" % G)
+    pts = np.asarray(tri.points, np.float64)
+    lo, hi = pts.min(axis=0), pts.max(axis=0)
+    cx = lo[0] + (np.arange(G) + 0.5) * ((hi[0] - lo[0]) / G)
+    cy = lo[1] + (np.arange(G) + 0.5) * ((hi[1] - lo[1]) / G)
+    centres = np.stack(np.meshgrid(cx, cy), axis=-1).reshape(-1, 2)
+    seed = np.asarray(tri.find_simplex(centres), np.int32)
+    out = np.nonzero(seed < 0)[0]
+    if len(out):
+        _d, near = cKDTree(pts).query(centres[out])
+        seed[out] = np.asarray(tri.vertex_to_simplex, np.int32)[near]
+    return seed.reshape(G, G), np.array([lo[0], lo[1], hi[0], hi[1]], np.float64)
+
+
+class Surface(object):
+    """A scipy.spatial.Delaunay triangulation and its vertex values on the device: 128-byte records
+    (iamx_surface_pack), the values, the seed grid.  upload_s is the host's time in the uploads."""
+
+    def __init__(self, tri, values, seed_g=None):
+        import time
+        dev = require_gpu()
+        simplices = np.ascontiguousarray(tri.simplices, np.int32)
+        self.T, self.P = int(simplices.shape[0]), int(np.asarray(tri.points).shape[0])
+        values = np.ascontiguousarray(values, np.float64).reshape(-1)
+        if simplices.shape[1] != 3 or values.shape[0] != self.P:
+            raise ValueError("expected a 2-d triangulation and one value per point")
+        if seed_g is None:
+            seed_g = min(1024, max(1, int(np.ceil(np.sqrt(self.T / 4.0)))))
+        seed, bbox = surface_seed_grid(tri, seed_g)
+        self.G, self.bbox = int(seed_g), bbox
+        t0 = time.perf_counter()
+        simp = _dev(simplices, I32)
+        nbr = _dev(np.ascontiguousarray(tri.neighbors, np.int32), I32)
+        trans = _dev(np.ascontiguousarray(tri.transform, np.float64), F64)
+        self.values = _dev(values, F64)
+        self.seed = _dev(seed, I32)
+        self.records = torch.empty(self.T * SURFACE_RECORD_BYTES, dtype=U8, device=dev)
+        check(lib().iamx_surface_pack(_ptr(simp), _ptr(nbr), _ptr(trans), self.T, _ptr(self.records),
+                                      stream_ptr()), 'iamx_surface_pack')
+        torch.cuda.current_stream().synchronize()         # (the scipy-shaped arrays are dropped here)
+        self.upload_s = time.perf_counter() - t0
+
+    def _bbox_ptr(self):
+        return self.bbox.ctypes.data_as(_lib.c_void_p)
+
+
+def surface_interp(surface, xy, max_steps=0, with_steps=False):
+    """LinearNDInterpolator(tri, values)(xy) by a walk per query (csrc/surface_grid.hip).
+    xy [N, 2] (numpy or device) -> z float64 [N] (NaN outside the hull), flags uint8 [N] (1: the
+    query was NOT answered -- step bound, degenerate simplex, NaN query -- and scipy has to be asked)
+    and, with_steps, the records each walk read (int32 [N]).  Device tensors."""
+    dev = require_gpu()
+    q = _dev(xy, F64).reshape(-1, 2)
+    n = int(q.shape[0])
+    out = torch.empty(n, dtype=F64, device=dev)
+    flags = torch.empty(n, dtype=U8, device=dev)
+    steps = torch.empty(n, dtype=I32, device=dev) if with_steps else None
+    check(lib().iamx_surface_interp(_ptr(surface.records), surface.T, _ptr(surface.values), surface.P,
+                                    _ptr(surface.seed), surface.G, surface._bbox_ptr(), _ptr(q), n,
+                                    int(max_steps), _ptr(out), _ptr(flags), _ptr(steps), stream_ptr()),
+          'iamx_surface_interp')
+    if not isinstance(xy, torch.Tensor):
+        torch.cuda.current_stream().synchronize()          # (the upload's staging copy has been read)
+    return (out, flags, steps) if with_steps else (out, flags)
+
+
+def surface_grid(surface, M, ned, avg_ground, uv, no_extrapolate=False, ground_m=None, max_steps=0,
+                 with_steps=False):
+    """projectVectors + intersect2d of render_panda3d.build_map for a batch of images, one thread per
+    (image, grid vertex).  M [I, 3, 3] = body2ned . cam2body . IK, ned [I, 3], avg_ground [I] = -z_avg,
+    uv [n, 2] the shared pixel grid; surface a Surface, or None with ground_m (the ground-plane mode,
+    intersectVectorsWithGroundPlane).  -> pts float64 [I, n, 3] NED, rounds int32 [I, n], flags uint8
+    [I, n] (SURFACE_SKY | SURFACE_HIGH_ANGLE | SURFACE_FALLBACK) and, with_steps, records read per ray."""
+    dev = require_gpu()
+    ground = ground_m is not None
+    if surface is None and not ground:
+        raise ValueError("a Surface, or ground_m for the ground-plane mode")
+    Md = _dev(M, F64).reshape(-1, 9)
+    nd = _dev(ned, F64).reshape(-1, 3)
+    I = int(Md.shape[0])
+    ag = _dev(avg_ground if avg_ground is not None else np.zeros(I), F64).reshape(-1)
+    uvd = _dev(uv, F64).reshape(-1, 2)
+    n = int(uvd.shape[0])
+    if nd.shape[0] != I or ag.shape[0] != I:
+        raise ValueError("M, ned and avg_ground must have one entry per image")
+    pts = torch.empty((I, n, 3), dtype=F64, device=dev)
+    rounds = torch.empty((I, n), dtype=I32, device=dev)
+    flags = torch.empty((I, n), dtype=U8, device=dev)
+    steps = torch.empty((I, n), dtype=I32, device=dev) if with_steps else None
+    s = None if ground else surface
+    check(lib().iamx_surface_grid(_ptr(s.records) if s else None, s.T if s else 0,
+                                  _ptr(s.values) if s else None, s.P if s else 0,
+                                  _ptr(s.seed) if s else None, s.G if s else 0,
+                                  s._bbox_ptr() if s else None, _ptr(Md), _ptr(nd), _ptr(ag), I, _ptr(uvd), n,
+                                  1 if no_extrapolate else 0, 1 if ground else 0,
+                                  float(ground_m) if ground else 0.0, int(max_steps), _ptr(pts),
+                                  _ptr(rounds), _ptr(flags), _ptr(steps), stream_ptr()),
+          'iamx_surface_grid')
+    torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
+    return (pts, rounds, flags, steps) if with_steps else (pts, rounds, flags)

@@ -1,11 +1,14 @@
-"""MI355X-native stand-in for the texture part of the reference's scripts/lib/panda3d.py:
+"""MI355X-native stand-in for the reference's scripts/lib/panda3d.py:
 
     make_textures_opencv(src_dir, analysis_dir, image_list, resolution=512)     panda3d.py:24-74
+    generate_from_grid(proj, group, ref_image, src_dir, analysis_dir, resolution)  panda3d.py:77-144
 
-the first and heaviest thing Step 5 ("Create the map") does: every full-resolution JPEG of the
-project is decoded, shrunk to resolution x resolution with cv2.resize(INTER_AREA) and written as
-<analysis_dir>/models/<image.name>.JPG, plus a 64 x 64 models/dummy.jpg from the first image.  The
-ray / Delaunay surface grids and the .egg writer of generate_from_grid are not here.
+make_textures_opencv is the first and heaviest thing Step 5 ("Create the map") does: every
+full-resolution JPEG of the project is decoded, shrunk to resolution x resolution with
+cv2.resize(INTER_AREA) and written as <analysis_dir>/models/<image.name>.JPG, plus a 64 x 64
+models/dummy.jpg from the first image.  generate_from_grid calls it and then writes
+models/<root>.egg for every image of the group from image.grid_list / image.distorted_uv (the ray /
+surface grids of render_panda3d.build_map), byte for byte the reference's files.
 
 Here the decode is the split JPEG decoder (bit-identical to libjpeg-turbo, kernels.jpeg_decode),
 the downscale is csrc/image_area.hip (kernels.resize_area) and only the 0.8 MB texture comes back
@@ -25,6 +28,7 @@ import io
 import os
 import threading
 import time
+from math import sqrt
 
 import numpy as np
 
@@ -249,6 +253,75 @@ def make_textures_opencv(src_dir, analysis_dir, image_list, resolution=512):
         dt = time.perf_counter() - t0
         with _stats_lock:
             texture_stats['frames_per_s'] = n_made / dt if dt > 0 else 0.0
+
+
+_EGG_HEAD = "<CoordinateSystem> { Z-Up }\n\n<Texture> tex { \"dummy.jpg\" }\n\n<VertexPool> surface {\n"
+
+
+def _uv_lines(distorted_uv, width, height):
+    return ["    <UV> { %.5f %.5f }\n  }\n" % (uv[0]/float(width), 1.0-uv[1]/float(height))
+            for uv in distorted_uv]
+
+
+def egg_text(grid_list, uv_lines):
+    """the text of one .egg file (panda3d.py:92-137) and its polygon count; uv_lines = _uv_lines()"""
+    steps = int(sqrt(len(grid_list))) - 1
+    side = steps + 1
+    out = [_EGG_HEAD]
+    nan = set()
+    for n in range(1, side * side + 1):
+        v = grid_list[n-1]
+        if v[0] != v[0] or v[1] != v[1] or v[2] != v[2]:
+            v = [0.0, 0.0, 0.0]
+            nan.add(n)
+        out.append("  <Vertex> %d {\n    %.2f %.2f %.2f\n" % (n, v[0], v[1], v[2]))
+        out.append(uv_lines[n-1])
+    out.append("}\n\n<Group> surface {\n")
+    count = 0
+    for j in range(steps):
+        for i in range(steps):
+            c = (j * side) + i + 1
+            d = ((j+1) * side) + i + 1
+            if nan and (c in nan or d in nan or (c+1) in nan or (d+1) in nan):
+                continue
+            out.append("  <Polygon> {\n   <TRef> { tex }\n   <Normal> { 0 0 1 }\n"
+                       "   <VertexRef> { %d %d %d %d <Ref> { surface } }\n  }\n" % (d, d+1, c+1, c))
+            count += 1
+    out.append("}\n")
+    return "".join(out), count
+
+
+def generate_from_grid(proj, group, ref_image=False, src_dir=".", analysis_dir=".", resolution=512):
+    """The reference's generate_from_grid: the textures (if needed), then models/<root>.egg per image
+    of the group -- "dummy.jpg" as the texture name, %.2f / %.5f numbers, NaN vertices written as
+    zeros and the polygons that touch one left out, a file without a polygon removed (with the
+    reference's warning), an image with an empty grid_list skipped.  Each file's text is built in
+    memory and written once (the reference: ~500 f.write calls per file); one host thread writes
+    1 000 files in 0.07 s (profiles/r11_step5_grid_rate.txt: 10 000 files in under a second), so
+    there are no worker threads."""
+    make_textures_opencv(src_dir, analysis_dir, proj.image_list, resolution)
+    camera = _deps.camera()
+    uv_cache = {}                                         # build_map gives a group ONE distorted_uv list
+    for name in group:
+        image = proj.findImageByName(name)
+        if len(image.grid_list) == 0:
+            continue
+        root, ext = os.path.splitext(image.name)
+        name = os.path.join(analysis_dir, "models", root + ".egg")
+        _log("EGG file name:", name)
+        width, height = camera.get_image_params()
+        key = (id(image.distorted_uv), width, height)
+        if key not in uv_cache:
+            uv_cache[key] = (image.distorted_uv, _uv_lines(image.distorted_uv, width, height))
+        text, count = egg_text(image.grid_list, uv_cache[key][1])
+        if count == 0:
+            # no polygon fully on the surface: the reference writes the file, warns and deletes it
+            _log("Warning: no polygons fully on surface, removing:", name)
+            if os.path.exists(name):
+                os.remove(name)
+            continue
+        with open(name, "w") as f:
+            f.write(text)
 
 
 def install(ref_panda3d_module):

@@ -338,3 +338,33 @@ def make_rendered_survey(project_dir, rows, cols, w=1368, h=912, focal=916.7, al
     if on_frames is not None and len(names) > handed:
         on_frames(names, truth, logged, K, handed, len(names))
     return names, truth, logged, K
+
+
+def make_step5_scene(rows=100, cols=100, n_points=300000, spacing=20.0, agl=100.0, seed=7,
+                     relief=6.0, roughness=0.3, jitter_deg=2.0):
+    """The grid stage of Step 5 at BASELINE config 4's shape: nadir cameras on a lawn-mower grid with a
+    few degrees of attitude jitter over `n_points` surface points (rolling relief of +-`relief` m plus
+    `roughness` m of noise; NED, so elevation = -z).
+    Returns dict(points [P,2] (east, north), values [P] (ned z), M [C,3,3] = body2ned . cam2body . IK,
+    ned [C,3], avg_ground [C], K, width, height)."""
+    rng = np.random.default_rng(seed)
+    C = rows * cols
+    r, c = np.divmod(np.arange(C), cols)
+    c = np.where(r % 2 == 1, cols - 1 - c, c)
+    ned = np.stack([r * spacing, c * spacing, np.full(C, -agl)], 1) + rng.normal(0, 0.3, (C, 3))
+    yaw = np.where(r % 2 == 0, 0.0, 180.0) + rng.normal(0, jitter_deg, C)
+    pitch = -90.0 + rng.normal(0, jitter_deg, C)
+    roll = rng.normal(0, jitter_deg, C)
+    d2r = np.pi / 180
+    north = rng.uniform(-40, (rows - 1) * spacing + 40, n_points)
+    east = rng.uniform(-60, (cols - 1) * spacing + 60, n_points)
+    z = relief * np.sin(north / 130.0) * np.cos(east / 170.0) + 0.4 * relief * np.sin((north + east) / 37.0) \
+        + rng.normal(0, roughness, n_points)
+    cam2body = np.linalg.inv(BODY2CAM)
+    IK = np.linalg.inv(K_FC6310S)
+    M = np.empty((C, 3, 3))
+    for i in range(C):
+        q = tf.quaternion_from_euler(yaw[i] * d2r, pitch[i] * d2r, roll[i] * d2r, 'rzyx')
+        M[i] = tf.quaternion_matrix(q)[:3, :3].dot(cam2body).dot(IK)
+    return dict(points=np.stack([east, north], 1), values=z, M=M, ned=ned, avg_ground=np.zeros(C),
+                K=K_FC6310S, width=W_PX, height=H_PX)

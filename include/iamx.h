@@ -634,6 +634,57 @@ int iamx_image_resize_area(const uint8_t *src, int height, int width, int channe
                            double fy, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Step 5 surface grids -- replace the per-point scipy.interpolate.LinearNDInterpolator calls of
+ * scripts/lib/render_panda3d.py:25-78,148-225 (intersect2d / intersect_vectors, with
+ * project.projectVectors and project.intersectVectorsWithGroundPlane).  The Delaunay
+ * triangulation itself stays scipy.spatial.Delaunay on the host; all pointers are DEV.
+ *
+ * iamx_surface_pack: simplices [T][3] i32, neighbors [T][3] i32 (-1 at the hull), transform
+ *   [T][3][2] f64 as scipy gives them -> records [T] of IAMX_SURFACE_RECORD_BYTES (128-byte
+ *   aligned): one step of a walk touches one record.
+ *
+ * The walk of a query (x, y): in triangle s, c0, c1 = rows 0, 1 of transform[s] applied to
+ *   (x, y) - transform[s][2], c2 = 1 - (c0 + c1); smallest c >= -100 DBL_EPSILON: inside, value
+ *   c0 z[v0] + c1 z[v1] + c2 z[v2] summed in that order; else step to the neighbour opposite the
+ *   smallest c, -1 = outside the hull = NaN.  A walk of more than max_steps records (0: T + 16), a
+ *   NaN transform or a NaN query is NOT answered: its flag is set and the caller asks scipy.
+ *   seed [G][G] i32: start triangle of the cell (row = y) of bbox = {xmin, ymin, xmax, ymax}
+ *   (HOST pointer, 4 doubles), queries outside the box start from the nearest cell.
+ *
+ * iamx_surface_interp: xy [N][2] -> out [N] f64, flags [N] u8 (1 = not answered), steps [N] i32
+ *   (records read; may be null).
+ *
+ * iamx_surface_grid: one thread per (image, grid vertex).  M [I][9] = body2ned . cam2body . IK,
+ *   ned [I][3], avg_ground [I] = -z_avg, uv [n][2] the shared pixel grid.  Ray = unit(M [u, v, 1]),
+ *   then intersect2d as written: v[2] <= 0 -> the camera position (IAMX_SURFACE_SKY); first look-up
+ *   at the camera position from the seed grid, NaN there -> avg_ground unless no_extrapolate; up to
+ *   25 rounds while |p[2] - surface| > 0.01, p recomputed from ned, a NaN inside the loop keeps the
+ *   previous surface, every look-up starting where the previous one ended; atan2(-dz, dist) < 30
+ *   degrees -> three NaNs (IAMX_SURFACE_HIGH_ANGLE).  A ray with a look-up that was not answered
+ *   carries IAMX_SURFACE_FALLBACK and its point is not valid.  ground_mode != 0: no triangulation
+ *   (records .. bbox may be null), intersectVectorsWithGroundPlane(ned, ground_m, rays).
+ *   pts [I][n][3] f64 NED, rounds [I][n] i32, flags [I][n] u8, steps [I][n] i32 or null.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_SURFACE_RECORD_BYTES 128
+#define IAMX_SURFACE_MAX_TRIANGLES (1 << 24)
+#define IAMX_SURFACE_MAX_SEED_GRID 4096
+#define IAMX_SURFACE_SKY 1
+#define IAMX_SURFACE_HIGH_ANGLE 2
+#define IAMX_SURFACE_FALLBACK 4
+int iamx_surface_pack(const int *simplices, const int *neighbors, const double *transform,
+                      int num_triangles, void *records, void *stream);
+int iamx_surface_interp(const void *records, int num_triangles, const double *values, int num_points,
+                        const int *seed, int seed_g, const double *bbox, const double *xy,
+                        int64_t num_queries, int max_steps, double *out, uint8_t *flags, int *steps,
+                        void *stream);
+int iamx_surface_grid(const void *records, int num_triangles, const double *values, int num_points,
+                      const int *seed, int seed_g, const double *bbox, const double *M,
+                      const double *ned, const double *avg_ground, int num_images, const double *uv,
+                      int num_vertices, int no_extrapolate, int ground_mode, double ground_m,
+                      int max_steps, double *pts, int *rounds, uint8_t *flags, int *steps,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------
  * K1: SIFT detect + describe -- replaces cv2.SIFT_create().detectAndCompute(scaled, None)
  *   scripts/lib/image.py:235-237,324 (OpenCV defaults: 3 layers/octave, sigma 1.6, image
  *   doubled, contrastThreshold 0.04, edgeThreshold 10, no feature cap).
