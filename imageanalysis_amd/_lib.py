@@ -110,6 +110,17 @@ SIGNATURES = {
     'iamx_image_area_dims': (c_int, [c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     'iamx_image_resize_area': (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
                                        c_void_p]),
+    'iamx_colour_histogram': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    'iamx_colour_accumulate_max_frames': (c_int, []),
+    'iamx_colour_accumulate': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    'iamx_colour_mean': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    'iamx_colour_moments_workspace_doubles': (c_int, []),
+    'iamx_colour_moments': (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    'iamx_colour_fit_mask': (c_int, [c_int, c_int, c_double, c_double, c_void_p, ctypes.c_uint64,
+                                     c_void_p, c_void_p]),
+    'iamx_colour_mask_finish': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'iamx_colour_lut': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'iamx_surface_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     'iamx_surface_interp': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                     c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1494,3 +1494,130 @@ def surface_grid(surface, M, ned, avg_ground, uv, no_extrapolate=False, ground_m
           'iamx_surface_grid')
     torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
     return (pts, rounds, flags, steps) if with_steps else (pts, rounds, flags)
+
+
+# --------------------------------------------------------------------------------------
+# the explorer's colour tables (csrc/image_colour.hip)
+# --------------------------------------------------------------------------------------
+def _frame3(img):
+    """numpy / tensor -> contiguous device uint8 [h, w, 3]"""
+    t = _dev(img, U8)
+    if t.dim() != 3 or t.shape[2] != 3 or t.numel() == 0:
+        raise ValueError("expected a uint8 [h,w,3] image")
+    return t
+
+
+def colour_histogram(img, hist=None):
+    """The three channel histograms of a uint8 [h,w,3] image (numpy or device): int32 device tensor
+    [3, 256] holding unsigned 32-bit counts.  With `hist` the counts are ADDED onto it (zero it once)."""
+    dev = require_gpu()
+    src = _frame3(img)
+    if hist is None:
+        hist = torch.zeros((3, 256), dtype=I32, device=dev)
+    elif hist.dtype != I32 or tuple(hist.shape) != (3, 256) or not hist.is_cuda or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int32 device tensor [3, 256]")
+    check(lib().iamx_colour_histogram(_ptr(src), src.shape[0] * src.shape[1], _ptr(hist), stream_ptr()),
+          'iamx_colour_histogram')
+    if not isinstance(img, torch.Tensor):
+        torch.cuda.current_stream().synchronize()      # (the upload's staging copy has been read)
+    return hist
+
+
+def colour_accumulate(total, frames):
+    """total (int32 device tensor of the frames' shape, unsigned 32-bit sums) += every frame of
+    `frames` (device uint8 tensors of one shape), 8 frames per launch: the sum is read and written
+    once per launch."""
+    import ctypes
+    require_gpu()
+    frames = list(frames)
+    for f in frames:
+        if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == U8 and f.is_contiguous()
+                and f.shape == total.shape):
+            raise ValueError("frames must be contiguous uint8 device tensors of the sum's shape")
+    if total.dtype != I32 or not total.is_cuda or not total.is_contiguous():
+        raise ValueError("the sum must be a contiguous int32 device tensor")
+    L = lib()
+    per = int(L.iamx_colour_accumulate_max_frames())
+    for k in range(0, len(frames), per):
+        part = frames[k:k + per]
+        ptrs = (ctypes.c_void_p * len(part))(*[f.data_ptr() for f in part])
+        check(L.iamx_colour_accumulate(ptrs, len(part), total.numel(), _ptr(total), stream_ptr()),
+              'iamx_colour_accumulate')
+    return total
+
+
+def colour_mean(total, count):
+    """uint8(trunc(float32(total) / float32(count))): the reference's (sum / count).astype('uint8');
+    count above 65 793 is refused (255 * count < 2^24: the reference's float32 sum is exact)"""
+    dev = require_gpu()
+    count = int(count)
+    if total.dtype != I32 or not total.is_cuda or not total.is_contiguous():
+        raise ValueError("the sum must be a contiguous int32 device tensor")
+    out = torch.empty(total.shape, dtype=U8, device=dev)
+    check(lib().iamx_colour_mean(_ptr(total), total.numel(), count, _ptr(out), stream_ptr()), 'iamx_colour_mean')
+    return out
+
+
+def colour_moments(img, cu, cv):
+    """The sums of the radial fit v ~ a' s^4 + b' s^2 + c about (cu, cv), s = r / R: (out, R) with
+    out a float64 device tensor [3, 8] = per channel sum s^8, s^6, s^4, s^2, n, s^4 v, s^2 v, v and
+    R the image's largest (float32-rounded) radius.  Reproducible bit for bit."""
+    import ctypes
+    dev = require_gpu()
+    src = _frame3(img)
+    L = lib()
+    ws = torch.empty(int(L.iamx_colour_moments_workspace_doubles()), dtype=F64, device=dev)
+    out = torch.empty((3, 8), dtype=F64, device=dev)
+    R = ctypes.c_double(0.0)
+    check(L.iamx_colour_moments(_ptr(src), src.shape[0], src.shape[1], float(cu), float(cv), ctypes.byref(R),
+                                _ptr(ws), _ptr(out), stream_ptr()), 'iamx_colour_moments')
+    torch.cuda.current_stream().synchronize()          # (the workspace, and an upload's staging copy)
+    return out, R.value
+
+
+def colour_fit_mask(height, width, cu, cv, coef, seed=0):
+    """dither(a r^4 + b r^2 + c) per channel, coef [3][3] = (a, b, c) per channel -> device uint8
+    [height, width, 3].  Raises IamxError when a polynomial leaves [0, 255] inside the image."""
+    dev = require_gpu()
+    coef = np.ascontiguousarray(coef, np.float64).reshape(9)
+    out = torch.empty((int(height), int(width), 3), dtype=U8, device=dev)
+    check(lib().iamx_colour_fit_mask(int(height), int(width), float(cu), float(cv),
+                                     coef.ctypes.data_as(_lib.c_void_p), int(seed) & (2 ** 64 - 1), _ptr(out),
+                                     stream_ptr()), 'iamx_colour_fit_mask')
+    return out
+
+
+def colour_mask_finish(img):
+    """per channel m = 255 - v, m -= min(m) -> device uint8 [h, w, 3]"""
+    dev = require_gpu()
+    src = _frame3(img)
+    scratch = torch.empty(3, dtype=I32, device=dev)
+    out = torch.empty(src.shape, dtype=U8, device=dev)
+    check(lib().iamx_colour_mask_finish(_ptr(src), src.shape[0] * src.shape[1], _ptr(scratch), _ptr(out),
+                                        stream_ptr()), 'iamx_colour_mask_finish')
+    torch.cuda.current_stream().synchronize()          # (the scratch words, and an upload's staging copy)
+    return out
+
+
+def colour_lut(img, lut, mask=None):
+    """out[y][x][c] = lut[c][img[y][x][c]], plus mask (uint8, img's shape) with saturation at 255.
+    A numpy image is uploaded and a numpy array comes back; a device tensor gives a device tensor
+    (like resize_area's input)."""
+    dev = require_gpu()
+    src = _frame3(img)
+    table = _dev(np.asarray(lut) if not isinstance(lut, torch.Tensor) else lut, U8)
+    if tuple(table.shape) != (3, 256):
+        raise ValueError("lut must be uint8 [3, 256]")
+    m = None
+    if mask is not None:
+        m = _frame3(mask)
+        if m.shape != src.shape:
+            raise ValueError("the mask must have the image's shape")
+    out = torch.empty(src.shape, dtype=U8, device=dev)
+    check(lib().iamx_colour_lut(_ptr(src), src.shape[0] * src.shape[1], _ptr(table), _ptr(m), _ptr(out),
+                                stream_ptr()), 'iamx_colour_lut')
+    if isinstance(img, torch.Tensor):
+        if not (isinstance(lut, torch.Tensor) and (mask is None or isinstance(mask, torch.Tensor))):
+            torch.cuda.current_stream().synchronize()  # (the uploads' staging copies have been read)
+        return out
+    return out.cpu().numpy()

@@ -634,6 +634,61 @@ int iamx_image_resize_area(const uint8_t *src, int height, int width, int channe
                            double fy, uint8_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Colour tables of the explorer -- replace the host loops of scripts/lib/histogram.py
+ * (get_histogram_rgb, match_neighbors) and scripts/99-vignette.py (the survey's mean frame, the
+ * radial fit's sums, the fitted mask, the mask's finish).  Frames are DEV [h][w][3] uint8,
+ * interleaved, in the decoder's channel order; n_pixels = h*w, n_values = 3*h*w.  Every call
+ * enqueues on `stream` and does not synchronise the host.  16-byte aligned images are read 48 bytes
+ * (16 pixels) per lane and step; unaligned ones byte by byte, with the same results.
+ *
+ * iamx_colour_histogram: hist DEV uint32 [3][256] += the counts of img's three channels (the
+ *   caller zeroes it once).  Integer counters throughout: LDS copies per workgroup, one integer
+ *   global atomic per non-empty bin and workgroup.  n_pixels < 2^32.
+ *
+ * iamx_colour_accumulate: sum DEV uint32 [n_values] += frames[0] + ... + frames[n_frames-1];
+ *   frames is a HOST list of 1 .. iamx_colour_accumulate_max_frames() (8) DEV pointers: the sum is
+ *   read and written once per launch, whatever the number of frames.
+ *
+ * iamx_colour_mean: avg[i] = uint8(trunc(float32(sum[i]) / float32(count))), the division rounded
+ *   once: numpy's (sum / count).astype('uint8') on the float32 sum of 99-vignette.py:63,69, which
+ *   is exact while 255 * count < 2^24.  count above 65 793 is IAMX_EINVAL.
+ *
+ * iamx_colour_moments: with r = double(float(sqrt(dx*dx + dy*dy))) about (cu, cv) (the reference
+ *   keeps its radii in a float32 table), *radius (HOST) = R = the largest r of the image (a corner)
+ *   and s = r / R, out DEV double [3][8] = per channel { sum s^8, s^6, s^4, s^2, n, s^4 v, s^2 v, v }:
+ *   the normal equations of v ~ a' s^4 + b' s^2 + c (a = a'/R^4, b = b'/R^2).  partials DEV double
+ *   [iamx_colour_moments_workspace_doubles()].  A fixed grid, a fixed tree per workgroup and the
+ *   partials added in index order: two runs give the same bits.  No floating-point atomics.
+ *
+ * iamx_colour_fit_mask: out[y][x][ch] = dither(a r^4 + b r^2 + c) with r = sqrt(dx*dx + dy*dy) in
+ *   doubles and the polynomial evaluated as a*r*r*r*r + b*r*r + c; coef HOST double [3][3] = per
+ *   channel a, b, c.  dither(x) = trunc(x), plus one with probability x - trunc(x); the uniform number
+ *   is a hash of (seed, 3*(y*width + x) + ch): no state, the same seed gives the same mask.  A
+ *   polynomial that leaves [0, 255] inside the image is IAMX_EINVAL (checked on the host at the
+ *   nearest and the farthest pixel and at the vertex), as the reference's uint8 assignment raises.
+ *
+ * iamx_colour_mask_finish: per channel m = 255 - v, m -= min(m) (99-vignette.py:142-149), i.e.
+ *   out = max(v) - v.  chan_max DEV uint32 [3] is scratch.  out may be img.
+ *
+ * iamx_colour_lut: out[i] = lut[i % 3][img[i]], lut DEV uint8 [3][256]; with mask (DEV uint8
+ *   [n_values], may be null) out[i] = min(255, lut[..] + mask[i]) in the same pass.  out may be img.
+ * ------------------------------------------------------------------------------------ */
+int iamx_colour_histogram(const uint8_t *img, int64_t n_pixels, uint32_t *hist, void *stream);
+int iamx_colour_accumulate_max_frames(void);
+int iamx_colour_accumulate(const uint8_t *const *frames, int n_frames, int64_t n_values, uint32_t *sum,
+                           void *stream);
+int iamx_colour_mean(const uint32_t *sum, int64_t n_values, int count, uint8_t *avg, void *stream);
+int iamx_colour_moments_workspace_doubles(void);
+int iamx_colour_moments(const uint8_t *img, int height, int width, double cu, double cv, double *radius,
+                        double *partials, double *out, void *stream);
+int iamx_colour_fit_mask(int height, int width, double cu, double cv, const double *coef, uint64_t seed,
+                         uint8_t *out, void *stream);
+int iamx_colour_mask_finish(const uint8_t *img, int64_t n_pixels, uint32_t *chan_max, uint8_t *out,
+                            void *stream);
+int iamx_colour_lut(const uint8_t *img, int64_t n_pixels, const uint8_t *lut, const uint8_t *mask,
+                    uint8_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Step 5 surface grids -- replace the per-point scipy.interpolate.LinearNDInterpolator calls of
  * scripts/lib/render_panda3d.py:25-78,148-225 (intersect2d / intersect_vectors, with
  * project.projectVectors and project.intersectVectorsWithGroundPlane).  The Delaunay
