@@ -487,6 +487,63 @@ __device__ __forceinline__ void row_min16_piece(int (&r)[16], int (&u)[4], int l
     }
 }
 
+// The two asm levels of half_wave_min16<true> in SIX blocks of four DPP instructions (round 13: a
+// block of eight filled its MFMA gap twice over).  P = 0..3: the level "xor 8" on register pairs
+// 2P and 2P + 1; P = 4, 5: the level "xor 4" on the register quadruples 2(P-4) and 2(P-4) + 1 and
+// (the sweep adds their floor `lo` itself, as it runs the levels "xor 16" and inside the quads: one
+// or two instructions a gap).  Each block opens with its own s_nop 1 (DPP reads).
+template <int P, bool PASS>
+__device__ __forceinline__ void row_min16_block(int (&r)[16], int &after)
+{
+    static_assert(P >= 0 && P < 6, "six blocks");
+    // (`after`: a value the block follows; with PASS it leaves the block again, so that what reads it next
+    //  follows the block.  The block's text does not touch it.)
+    int keep = after;
+    if constexpr (P < 4) {
+        asm("s_nop 1\n\t"
+            "v_min_i32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %0, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_min_i32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_min_i32_dpp %1, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xc"
+            : "+v"(r[4 * P]), "+v"(r[4 * P + 2]), "+v"(keep)
+            : "v"(r[4 * P + 1]), "v"(r[4 * P + 3]));
+    } else {
+        constexpr int Q = 8 * (P - 4);
+        asm("s_nop 1\n\t"
+            "v_min_i32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %0, %3, %3 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_min_i32_dpp %1, %1, %1 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"
+            "v_min_i32_dpp %1, %4, %4 row_ror:4 row_mask:0xf bank_mask:0xa"
+            : "+v"(r[Q]), "+v"(r[Q + 4]), "+v"(keep)
+            : "v"(r[Q + 2]), "v"(r[Q + 6]));
+    }
+    if constexpr (PASS) after = keep;
+}
+
+// Form 2's chunk loop: the valu instructions that go behind MFMA `g` (0..7) of a step with `nv` of them
+// and `tail` other vector instructions (they end up in the last gap).  With `blocks`, gaps 3 and 4 hold
+// one minimum and an asm block of the row butterfly each.  Six issue slots a gap.
+constexpr int sweep_gap_valu(int nv, int tail, bool blocks, int g)
+{
+    const int last = tail < 6 ? 6 - tail : 0;
+    const int rest = nv - last - (blocks ? 2 : 0), n = blocks ? 5 : 7;
+    if (g == 7) return last;
+    if (blocks && (g == 3 || g == 4)) return 1;
+    const int i = blocks && g > 4 ? g - 2 : g;
+    return rest / n + (i < rest % n ? 1 : 0);
+}
+
+// a loop whose index is a compile-time constant in its body: f(int_c<I>) for I = FROM .. TO - 1
+template <int V> struct int_c { static constexpr int value = V; };
+template <int FROM, int TO, typename F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (FROM < TO) {
+        f(int_c<FROM>{});
+        static_for<FROM + 1, TO>(f);
+    }
+}
+
 // PIPE: the MFMAs of a pair of query blocks are issued while the minima of the previous pair are
 // taken (software pipeline across the 8 steps of a chunk, sched_group_barrier interleave); PIPE
 // epilogue VALU instructions go beside every MFMA.
@@ -761,8 +818,145 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
         // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
         // (meaningless) last tile into the buffer chunk 2 overwrites
         int rbo = 0, rbo_prev = 2 * NW * CHUNK;
+        // (the stage inside the chunk loop: ONE lane offset for every piece and chunk -- the swizzle of a
+        //  row depends on the row inside its piece only -- beside a scalar base, and the wave's LDS
+        //  destination from a scalar register)
+        const int wave_u = uniform32(wave);
+        // (the operand reads inside the chunk loop: a lane's LDS offsets in the stage buffer the reads go
+        //  to, switched by one xor each where the reads move on to the next chunk's buffer -- the tile and
+        //  the read ride in the instruction's offset)
+        typedef __attribute__((address_space(3))) const int8_t *lds_bytes;
+        int opoff[4], tboff = 2 * CHUNK * D + 16 * g;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) opoff[s] = c * D + (((2 * s + g) ^ ((c >> 1) & 7)) * 16);
+        auto load_op_at = [&](int tile, int k, v4i (&a)[4], v4i (&tbv)[4]) {
+            if (k < 4) tbv[k] = *reinterpret_cast<const __attribute__((address_space(3))) v4i *>((lds_bytes)lds + tboff + tile * 128 + 32 * k);
+            else a[k - 4] = *reinterpret_cast<const __attribute__((address_space(3))) v4i *>((lds_bytes)lds + opoff[k - 4] + tile * (32 * D));
+        };
+        const unsigned stage_voff = (unsigned)((tid >> 3) * D + (((tid & 7) ^ ((tid >> 4) & 7)) * 16));
+        const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
         for (int ch = 0; ch < nchunks; ++ch) {
             const int buf = ch & 1;
+            if constexpr (PP == 4) {
+            // Form 2 (round 13): the gap behind every MFMA of a step gets its own count of valu instructions
+            // (sched_group_barrier, sweep_gap_valu), so that no gap carries more than the MFMA beside it hides:
+            // 6 issue slots of 4 cycles behind the MFMA's own 8, of 32.  A step has 32 minima (16 row minima,
+            // then 8 + 8 column minima in two chains) and its share of the previous tile's row butterfly: an
+            // asm block of four DPP instructions in each of gaps 3 and 4 of the tile's first three steps, the
+            // floor behind the second level, the levels "xor 16" and inside the quads in the fourth step.
+            // What is no valu instruction belongs to no group (a group of LDS or memory instructions breaks
+            // the pipeline of groups behind it with this compiler) and ends up behind the step's last group:
+            // the step's two operand reads, and at most one instruction of the chunk's own work -- so the
+            // stage of chunk + 2 goes one instruction a step into the five steps from the barrier on, never
+            // two in one gap, and the merge of the previous chunk reads, computes and stores in three steps.
+            // The chunk's barrier is the head of the last step of tile NT4 - 2; the step in front of it
+            // issues no LDS read.
+            constexpr int BAR = (NT4 - 1) * PP - 1;
+            static_assert(NW == 4 && PIECES == 4 && BAR + 4 < NS && (NT / 8) % 16 == 0, "the gaps below are form 2's");
+            const int chs = ch + 2 < nchunks ? ch + 2 : nchunks - 1;
+            const int8_t *const sg_tile = tbase + (int64_t)chs * (CHUNK * D);
+            const int8_t *const sg_ct = reinterpret_cast<const int8_t *>(tci + chs * CHUNK);
+            int mR[NW], mL = BIG, mU1 = BIG, mU2 = BIG;
+            static_for<0, NS>([&](auto st_c) {
+                constexpr int st = decltype(st_c)::value;
+                constexpr int t = st / PP, ph = st % PP, qp = 2 * ph, cur = st & 1;
+                constexpr int nst = st + 1 < NS ? st + 1 : 0;
+                if constexpr (st == BAR) {
+                    // every read of this chunk's stage is done (lgkmcnt), the next chunk's stage has landed
+                    // (vmcnt): the stage of chunk + 2 may overwrite this one
+                    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
+                    __syncthreads();
+                }
+                issue(nst / PP, 2 * (nst % PP), accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                // the operand reads of tile T (flattened across chunks), 8 / PP a step as before; from tile
+                // NT4 on they read the next chunk's stage.  The step in front of the barrier has none (the
+                // barrier's wait would sit right behind them): the step before that issues them
+                static_for<(st == BAR - 1 ? 1 : 0), (st == BAR - 2 ? 2 : 1)>([&](auto d_c) {
+                    constexpr int sr = st + decltype(d_c)::value;
+                    constexpr int T = (sr + 1) / PP + 1, i = (sr + 1) % PP;
+                    if constexpr (T == NT4 && i == 0) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) opoff[s] ^= CHUNK * D;
+                        tboff ^= CHUNK * 4;
+                    }
+#pragma unroll
+                    for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k) load_op_at(T % NT4, k, aop[T & 1], tbop[T & 1]);
+                });
+                // the valu instructions of the step (the two swaps of the fourth step count twice) and what
+                // its last gap holds beside them
+                constexpr int nv = (ph == 2 ? 36 : ph == 3 ? 40 : 32) + (st == BAR + 2 ? 11 : 0) + (st == BAR + 3 ? 5 : 0) +
+                                   (st >= BAR && st <= BAR + PIECES ? 1 : 0) +    // (a stage instruction's address)
+                                   (st == NS - 1 ? 2 : 0);                          // (the loop's own)
+                constexpr int tail = (st == BAR - 1 ? 0 : st == BAR - 2 ? 4 : 2) + (ph == 3 ? 1 + 2 : 0) + (st >= BAR && st <= BAR + PIECES ? 1 : 0) +
+                                     (st == BAR + 1 ? 2 : 0) + (st == BAR + 3 ? 1 : 0);
+                // (the asm blocks of the row butterfly belong to no group: the first sits between the column
+                //  minimum that is the one valu instruction of gap 3 and the next one -- it passes the running
+                //  minimum through -- and the second reads that next one, the one of gap 4)
+                constexpr int blk_at = sweep_gap_valu(nv, tail, true, 0) + sweep_gap_valu(nv, tail, true, 1) +
+                                       sweep_gap_valu(nv, tail, true, 2) - 16;
+                static_assert(ph == 3 || (blk_at >= 0 && blk_at < 15 && blk_at != 7), "gaps 3 and 4 hold two minima of one column chain");
+                // minima of this step: the rows first, then the two column chains; with them the previous
+                // tile's row butterfly (tile NT4 - 1 of the previous chunk for t = 0)
+                const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
+                int (&rc_)[16] = r[t & 1];
+                int (&rp)[16] = r[(t + 1) & 1];
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg)
+                    rc_[reg] = qp == 0 ? min(acc0[reg], acc1[reg]) : min(min(rc_[reg], acc0[reg]), acc1[reg]);
+                static_for<0, 16>([&](auto w_c) {
+                    constexpr int w = decltype(w_c)::value;
+                    int &mm = m[qp + (w >> 3)][t & 3];
+                    const v16i &acc = w < 8 ? acc0 : acc1;
+                    mm = min(min(mm, acc[2 * (w & 7)]), acc[2 * (w & 7) + 1]);
+                    if constexpr (ph < 3 && w == blk_at) row_min16_block<2 * ph, true>(rp, mm);
+                    if constexpr (ph < 3 && w == blk_at + 1) row_min16_block<2 * ph + 1, true>(rp, mm);
+                });
+                if constexpr (ph == 2) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) bu[k] = rp[4 * k] + lo_lane;
+                }
+                if constexpr (ph == 3) {
+                    int *const dst = row_dst + (t > 0 ? rbo : rbo_prev) + (t > 0 ? t - 1 : NT4 - 1) * 32;
+                    row_min16_piece<3>(rp, bu, lo_lane, dst);
+                }
+                // the chunk's own work behind its barrier: the merge of the previous chunk (its rows' last
+                // minima were stored in this chunk's first tile) and the stage of chunk + 2
+                // what is no valu instruction belongs to no group and goes behind the step's last group, into
+                // its last gap: the step's two operand reads, the store of the row minima, and one piece of the
+                // chunk's own work a step from the barrier on -- the stage of chunk + 2 (one instruction a step:
+                // its buffer is free behind the barrier, its data is due a chunk later) and the merge of the
+                // previous chunk (its rows' last minima were stored in this chunk's first tile)
+                if constexpr (st >= BAR && st < BAR + PIECES)
+                    __builtin_amdgcn_global_load_lds(sg_tile + (st - BAR) * ((NT / 8) * D) + stage_voff,
+                                                     (lds_ptr)(lds_tile + buf * (CHUNK * D) + ((st - BAR) * NT + wave_u * 64) * 16), 16, 0, 0);
+                if constexpr (st == BAR + PIECES)
+                    __builtin_amdgcn_global_load_lds(sg_ct + ct_voff,
+                                                     (lds_ptr)(lds_tb + buf * CHUNK + (wave_u & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
+                if constexpr (st == BAR + 1) {
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) mR[w] = lds_row[rbo_prev + w * CHUNK + mrow];
+                }
+                if constexpr (st == BAR + 2) {
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        const int uw = mR[w] + spread_w[w];
+                        mL = min(mL, mR[w]);
+                        mU2 = min(max(mU1, uw), mU2);
+                        mU1 = min(mU1, uw);
+                    }
+                }
+                if constexpr (st == BAR + 3)
+                    __builtin_amdgcn_raw_buffer_store_b64(v2i{mL, pack_row_bounds(mL, mU1, mU2)}, rowp_rsrc,
+                                                          merger && ch > 0 ? ((ch - 1) * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
+                static_for<0, 8>([&](auto g_c) {
+                    constexpr int g = decltype(g_c)::value;
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    // (the last group takes what the counts above missed)
+                    __builtin_amdgcn_sched_group_barrier(0x002, sweep_gap_valu(nv, tail, ph < 3, g) + (g == 7 ? 3 : 0), 0);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            } else {
 #pragma unroll
             for (int st = 0; st < NS; ++st) {
                 const int t = st / PP, qp = 2 * (st % PP), cur = st & 1;
@@ -828,6 +1022,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                     __builtin_amdgcn_sched_group_barrier(0x002, PIPE, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
+            }
             }
             rbo_prev = rbo;
             rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
