@@ -201,6 +201,11 @@ SIGNATURES = {
     'iamx_trf_active': (c_int, [c_int64] + [c_void_p] * 3 + [c_double] + [c_void_p] * 2),
     'iamx_trf_feasible_start': (c_int, [c_int64] + [c_void_p] * 3 + [c_double] + [c_void_p] * 2),
     'iamx_trf_scaled_start': (c_int, [c_int64] + [c_void_p] * 6),
+    'iamx_undistort_points': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'iamx_chain_triangulate': (c_int, [c_void_p] * 4 + [c_int64, c_int] + [c_void_p] * 3 + [c_int]
+                               + [c_void_p] * 5),
+    'iamx_chain_pair_angles': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p, c_void_p, c_int,
+                                       c_double] + [c_void_p] * 4),
 }
 
 

@@ -10,6 +10,12 @@
     link_matches(proj, direct)      :223-301                   chains per feature, kp -> uv, longest first
     triangulate_smart(proj, matches):303-347                   match[0] = mean ground intersection
 
+and the loop of scripts/3c-match-triangulation.py --method triangulate:
+
+    triangulate_rays(proj, matches, group_list, group_index, attitude='initial')
+                                                               match[0] = least-squares intersection of
+                                                               the chain's undistorted rays
+
 Same function names, arguments, in-place effects and result structures (plain python lists, so
 the `matches_grouped` pickle stays readable by the reference's tools).  What changes is how the
 work is done: keys are exact integers instead of formatted strings (matcher.kp_key2), per-pair
@@ -638,3 +644,130 @@ def triangulate_smart(proj, matches):
         res = out.cpu().numpy().tolist()
         for m, p in zip(matches, res):
             m[0] = p
+
+
+# --------------------------------------------------------------------------------------
+# ray intersection -- scripts/3c-match-triangulation.py:137-165 (+ lib/line_solver.py)
+# --------------------------------------------------------------------------------------
+# per-chain status of iamx_chain_triangulate / iamx_chain_pair_angles (include/iamx.h IAMX_CHAIN_*)
+CHAIN_UNTOUCHED, CHAIN_WRITTEN, CHAIN_WRITTEN_BELOW, CHAIN_SINGULAR, CHAIN_BAD_IMAGE = range(5)
+
+
+class RayTriangulation(object):
+    """what triangulate_rays() did: `written` chain indices (ascending, the reference's order),
+    `below` those of them with x[2] > 0 (the reference prints "WHOA!"), `old` / `new` [len(written), 3]
+    positions before (NaN where there was none) and after."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def chain_arrays(matches):
+    """(ptr, img, uv, group, ned, has_ned) of list chains or an untouched Chains (no copy then)."""
+    if isinstance(matches, Chains) and matches.untouched():
+        return matches.ptr, matches.img, matches.uv, matches.group, matches.ned, matches.has_ned
+    n = len(matches)
+    with _no_gc():
+        ptr = np.zeros(n + 1, np.int64)
+        if n:
+            np.cumsum([len(m) - 2 for m in matches], out=ptr[1:])
+        flat = [p for m in matches for p in m[2:]]
+        img = np.fromiter((p[0] for p in flat), np.int64, len(flat))
+        uv = np.array([p[1] for p in flat], np.float64).reshape(-1, 2)
+        del flat
+        group = np.fromiter((m[1] for m in matches), np.int64, n)
+        has_ned = np.fromiter((m[0] is not None for m in matches), bool, n)
+        ned = np.zeros((n, 3), np.float64)
+        for c in np.nonzero(has_ned)[0].tolist():
+            ned[c] = matches[c][0]
+    # (an index that does not fit int32 is out of range for any project: keep it so)
+    lim = np.iinfo(np.int32)
+    return (ptr, np.clip(img, lim.min, lim.max).astype(np.int32), uv,
+            np.clip(group, lim.min, lim.max).astype(np.int32), ned, has_ned)
+
+
+def group_membership(proj, group_list, group_index):
+    """uint8 [n_images]: image.name in group_list[group_index]"""
+    names = set(group_list[group_index])
+    return np.fromiter((im.name in names for im in proj.image_list), np.uint8, len(proj.image_list))
+
+
+def raise_bad_image(status, img, ptr, n_img, what):
+    bad = np.nonzero(status == CHAIN_BAD_IMAGE)[0]
+    if len(bad):
+        c = int(bad[0])
+        members = img[ptr[c]:ptr[c + 1]]
+        k = members[(members < 0) | (members >= n_img)][0]
+        raise IndexError("%s: chain %d refers to image %d, the project has %d images"
+                         % (what, c, int(k), n_img))
+
+
+def triangulate_rays(proj, matches, group_list, group_index, attitude='initial'):
+    """Every chain of group `group_index` with at least two members in the group gets the
+    least-squares intersection of those members' rays as its position (in place), one thread per
+    chain (iamx_chain_triangulate).  Optimised K and distortion, camera positions from
+    camera_pose_opt.  attitude='initial' takes body2ned from the INITIAL pose, as the reference's
+    script does (image.get_body2ned() defaults to opt=False); 'optimized' takes it from
+    camera_pose_opt as well.  -> RayTriangulation."""
+    import ctypes
+    import torch
+    from . import kernels
+    from .kernels import _ptr, check, lib, stream_ptr
+    if attitude not in ('initial', 'optimized'):
+        raise ValueError("attitude must be 'initial' or 'optimized'")
+    if not 0 <= group_index < len(group_list):
+        raise IndexError("group %d of %d" % (group_index, len(group_list)))
+    cam = _deps.camera()
+    K = np.asarray(cam.get_K(optimized=True), np.float64)
+    dist = np.ascontiguousarray(np.array(cam.get_dist_coeffs(optimized=True), np.float64).ravel())
+    IK = np.linalg.inv(K)
+    k4 = np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]], np.float64)
+    n_img = len(proj.image_list)
+    M = np.zeros((n_img, 9))
+    pos = np.zeros((n_img, 3))
+    opt_att = attitude == 'optimized'
+    for i, image in enumerate(proj.image_list):
+        cam2body = image.get_cam2body() if hasattr(image, 'get_cam2body') else CAM2BODY
+        body2ned = image.get_body2ned(opt=True) if opt_att else image.get_body2ned()
+        M[i] = body2ned.dot(cam2body).dot(IK).ravel()
+        pos[i] = image.get_camera_pose(opt=True)[0]
+    in_group = group_membership(proj, group_list, group_index)
+    n = len(matches)
+    empty = RayTriangulation(written=np.zeros(0, np.int64), below=np.zeros(0, np.int64),
+                             old=np.zeros((0, 3)), new=np.zeros((0, 3)), attitude=attitude)
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    if n == 0:
+        check(lib().iamx_chain_triangulate(None, None, None, None, 0, group_index, None, None, None,
+                                           n_img, hp(k4), hp(dist), None, None, None),
+              'iamx_chain_triangulate')
+        return empty
+    fast = isinstance(matches, Chains) and matches.untouched()
+    ptr, img, uv, group, ned, has_ned = chain_arrays(matches)
+    dev = kernels.require_gpu()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_ptr, d_img, d_uv, d_group, d_M, d_pos, d_in, d_ned = (
+        t(a) for a in (ptr, img, uv, group, M, pos, in_group, ned))
+    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib().iamx_chain_triangulate(_ptr(d_ptr), _ptr(d_img), _ptr(d_uv), _ptr(d_group), n, group_index,
+                                       _ptr(d_M), _ptr(d_pos), _ptr(d_in), n_img, hp(k4), hp(dist),
+                                       _ptr(d_ned), _ptr(d_status), stream_ptr()),
+          'iamx_chain_triangulate')
+    status = d_status.cpu().numpy()
+    raise_bad_image(status, img, ptr, n_img, 'triangulate_rays')
+    singular = np.nonzero(status == CHAIN_SINGULAR)[0]
+    if len(singular):
+        raise np.linalg.LinAlgError("Singular matrix: the rays of chain %d do not intersect in a point"
+                                    % int(singular[0]))
+    written = np.nonzero((status == CHAIN_WRITTEN) | (status == CHAIN_WRITTEN_BELOW))[0]
+    new = d_ned.cpu().numpy()
+    old = np.where(has_ned[written, None], ned[written], np.nan)
+    res = RayTriangulation(written=written, below=np.nonzero(status == CHAIN_WRITTEN_BELOW)[0], old=old,
+                           new=new[written], attitude=attitude)
+    if fast and matches.untouched():
+        matches.ned[written] = new[written]
+        matches.has_ned[written] = True
+        return res
+    with _no_gc():
+        for c, p in zip(written.tolist(), new[written].tolist()):
+            matches[c][0] = p
+    return res

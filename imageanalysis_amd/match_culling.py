@@ -19,6 +19,13 @@ New, for the 4b-mre-by-image.py twin (imageanalysis_amd/scripts/4b-mre-by-image.
         flagged observations (ascending) come back, are ordered by descending e on the host (ties
         in observation order: the reference's stable sort) and marked
 
+New, for the 4b-colocated-feats.py twin (imageanalysis_amd/scripts/4b-colocated-feats.py):
+
+    colocated_features(proj, matches, group_list, group_index, min_angle) -> mark list
+        [chain, member] once per member pair of the group that sees the chain's position under less
+        than min_angle degrees, in the reference's order: one pass of iamx_chain_pair_angles, the
+        per-member counts come back and are unrolled on the host
+
 `matches` is the reference's list of `[ned, group, [image, [u, v]], ...]` chains, or the
 array-backed match_cleanup.Chains: marks on an untouched Chains are kept in a member mask
 (`chains.marked`) and delete_marked_features() rebuilds its arrays with numpy.
@@ -227,6 +234,71 @@ def mark_outliers(matches, report, trim_stddev, max_error=None):
     for m, f, e in zip(match_index.tolist(), feat_index.tolist(), err.tolist()):
         mark_feature(matches, m, f, e)
     return len(obs)
+
+
+# ---------------------------------------------------------------------------------------------
+# co-located cameras (4b-colocated-feats.py:47-91)
+# ---------------------------------------------------------------------------------------------
+def marks_from_counts(ptr, count):
+    """per-member pair counts -> the reference's mark_list: [chain, member] repeated count times,
+    chains ascending, members ascending (its loops append [k, i] for every j > i that is close)"""
+    count = np.asarray(count, np.int64)
+    hit = np.nonzero(count)[0]
+    if len(hit) == 0:
+        return []
+    ptr = np.asarray(ptr, np.int64)
+    chain = np.searchsorted(ptr, hit, side='right') - 1
+    member = hit - ptr[chain]
+    rep = count[hit]
+    return np.stack([np.repeat(chain, rep), np.repeat(member, rep)], 1).tolist()
+
+
+def colocated_features(proj, matches, group_list, group_index, min_angle):
+    """The mark list of scripts/4b-colocated-feats.py: for every chain of group `group_index`, every
+    pair of members i < j whose images are both in the group and whose two cameras (camera_pose_opt
+    positions) see the chain's position under less than `min_angle` degrees contributes [chain, i].
+    The angle is the one the reference's compute_angle() means: its script never imports math, so as
+    written every pair comes back as 0 and is marked.  Duplicates are kept (a member close to two
+    others is listed twice), as the reference prints and counts them."""
+    import torch
+    from . import kernels, match_cleanup
+    from .kernels import _ptr, check, lib, stream_ptr
+    if not 0 <= group_index < len(group_list):
+        raise IndexError("group %d of %d" % (group_index, len(group_list)))
+    min_angle = float(min_angle)
+    if np.isnan(min_angle):
+        raise ValueError("min_angle is NaN")
+    n_img = len(proj.image_list)
+    n = len(matches)
+    if n == 0:
+        check(lib().iamx_chain_pair_angles(None, None, None, None, 0, group_index, None, None, n_img,
+                                           min_angle, None, None, None, None), 'iamx_chain_pair_angles')
+        return []
+    ptr, img, _uv, group, ned, has_ned = match_cleanup.chain_arrays(matches)
+    missing = np.nonzero((group == group_index) & ~has_ned)[0]
+    if len(missing):
+        raise ValueError("chain %d of group %d has no position (match[0] is None): triangulate the "
+                         "chains before looking for co-located cameras" % (int(missing[0]), group_index))
+    pos = np.zeros((n_img, 3))
+    for i, image in enumerate(proj.image_list):
+        pos[i] = image.get_camera_pose(opt=True)[0]
+    in_group = match_cleanup.group_membership(proj, group_list, group_index)
+    dev = kernels.require_gpu()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_ptr, d_img, d_group, d_ned, d_pos, d_in = (t(a) for a in (ptr, img, group, ned, pos, in_group))
+    d_count = torch.empty(max(len(img), 1), dtype=torch.int32, device=dev)
+    d_total = torch.empty(1, dtype=torch.int64, device=dev)
+    d_status = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib().iamx_chain_pair_angles(_ptr(d_ptr), _ptr(d_img), _ptr(d_group), _ptr(d_ned), n, group_index,
+                                       _ptr(d_pos), _ptr(d_in), n_img, min_angle, _ptr(d_count),
+                                       _ptr(d_total), _ptr(d_status), stream_ptr()),
+          'iamx_chain_pair_angles')
+    match_cleanup.raise_bad_image(d_status.cpu().numpy(), img, ptr, n_img, 'colocated_features')
+    if int(d_total.item()) == 0:
+        return []
+    mark_list = marks_from_counts(ptr, d_count[:len(img)].cpu().numpy())
+    assert len(mark_list) == int(d_total.item())
+    return mark_list
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1161,6 +1161,56 @@ int iamx_trf_feasible_start(int64_t n, const double *x, const double *lb, const 
 int iamx_trf_scaled_start(int64_t n, const double *x, const double *scale_inv, const double *v,
                           const double *dv, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Chain geometry between optimiser passes -- scripts/3c-match-triangulation.py (--method
+ * triangulate), scripts/4b-colocated-feats.py and lib/project.py:257-296 (undistort_uvlist,
+ * undistort_image_keypoints).  One thread per point / per chain, f64 in stored order, every product
+ * and sum rounded on its own.  K4 = {fx, fy, cx, cy} and dist5 = {k1, k2, p1, p2, k3} are HOST
+ * pointers; everything else is DEV.  Null and size checks need no GPU; n == 0 returns 0 without a
+ * launch.
+ *
+ * iamx_undistort_points: src [n][2] f32 -> dst [n][2] f32, cv2.undistortPoints(src, K, dist, P=K)
+ *   with OpenCV's default criteria as published: x = (u-cx)/fx, y = (v-cy)/fy, five rounds of
+ *   r2 = x*x + y*y; icdist = 1/(1 + ((k3*r2 + k2)*r2 + k1)*r2); dx = 2*p1*x*y + p2*(r2 + 2*x*x);
+ *   dy = p1*(r2 + 2*y*y) + 2*p2*x*y; x = (x0 - dx)*icdist; y = (y0 - dy)*icdist (icdist < 0: x0, y0
+ *   and stop); out = x*fx + cx, y*fy + cy rounded to f32.  Pinned bit for bit to the numpy
+ *   restatement tests/undistort_restatement.py; parity with cv2 itself is UNPINNED (cv2 is not
+ *   available to the tests), as for CLAHE and the resizes.
+ *
+ * The chain arrays are match_cleanup.Chains': ptr [n_chains + 1] i64, img [total] i32, uv [total][2]
+ * f64, group [n_chains] i32, ned [n_chains][3] f64.  pos [n_images][3] camera positions, in_group
+ * [n_images] u8.  A chain is looked at when group[c] == group_index.  An image index outside
+ * [0, n_images) in such a chain: IAMX_CHAIN_BAD_IMAGE, nothing is read through it, nothing written.
+ *
+ * iamx_chain_triangulate: chains with >= 2 members in the group; per such member, in stored order:
+ *   uv -> f32 -> undistort (as above) -> f32, v = unit(unit(M [u, v, 1])) with M [n_images][9] =
+ *   body2ned . cam2body . inv(K) row major, r += I - v v^T, q += (I - v v^T) pos; r x = q by LU with
+ *   partial pivoting (lib/line_solver.py ls_lines_intersection), x -> ned[c].  status [n_chains]:
+ *   IAMX_CHAIN_UNTOUCHED / _WRITTEN / _WRITTEN_BELOW (x[2] > 0, the reference's "WHOA!") /
+ *   _SINGULAR (zero pivot, ned[c] kept) / _BAD_IMAGE.
+ *
+ * iamx_chain_pair_angles: members i < j both in the group: v1 = ned[c] - pos[i], v2 = ned[c] - pos[j],
+ *   tmp = v1.v2 / (|v1| |v2|), angle = acos(min(tmp, 1)) in degrees, tmp < -1 -> 0 (the reference's
+ *   except path), NaN never counts; angle < min_angle_deg: count[i] += 1.  count [total] i32 (every
+ *   member of every chain is written), total [1] i64 = sum of count, status [n_chains]:
+ *   IAMX_CHAIN_UNTOUCHED / _WRITTEN (scanned) / _BAD_IMAGE.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_CHAIN_UNTOUCHED 0
+#define IAMX_CHAIN_WRITTEN 1
+#define IAMX_CHAIN_WRITTEN_BELOW 2
+#define IAMX_CHAIN_SINGULAR 3
+#define IAMX_CHAIN_BAD_IMAGE 4
+int iamx_undistort_points(const float *src, int64_t n, const double *K4, const double *dist5,
+                          float *dst, void *stream);
+int iamx_chain_triangulate(const int64_t *ptr, const int32_t *img, const double *uv,
+                           const int32_t *group, int64_t n_chains, int group_index, const double *M,
+                           const double *pos, const uint8_t *in_group, int n_images, const double *K4,
+                           const double *dist5, double *ned, int32_t *status, void *stream);
+int iamx_chain_pair_angles(const int64_t *ptr, const int32_t *img, const int32_t *group,
+                           const double *ned, int64_t n_chains, int group_index, const double *pos,
+                           const uint8_t *in_group, int n_images, double min_angle_deg, int32_t *count,
+                           int64_t *total, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
