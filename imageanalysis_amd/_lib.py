@@ -107,6 +107,7 @@ SIGNATURES = {
     'iamx_image_resized_dims': (c_int, [c_int, c_int, c_double, c_void_p, c_void_p]),
     'iamx_image_equalize_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_double,
                                            c_void_p, c_int64, c_void_p, c_void_p]),
+    'iamx_image_prep_stage': (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     'iamx_image_area_dims': (c_int, [c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     'iamx_image_resize_area': (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
                                        c_void_p]),

@@ -23,6 +23,8 @@ for f in $SRCS; do
         [ "$(basename $f)" = "image_colour.hip" ] && EXTRA="-ffp-contract=off"
         # the surface walk restates scipy's barycentric f64 expressions, operation by operation
         [ "$(basename $f)" = "surface_grid.hip" ] && EXTRA="-ffp-contract=off"
+        # the image preparation restates numpy's float32 CLAHE blend and HSV->BGR chains, operation by operation
+        [ "$(basename $f)" = "image_prep.hip" ] && EXTRA="-ffp-contract=off"
         # the chain geometry restates numpy / OpenCV double expressions, operation by operation
         [ "$(basename $f)" = "chain_geom.hip" ] && EXTRA="-ffp-contract=off"
         # the one-wave-per-SIMD sweep (form 2) needs its MFMA

@@ -5,6 +5,11 @@
 // The 8-bit algorithms are restated from their published definitions (fixed-point HSV with
 // 12-bit division tables, clip + uniform redistribution, bilinear blending of the tile LUTs,
 // 11-bit fixed-point resize); cv2 itself is absent, the oracle is oracle/image_oracle.py.
+// The float chains restate the oracle's numpy expressions, operation by operation: every multiply,
+// add and subtract is rounded on its own.  build.sh compiles this file with -ffp-contract=off for
+// that; the __fmul_rn / __fadd_rn / __fsub_rn below are plain * + - to this compiler (they only
+// mark the chains that must stay unfused) and did not keep it from fusing seven of them, nor the
+// resize's double `(d + 0.5) * sc - 0.5`.
 #include "iamx_common.h"
 
 namespace {
@@ -181,12 +186,45 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t *__restrict__
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// Workspace layout: hsv [npx*3] | equalised [npx*3] | pad to 256 | hist [64][256] int | lut [64][256]
+enum { STAGE_HSV = 0, STAGE_EQ = 1, STAGE_HIST = 2, STAGE_LUT = 3 };
+
+inline bool stage_span(int height, int width, int stage, int64_t *offset, int64_t *bytes)
+{
+    const int64_t npx = (int64_t)height * width;
+    const int64_t hist = (npx * 6 + 255) / 256 * 256;
+    switch (stage) {
+    case STAGE_HSV: *offset = 0; *bytes = npx * 3; return true;
+    case STAGE_EQ: *offset = npx * 3; *bytes = npx * 3; return true;
+    case STAGE_HIST: *offset = hist; *bytes = 64 * 256 * 4; return true;
+    case STAGE_LUT: *offset = hist + 64 * 256 * 4; *bytes = 64 * 256; return true;
+    }
+    return false;
+}
+
+template <typename T> inline T *stage_ptr(void *workspace, int height, int width, int stage)
+{
+    int64_t off = 0, bytes = 0;
+    stage_span(height, width, stage, &off, &bytes);
+    return reinterpret_cast<T *>(static_cast<uint8_t *>(workspace) + off);
+}
+
 }  // namespace
 
 extern "C" int64_t iamx_image_prep_workspace_bytes(int height, int width)
 {
     if (height < 1 || width < 1) return 0;
     return (int64_t)height * width * 6 + 64 * 256 * 4 + 64 * 256 + 1024;
+}
+
+// Where a stage's result lives inside the workspace after iamx_image_equalize_resize (tests /
+// diagnosis): 0 = hsv, 1 = equalised BGR, 2 = tile histograms, 3 = tile LUTs.  Host only.
+extern "C" int iamx_image_prep_stage(int height, int width, int stage, int64_t *offset, int64_t *bytes)
+{
+    IAMX_REQUIRE(offset && bytes, "null pointer");
+    IAMX_REQUIRE(height >= 1 && width >= 1, "bad image size");
+    IAMX_REQUIRE(stage_span(height, width, stage, offset, bytes), "no such stage");
+    return IAMX_OK;
 }
 
 extern "C" int iamx_image_resized_dims(int height, int width, double scale, int *out_h, int *out_w)
@@ -207,10 +245,10 @@ extern "C" int iamx_image_equalize_resize(const uint8_t *bgr, int height, int wi
                  "workspace too small");
     hipStream_t st = iamx::as_stream(stream);
     const int64_t npx = (int64_t)height * width;
-    uint8_t *hsv = static_cast<uint8_t *>(workspace);
-    uint8_t *eq = hsv + npx * 3;
-    int *hist = reinterpret_cast<int *>(eq + npx * 3 + (256 - (npx * 6) % 256) % 256);
-    uint8_t *lut = reinterpret_cast<uint8_t *>(hist + 64 * 256);
+    uint8_t *hsv = stage_ptr<uint8_t>(workspace, height, width, STAGE_HSV);
+    uint8_t *eq = stage_ptr<uint8_t>(workspace, height, width, STAGE_EQ);
+    int *hist = stage_ptr<int>(workspace, height, width, STAGE_HIST);
+    uint8_t *lut = stage_ptr<uint8_t>(workspace, height, width, STAGE_LUT);
     const uint8_t *src = bgr;
     if (equalize) {
         const int pw = width % TILES ? width + (TILES - width % TILES) : width;

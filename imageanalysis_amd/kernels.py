@@ -1353,6 +1353,25 @@ def equalize_resize(bgr, scale, equalize=True, clip_limit=3.0):
     return out
 
 
+def image_prep_stages(h, w):
+    """What the last equalize_resize(equalize=True) of an [h, w, 3] image left in the current slot's
+    workspace (tests / diagnosis): views 'hsv' and 'equalised' uint8 [h,w,3], 'hist' int32 [64,256]
+    and 'lut' uint8 [64,256], laid out as iamx_image_prep_stage says."""
+    dev = require_gpu()
+    ws = _prep_ws.get(_slot_key(dev))
+    if ws is None or ws.numel() < int(lib().iamx_image_prep_workspace_bytes(h, w)):
+        raise _lib.IamxError("no equalize_resize of a %dx%d image has run in this slot" % (h, w))
+    import ctypes
+    views = {}
+    for stage, (name, dtype, shape) in enumerate((('hsv', U8, (h, w, 3)), ('equalised', U8, (h, w, 3)),
+                                                  ('hist', I32, (64, 256)), ('lut', U8, (64, 256)))):
+        off, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().iamx_image_prep_stage(h, w, stage, ctypes.byref(off), ctypes.byref(nbytes)),
+              'iamx_image_prep_stage')
+        views[name] = ws[off.value:off.value + nbytes.value].view(dtype).view(shape)
+    return views
+
+
 def resize_area(img, fx, fy):
     """cv2.resize(img, (0, 0), fx=fx, fy=fy, interpolation=cv2.INTER_AREA) on the device
     (csrc/image_area.hip; downscale only).  img uint8 [h,w,3] or [h,w] (numpy or device) ->

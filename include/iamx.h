@@ -615,6 +615,13 @@ int iamx_image_equalize_resize(const uint8_t *bgr, int height, int width, int eq
                                float clip_limit, double scale, void *workspace,
                                int64_t workspace_bytes, uint8_t *out, void *stream);
 
+/* Where a stage's result lives inside the workspace after iamx_image_equalize_resize with
+ * equalize != 0 (tests / diagnosis; host only): stage 0 = hsv uint8 [height][width][3],
+ * 1 = equalised BGR uint8 [height][width][3], 2 = tile histograms int32 [64][256] (row = tile
+ * ty * 8 + tx, over the reflect-101 padded tile), 3 = tile look-up tables uint8 [64][256]; at
+ * workspace + *offset, *bytes long.  Any other stage, or a null pointer, fails with -1. */
+int iamx_image_prep_stage(int height, int width, int stage, int64_t *offset, int64_t *bytes);
+
 /* ------------------------------------------------------------------------------------
  * Area downscale -- replaces cv2.resize(src, (0,0), fx, fy, interpolation=cv2.INTER_AREA) of the
  * texture step (scripts/lib/panda3d.py:38-41,69-72) for interleaved uint8 images.

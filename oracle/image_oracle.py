@@ -67,8 +67,9 @@ def _reflect101(idx, n):
     return np.where(idx >= n, period - idx, idx)
 
 
-def clahe(v, clip_limit=3.0, tiles=(8, 8)):
-    """cv2.createCLAHE(clipLimit, tileGridSize).apply on uint8."""
+def clahe(v, clip_limit=3.0, tiles=(8, 8), return_luts=False):
+    """cv2.createCLAHE(clipLimit, tileGridSize).apply on uint8.  return_luts=True: (result, the
+    tile look-up tables uint8 [ty, tx, 256]) instead of the result alone."""
     h, w = v.shape
     tx, ty = tiles
     pw = w if w % tx == 0 else w + (tx - w % tx)
@@ -117,7 +118,8 @@ def clahe(v, clip_limit=3.0, tiles=(8, 8)):
     ya1 = np.float32(1) - ya
     res = (l11 * xa1[None, :] + l12 * xa[None, :]) * ya1[:, None] + \
           (l21 * xa1[None, :] + l22 * xa[None, :]) * ya[:, None]
-    return np.clip(np.rint(res), 0, 255).astype(np.uint8)
+    res = np.clip(np.rint(res), 0, 255).astype(np.uint8)
+    return (res, luts) if return_luts else res
 
 
 def equalize_bgr(bgr):

@@ -23,8 +23,7 @@ def test_equalize_resize_equals_oracle(shape, scale):
     want = io.resize_linear_u8(io.equalize_bgr(img), scale)
     got = kernels.equalize_resize(img, scale).cpu().numpy()
     assert got.shape == want.shape
-    diff = np.abs(got.astype(int) - want.astype(int))
-    assert diff.max() <= 1 and (diff == 0).mean() > 0.995     # u8 rounding ties of float chains
+    assert np.array_equal(got, want)          # (stage by stage: test_image_prep_gpu.py)
     plain = kernels.equalize_resize(img, scale, equalize=False).cpu().numpy()
     assert np.array_equal(plain, io.resize_linear_u8(img, scale))
 
