@@ -55,7 +55,7 @@ BATCH_BYTES = 24 << 30  # ... as far as one batch's device workspace stays below
 PREWARM_ROUNDS = 32     # a call with at least this many rounds fills its buffer pools on a helper thread first
 EARLY_SMART_ROUNDS = 8  # rounds in a row without a match before smart.json is written ahead of time
 early_smart_stats = {'written': 0, 'current_at_end': 0}     # (tests / diagnosis)
-PACK_CAP = 4 << 20      # matches a batch's packed download holds (more: that batch's slots are copied)
+MAX_IMAGE_ROWS = 1 << 24    # descriptor rows of one image: what the packers and the filter kernel index
 # Which sweep a round of find_matches takes.  The symmetric sweep (one MFMA pass per image pair)
 # leaves the rows whose bounds pass the metric test to an exact stage that runs at half the sweep's
 # rate; on overlapping frames of real imagery 15-30 % of the rows are such candidates.  Round 5
@@ -154,8 +154,6 @@ class DeviceMatcher(object):
         self._pending = []
         self._kp = {}             # slot -> (xy float32 [n,2], key2 int32 [n,2]) host copies
         self._kp_dev = None       # (n_slots, kp_off, xy, key2) device arena of the post filter
-        self._proj = {}           # slot -> (pose, [R|t] row major, epoch) for the surface triangulation
-        self._pose_epoch = None   # set by find_matches: camera poses do not change inside one call
         self._adopted = {}        # image name -> n_rows: features that arrived from another rank
 
     # cv2-style single pair call (returns numpy (idx[nq,2], dist[nq,2] float32))
@@ -178,6 +176,7 @@ class DeviceMatcher(object):
         n = int(image.des_list.shape[0])
         if ent is not None and ent[1] == n:
             return ent[0]
+        _check_rows(image.name, n)
         self._adopted.pop(image.name, None)     # (re-)detected here after all
         slot = len(self._counts)
         self._slots[image.name] = (slot, n)
@@ -204,6 +203,7 @@ class DeviceMatcher(object):
         des uint8 [n,128] (device or host), xy float32 [n,2] host.  The image object itself keeps
         no kp_list / des_list on this rank."""
         n = int(des.shape[0])
+        _check_rows(name, n)
         slot = len(self._counts)
         self._slots[name] = (slot, n)
         self._adopted[name] = n
@@ -362,6 +362,14 @@ class DeviceMatcher(object):
         if want_train and not self._store.has_train_layout:
             self._store.ensure_train_layout()
         return self._store
+
+
+def _check_rows(name, n):
+    """an image the device matcher cannot hold: the single-image packers and the survivor lists of
+    the filter kernel (MAX_SURV) take at most 2^24 rows, so no batch ever hands a pair back"""
+    if n > MAX_IMAGE_ROWS:
+        raise ValueError("image %s has %d descriptor rows; the device matcher takes at most %d (1 << 24)"
+                         % (name, n, MAX_IMAGE_ROWS))
 
 
 def _kp_xy(image):
@@ -782,7 +790,7 @@ def _workspace(rows, pairs):
 
 
 def _post_set(n, clip, dev, surface):
-    """surface: False, True (triangulated heights + similarity fits) or 'fit' (the fits only)"""
+    """surface (a bool): with the similarity fits"""
     import torch
     free = _post_pool.setdefault((n, clip, surface), [])
     if free:
@@ -793,8 +801,6 @@ def _post_set(n, clip, dev, surface):
                 scratch=torch.empty((n, 2, clip, 2), dtype=torch.int32, device=dev),
                 stat=torch.empty((n, 4), dtype=torch.int32, device=dev),
                 status=torch.empty(n, dtype=torch.int32, device=dev))
-    if surface is True:
-        post['z'] = torch.empty((n, clip), dtype=torch.float64, device=dev)
     if surface:
         post['aff'] = torch.empty((n, 2, 6), dtype=torch.float64, device=dev)
         post['aff_ok'] = torch.empty((n, 2), dtype=torch.int32, device=dev)
@@ -849,8 +855,11 @@ def device_memory_model(n_images, rows_per_image, train_layout=False):
                 peak_bytes=int(arena + 3 * ws + 2 * ppb * clip * 32))
 
 
-def _recycle(h):
-    """a finished round's device buffers back to their pools"""
+def _recycle(h, keep_host=False):
+    """a finished round's buffers back to their pools: workspace, device result set and -- unless
+    the round's _RoundResult keeps them until its done() -- the page-locked landing buffers"""
+    if not keep_host:
+        _host_sets[h['host']['key']].append(h['host'])
     if h.get('ws') is not None:
         _ws_pool.append(h['ws'])
         h['ws'] = None
@@ -873,11 +882,9 @@ def _host_set(n, clip, surface):
     if clip:
         # the matches of the pairs that have some, packed back to back by the device
         # (iamx_match_pack_results writes these page-locked buffers directly)
-        # (grows with the batch.  The closest pairs of a survey carry ~1700 matches each and a
-        #  distance-sorted schedule puts 16 384 of them into ONE round: with room for 1024 per pair
-        #  the first three rounds of the 2812-image survey overflowed into the slot-by-slot path,
-        #  0.45 s each -- tools/find_matches_rate.py --trace)
-        cap = min(n * clip, max(PACK_CAP, n * 2048))
+        # (room for every pair's `clip` matches.  The closest pairs of a survey carry ~1700 each and
+        #  a distance-sorted schedule puts 16 384 of them into ONE round)
+        cap = n * clip
         hs.update(cnt=pin(n, torch.int32), status=pin(n, torch.int32), cap=cap,
                   off=pin(n + 1, torch.int64), pk_pairs=pin((cap, 2), torch.int32))
         if surface:
@@ -896,6 +903,7 @@ def _prewarm_pools(n, rows, surface, dev, stream, sets=3):
     the bookkeeping between the schedule and the first launch; everything goes through the pools'
     own constructors, so a round that asks for another size simply allocates as before."""
     import torch
+    surface = bool(surface)                      # (the pools' keys, as _launch_batch forms them)
     clip = int(_lib.lib().iamx_match_postfilter_clip())
     with torch.cuda.device(dev), torch.cuda.stream(stream):
         host = [_host_set(n, clip, surface) for _ in range(sets)]
@@ -924,29 +932,28 @@ def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_di
     """batch: list of (i1, i2) image objects.  ENQUEUES, on the current stream, the device k=2
     NN + metric threshold for both directions of every pair, the per-pair filters (sort/clip,
     GMS, de-dup, gates, cross check: iamx_match_postfilter) unless `device_filters` is False,
-    with `surface` the DLT triangulation of every pair's matches (one launch for the batch), and
-    the downloads of the results into page-locked buffers.  Nothing is waited for: the returned
-    handle goes to _finish_batch(), and find_matches launches the next batch before it finishes
-    this one so that the GPU works while python builds the match lists."""
+    with `surface` (any true value; find_matches passes 'fit') the similarity fits between every
+    pair's matched keypoints, and the downloads of the results into page-locked buffers.  Nothing
+    is waited for: the returned handle goes to _finish_batch(), and find_matches launches the next
+    batch before it finishes this one so that the GPU works while python builds the match lists."""
     import torch
     from . import kernels
     from .kernels import _ptr, check, lib, stream_ptr
     dm = the_matcher
-    by_id = {}                                   # one slot_of() per image, not per pair
-    if isinstance(batch, _PairView):
+    surface = bool(surface)
+    if isinstance(batch, _PairView):             # (one slot_of() per image, not per pair)
         # a round of find_matches: index arrays, no tuple per pair
         slot_of = np.zeros(len(batch.image_list), np.int32)
         for u in batch.uniq.tolist():
-            im = batch.image_list[u]
-            slot_of[u] = dm.slot_of(im)
-            by_id[id(im)] = (int(slot_of[u]), im)
+            slot_of[u] = dm.slot_of(batch.image_list[u])
         slots = np.stack([slot_of[batch.pi], slot_of[batch.pj]], 1)
     else:
+        by_id = {}
         for pair in batch:
             for im in pair:
                 if id(im) not in by_id:
-                    by_id[id(im)] = (dm.slot_of(im), im)
-        slots = [(by_id[id(a)][0], by_id[id(b)][0]) for a, b in batch]
+                    by_id[id(im)] = dm.slot_of(im)
+        slots = [(by_id[id(a)], by_id[id(b)]) for a, b in batch]
     if dm._pending or dm._kp_dev is None or dm._kp_dev[0] != len(dm._counts):
         # new images: the descriptor / keypoint arenas are about to be rebuilt, and the previous
         # round's side-stream kernels may still be reading the old ones
@@ -956,28 +963,6 @@ def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_di
     store = dm.store()
     arena = _upload_arena()
     arena.begin()
-    d_proj = d_ik = None
-    if surface is True and device_filters:
-        # (every small table of the batch goes up with ONE asynchronous copy: a pageable upload
-        #  blocks the host until the previous batch's kernels have run)
-        from . import smart as _smart
-        PROJ = np.zeros((len(dm._counts), 12))
-        epoch = dm._pose_epoch
-        for s, im in by_id.values():
-            hit = dm._proj.get(s)
-            if hit is None or epoch is None or hit[2] is not epoch:
-                # (reading a pose back from the property tree costs more than a pair's share of
-                #  the kernels: once per image and find_matches call, else whenever it changed)
-                pose = im.get_camera_pose()
-                if hit is None or hit[0] != pose:
-                    hit = (pose, _smart.projection_matrix(im).ravel(), epoch)
-                else:
-                    hit = (hit[0], hit[1], epoch)
-                dm._proj[s] = hit
-            PROJ[s] = hit[1]
-        IK = np.linalg.inv(np.asarray(_deps.camera().get_K(), float))
-        d_proj = arena.put(PROJ)
-        d_ik = arena.put(np.ascontiguousarray(IK.ravel()))
     sl = np.asarray(slots, np.int32).reshape(-1, 2)
     ordered = np.concatenate([sl, sl[:, ::-1]])
     pb = kernels.PairBatch(store, ordered, sym=False if one_direction else None, arena=arena)
@@ -988,10 +973,10 @@ def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_di
     #  the ZeroDivisionError of matcher.py:255 -- would fail every later batch that draws it)
     ws.flags.zero_()
     if device_filters:
-        kp_off, xy, key2 = dm.keypoints()        # (may upload: before the kernels, like PROJ)
+        kp_off, xy, key2 = dm.keypoints()        # (may upload: before the kernels)
     thresh = max_distance * match_ratio
     # The sweep fills the machine for ~95 % of a round; everything behind it -- candidate test,
-    # exact stage, per-pair filters, triangulation, packing, the downloads -- is small, latency
+    # exact stage, per-pair filters, similarity fits, packing, the downloads -- is small, latency
     # bound work that runs on a SECOND stream beside the next round's sweep (each round has its
     # own workspace / result set from the pools, handed back only after the host has read them).
     main = torch.cuda.current_stream()
@@ -1002,14 +987,13 @@ def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_di
     swept.record(main)
     side.wait_event(swept)
     with torch.cuda.stream(side):
-        h = _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, d_proj, d_ik,
+        h = _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface,
                                kp_off if device_filters else None, xy if device_filters else None,
                                key2 if device_filters else None)
     # (the side stream reads these tables; the caching allocator knows them by the stream they were
     #  made on, so a table that outgrew the upload arena's slot -- a fresh main-stream tensor --
     #  must stay referenced until the host has seen the batch's `done` event)
-    h['tables'] = (d_proj, d_ik, kp_off if device_filters else None,
-                   xy if device_filters else None, key2 if device_filters else None)
+    h['tables'] = (kp_off, xy, key2) if device_filters else None
     return h
 
 
@@ -1026,7 +1010,7 @@ def _side_stream():
     return st
 
 
-def _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, d_proj, d_ik, kp_off, xy, key2):
+def _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, kp_off, xy, key2):
     """the part of _launch_batch() behind the sweep (enqueued on the side stream)"""
     import torch
     from .kernels import _ptr, check, lib, stream_ptr
@@ -1048,19 +1032,12 @@ def _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, d_proj, d
                                       _ptr(post['pairs']), _ptr(post['scratch']), _ptr(post['stat']),
                                       _ptr(post['status']), stream_ptr()), 'iamx_match_postfilter')
         if surface:
-            post['tri_cnt'] = post['cnt']           # (0 for the pairs left to the host filters)
-        if surface is True:
-            check(L.iamx_triangulate_pairs(_ptr(pb.d_pairs), _ptr(d_proj), _ptr(d_ik), _ptr(kp_off),
-                                           _ptr(xy), _ptr(post['tri_cnt']), _ptr(post['pairs']), n,
-                                           clip, _ptr(post['z']), stream_ptr()),
-                  'iamx_triangulate_pairs')
-        if surface:
             # the similarity between the two images' keypoints, both ways (yaw-error estimate)
             check(L.iamx_similarity_pairs(_ptr(pb.d_pairs), _ptr(kp_off), _ptr(xy),
-                                          _ptr(post['tri_cnt']), _ptr(post['pairs']), n, clip,
+                                          _ptr(post['cnt']), _ptr(post['pairs']), n, clip,
                                           _ptr(post['aff']), _ptr(post['aff_ok']), stream_ptr()),
                   'iamx_similarity_pairs')
-    hs = _host_set(n, clip, surface if post is not None else False)
+    hs = _host_set(n, clip, surface and post is not None)
     hs['zero_div'].copy_(ws.flags, non_blocking=True)
     hs['count'].copy_(ws.surv_cnt[:2 * n], non_blocking=True)
     if pb.sym and pb.rows and pb.n_pairs:
@@ -1068,11 +1045,10 @@ def _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, d_proj, d
     if post is not None:
         hs['cnt'].copy_(post['cnt'], non_blocking=True)
         hs['status'].copy_(post['status'], non_blocking=True)
-        has_z = 'z' in post
+        # (no heights to pack: the surface stage writes them into hs['pk_z'] later, _surface_device)
         check(lib().iamx_match_pack_results(_ptr(post['cnt']), _ptr(post['status']), _ptr(post['pairs']),
-                                            _ptr(post['z']) if has_z else None, n, clip, hs['cap'],
-                                            _ptr(hs['off']), _ptr(hs['pk_pairs']),
-                                            _ptr(hs['pk_z']) if has_z else None, stream_ptr()),
+                                            None, n, clip, hs['cap'], _ptr(hs['off']),
+                                            _ptr(hs['pk_pairs']), None, stream_ptr()),
               'iamx_match_pack_results')
         if 'aff' in post:
             hs['aff'].copy_(post['aff'], non_blocking=True)
@@ -1083,61 +1059,54 @@ def _launch_batch_tail(batch, pb, ws, thresh, device_filters, surface, d_proj, d
                 sym=bool(pb.sym and pb.rows and pb.n_pairs), rows=int(pb.rows))
 
 
+def _await_batch(h):
+    """What both finishers do first: wait for the batch's downloads, refuse what neither of them
+    may deliver, note the round's candidate share for the route.  Raises with the batch's
+    buffers still out: the finishers' `finally` hands them back."""
+    h['done'].synchronize()
+    hs, n = h['host'], h['n']
+    if int(hs['zero_div'][0]):
+        raise ZeroDivisionError("float division by zero")       # matcher.py:255
+    if int(hs['zero_div'][1]):
+        # (never seen: the bound forms' exact stage covers every candidate row by
+        #  construction; a .match file written past this would be silently wrong)
+        raise RuntimeError("libiamx: %d query rows left unresolved by the exact stage"
+                           % int(hs['zero_div'][1]))
+    if 'status' in hs and hs['status'].numpy().any():
+        # (never seen either: a direction with more than 2^24 survivors, and DeviceMatcher
+        #  registers no image of more than MAX_IMAGE_ROWS rows)
+        raise RuntimeError("libiamx: the filters gave up on %d of the batch's %d pairs (more than "
+                           "2^24 survivors in one direction)"
+                           % (int(np.count_nonzero(hs['status'].numpy())), n))
+    if h.get('sym'):
+        _route['share'] = float(hs['cand'].numpy()[:2 * n].sum(dtype=np.int64)) / max(h['rows'], 1)
+
+
 def _finish_batch(h):
     """Waits for the batch's results and builds the python lists of the callers' contract.
-    Returns per pair (match_fwd, match_rev, n_fwd_quality, n_rev_quality); when the batch was
-    launched with `surface` a fifth entry: the pair's ground-surface statistics
-    (avg, std, dist_m) of smart.estimate_surface_elevation(), or None where the pair took the
-    host filter path (the caller then asks smart per pair)."""
-    h['done'].synchronize()
+    Returns per pair (match_fwd, match_rev, n_fwd_quality, n_rev_quality)."""
     hs, n, ws, post = h['host'], h['n'], h['ws'], h['post']
     try:
-        if int(hs['zero_div'][0]):
-            raise ZeroDivisionError("float division by zero")       # matcher.py:255
-        if int(hs['zero_div'][1]):
-            # (never seen: the bound forms' exact stage covers every candidate row by
-            #  construction; a .match file written past this would be silently wrong)
-            raise RuntimeError("libiamx: %d query rows left unresolved by the exact stage"
-                               % int(hs['zero_div'][1]))
-        if h.get('sym'):
-            _route['share'] = float(hs['cand'].numpy()[:2 * n].sum(dtype=np.int64)) / max(h['rows'], 1)
+        _await_batch(h)
         count = hs['count'].numpy().astype(np.int64)
-        first = sq = st = sm = status = cnt = lists = None
-        z_rows = {}
+        first = sq = st = sm = cnt = lists = None
         if post is not None:
-            cnt, status = hs['cnt'].numpy(), hs['status'].numpy()
-            lists, zs = _unpacked(hs, post, n)
-            if zs is not None:
-                aff, aff_ok = hs['aff'].numpy(), hs['aff_ok'].numpy()
-                z_rows = {int(k): (zs(k),
-                                   aff[k, 0].reshape(2, 3).copy() if aff_ok[k, 0] else None,
-                                   aff[k, 1].reshape(2, 3).copy() if aff_ok[k, 1] else None)
-                          for k in np.nonzero((status == 0) & (cnt > 0))[0]}
-        if post is None or status.any():
+            cnt, lists = hs['cnt'].numpy(), _unpacked(hs)
+        else:
             # survivor arrays: only the host filter path reads them (blocking copies)
             first, count, sq, st, sm = ws.survivors(h['pb'].n_pairs)
         out = []
         with _no_gc():
-            _collect_batch(out, h['batch'], n, count, first, sq, st, sm, post is not None, status,
-                           cnt, lists, z_rows, h['surface'])
+            _collect_batch(out, h['batch'], n, count, first, sq, st, sm, post is not None, cnt, lists)
     finally:
-        _host_sets[hs['key']].append(hs)
         _recycle(h)
     return out
 
 
-def _unpacked(hs, post, n):
-    """accessors of a finished batch's packed download: (pairs_of(k) -> int32 [cnt, 2],
-    z_of(k) -> float64 [cnt] or None).  A batch with more matches than the packed buffers hold
-    has its slots copied the plain way."""
-    cnt, off = hs['cnt'].numpy(), hs['off'].numpy()
-    if int(off[n]) <= hs['cap']:
-        pk, pz = hs['pk_pairs'].numpy(), hs['pk_z'].numpy() if 'pk_z' in hs and 'z' in post else None
-        return ((lambda k: pk[off[k]:off[k] + cnt[k]]),
-                (lambda k: pz[off[k]:off[k] + cnt[k]]) if pz is not None else None)
-    full = post['pairs'].cpu().numpy()
-    fz = post['z'].cpu().numpy() if 'z' in post else None
-    return ((lambda k: full[k, :cnt[k]]), (lambda k: fz[k, :cnt[k]]) if fz is not None else None)
+def _unpacked(hs):
+    """accessor of a finished batch's packed download: pairs_of(k) -> int32 [cnt, 2]"""
+    cnt, off, pk = hs['cnt'].numpy(), hs['off'].numpy(), hs['pk_pairs'].numpy()
+    return lambda k: pk[off[k]:off[k] + cnt[k]]
 
 
 class _PairView(object):
@@ -1168,7 +1137,11 @@ class _RoundResult(object):
     fit exists; mean / std of the triangulated "down" are filled in by the surface stage.
     `src`: where the surface stage finds the match rows without another copy (the page-locked
     buffer the device packed them into, or the device buffer a gather landed in), `release`
-    hands the round's landing buffers back to their pool."""
+    hands the round's landing buffers back to their pool.
+    Invariant: the match rows are exactly those of the pairs with matches, back to back in hit
+    order -- lo[0] == 0, lo[1:] == hi[:-1], hi[-1] == len(fwd_all).  Every producer keeps it (the
+    packed download of _finish_batch_arrays, _round_from_tuples, _Part.from_wire), so the wire
+    form and the surface stage use the rows and offsets as they are."""
     __slots__ = ('n', 'n_fwd', 'n_rev', 'cc', 'quiet', 'hit_rows', 'lo', 'hi', 'fwd_all', 'rev_all',
                  'fit', 'dist', 'same', 'yv_f', 'yv_r', 'aff_ok', 'mean', 'std', 'src', 'release')
 
@@ -1227,30 +1200,6 @@ class _LazyHits(object):
         return (self._one(t) for t in range(len(self)))
 
 
-def _similarity_of_lists(view, rows, lists):
-    """similarity fits of a few pairs whose match lists were made on the host (pairs the device
-    filters handed back): [(aff [2, 6], ok [2])] through iamx_similarity_pairs"""
-    import torch
-    from .kernels import _ptr, check, lib, stream_ptr
-    dm = the_matcher
-    kp_off, xy, _k2 = dm.keypoints()
-    dev = xy.device
-    out = []
-    for k, fwd in zip(rows, lists):
-        i1, i2 = view[k]
-        pairs = np.ascontiguousarray(np.asarray(fwd, np.int32).reshape(-1, 2))
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-        aff = torch.empty((1, 2, 6), dtype=torch.float64, device=dev)
-        ok = torch.empty((1, 2), dtype=torch.int32, device=dev)
-        d_img = t(np.array([[dm.slot_of(i1), dm.slot_of(i2)]]), torch.int32)
-        d_cnt, d_pairs = t(np.array([len(pairs)]), torch.int32), t(pairs, torch.int32)
-        check(lib().iamx_similarity_pairs(_ptr(d_img), _ptr(kp_off), _ptr(xy), _ptr(d_cnt), _ptr(d_pairs),
-                                          1, max(len(pairs), 1), _ptr(aff), _ptr(ok), stream_ptr()),
-              'iamx_similarity_pairs')
-        out.append((aff[0].cpu().numpy(), ok[0].cpu().numpy()))
-    return out
-
-
 def _finish_batch_arrays(h):
     """_finish_batch() for find_matches: the same wait and the same results, but only the pairs
     that HAVE matches become python objects (and only when they are booked) -- on an all-pairs
@@ -1261,107 +1210,41 @@ def _finish_batch_arrays(h):
         #  the CPU tests of the multi-rank logic)
         return _round_from_tuples(h)
     from . import smart as _smart
-    _t0 = time.perf_counter()
-    h['done'].synchronize()
-    _t1 = time.perf_counter()
-    hs, n, ws, post = h['host'], h['n'], h['ws'], h['post']
+    hs, n = h['host'], h['n']
     R = _RoundResult(n)
     keep_host = False
     try:
-        if int(hs['zero_div'][0]):
-            raise ZeroDivisionError("float division by zero")       # matcher.py:255
-        if int(hs['zero_div'][1]):
-            # (never seen: the bound forms' exact stage covers every candidate row by
-            #  construction; a .match file written past this would be silently wrong)
-            raise RuntimeError("libiamx: %d query rows left unresolved by the exact stage"
-                               % int(hs['zero_div'][1]))
-        if h.get('sym'):
-            _route['share'] = float(hs['cand'].numpy()[:2 * n].sum(dtype=np.int64)) / max(h['rows'], 1)
+        _t0 = time.perf_counter()
+        _await_batch(h)
+        _t1 = time.perf_counter()
         count = hs['count'].numpy()
         R.n_fwd, R.n_rev = count[:n].astype(np.int64), count[n:2 * n].astype(np.int64)
-        if post is None:
+        if h['post'] is None:
             raise ValueError("find_matches runs the device filters")
-        cnt, status = hs['cnt'].numpy(), hs['status'].numpy()
-        R.cc = np.where(status == 0, cnt, 0).astype(np.int64)
-        R.quiet = (status == 0) & (cnt == 0)
-        dev_rows = np.nonzero((status == 0) & (cnt > 0))[0]
-        host_rows = np.nonzero(status != 0)[0]
+        cnt, off = hs['cnt'].numpy(), hs['off'].numpy()
+        R.cc = cnt.astype(np.int64)
+        R.quiet = cnt == 0
+        dev_rows = np.nonzero(cnt > 0)[0]
         R.fit = bool(h['surface']) and 'aff' in hs
         view = h['batch']
-        off_h = hs['off'].numpy()
-        packed = int(off_h[n]) <= hs['cap']
         _hp = lambda a_: a_.ctypes.data_as(ctypes.c_void_p)
-        c = cnt[dev_rows].astype(np.int64)
-        if len(dev_rows) and packed:
+        lo = off[dev_rows].astype(np.int64)
+        R.hit_rows, R.lo, R.hi = dev_rows.astype(np.int64), lo, lo + cnt[dev_rows]
+        if len(dev_rows):
             # the round's pair rows, forward and reversed, as TWO arrays the match lists are views
             # of (the download is a pinned buffer the next round reuses: copied once, one threaded
             # pass writes the copy and its column-swapped twin)
-            src = hs['pk_pairs'].numpy()[:int(off_h[n])]
+            src = hs['pk_pairs'].numpy()[:int(off[n])]
             R.fwd_all, R.rev_all = empty_huge(src.shape, np.int32), empty_huge(src.shape, np.int32)
             _lib.check(_lib.lib().iamx_pairs_fwd_rev(_hp(src), len(src), _hp(R.fwd_all), _hp(R.rev_all),
                                                      _HOST_THREADS), 'iamx_pairs_fwd_rev')
-            lo = off_h[dev_rows].astype(np.int64)
             if R.fit:
                 # (the surface stage reads the rows where the device packed them and writes the
                 #  triangulated heights beside them: the landing buffers stay out of the pool
                 #  until R.done())
-                R.src = dict(kind='pinned', pairs=hs['pk_pairs'], z=hs['pk_z'], total=int(off_h[n]))
-                keep_host = True
-        elif len(dev_rows):
-            # a batch whose matches did not fit the packed download: the slots, copied plainly
-            full = post['pairs'].cpu().numpy()
-            R.fwd_all = np.concatenate([full[k, :cnt[k]] for k in dev_rows.tolist()])
-            R.rev_all = np.ascontiguousarray(R.fwd_all[:, ::-1])
-            lo = np.concatenate([[0], np.cumsum(c)[:-1]]).astype(np.int64)
-        else:
-            lo = np.zeros(0, np.int64)
-        R.hit_rows, R.lo, R.hi = dev_rows.astype(np.int64), lo, lo + c
+                R.src = dict(kind='pinned', pairs=hs['pk_pairs'], z=hs['pk_z'], total=int(off[n]))
         aff = hs['aff'].numpy()[dev_rows] if R.fit else None
         aff_ok = hs['aff_ok'].numpy()[dev_rows] if R.fit else None
-        if len(host_rows):
-            # pairs the device filters handed back (more candidates than their buffers hold):
-            # the host filters, per pair, as before; their rows go behind the packed ones
-            first, count_s, sq, st, sm = ws.survivors(h['pb'].n_pairs)
-            extra_rows, extra = [], []
-            for k in host_rows.tolist():
-                i1, i2 = view[k]
-                _ensure_features(i1)
-                _ensure_features(i2)
-                xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
-                a, b = first[k], first[k] + count_s[k]
-                fwd = _post_filter(i1, i2, _threshold_sort_clip(sq[a:b], st[a:b], sm[a:b]), (xy1, xy2))
-                rev = []
-                if len(fwd) >= min_pairs:
-                    a, b = first[n + k], first[n + k] + count_s[n + k]
-                    rev = _post_filter(i2, i1, _threshold_sort_clip(sq[a:b], st[a:b], sm[a:b]),
-                                       (xy2, xy1))
-                fwd, rev = filter_cross_check(fwd, rev)
-                R.cc[k] = len(fwd)
-                if len(fwd) == 0 and len(rev) == 0:
-                    R.quiet[k] = True
-                else:
-                    extra_rows.append(k)
-                    extra.append(np.asarray(fwd, np.int32).reshape(-1, 2))
-            if extra_rows:
-                base = len(R.fwd_all)
-                R.fwd_all = np.concatenate([R.fwd_all] + extra)
-                R.rev_all = np.ascontiguousarray(R.fwd_all[:, ::-1])
-                ec = np.array([len(e) for e in extra], np.int64)
-                elo = base + np.concatenate([[0], np.cumsum(ec)[:-1]]).astype(np.int64)
-                rows_all = np.concatenate([R.hit_rows, np.array(extra_rows, np.int64)])
-                lo_all, hi_all = np.concatenate([R.lo, elo]), np.concatenate([R.hi, elo + ec])
-                if R.fit:
-                    fits = _similarity_of_lists(view, extra_rows, extra)
-                    aff = np.concatenate([aff, np.stack([f[0] for f in fits])])
-                    aff_ok = np.concatenate([aff_ok, np.stack([f[1] for f in fits])])
-                order = np.argsort(rows_all, kind='stable')
-                R.hit_rows, R.lo, R.hi = rows_all[order], lo_all[order], hi_all[order]
-                if R.fit:
-                    aff, aff_ok = aff[order], aff_ok[order]
-                if R.src is not None:
-                    # (the device-packed rows no longer cover every pair with matches: the surface
-                    #  stage uploads the round's rows instead)
-                    R.src = None
         if R.fit and len(R.hit_rows):
             ned, air_yaw = _smart.frozen_ned(view.image_list, with_yaw=True)
             a_idx, b_idx = view.pi[R.hit_rows], view.pj[R.hit_rows]
@@ -1378,13 +1261,11 @@ def _finish_batch_arrays(h):
             R.dist, R.same = np.zeros(0), np.zeros(0, bool)
             R.yv_f = R.yv_r = np.zeros((0, 4))
             R.aff_ok = np.zeros((0, 2), bool)
+        keep_host = R.src is not None
     finally:
-        if keep_host and R.src is not None:
-            R.release = lambda hs_=hs: _host_sets[hs_['key']].append(hs_)
-        else:
-            R.src = None
-            _host_sets[hs['key']].append(hs)
-        _recycle(h)
+        _recycle(h, keep_host)
+    if keep_host:
+        R.release = lambda: _host_sets[hs['key']].append(hs)
     if _round_trace is not None:        # (tools/find_matches_rate.py --trace)
         _round_trace.append(('finish', _t1 - _t0, time.perf_counter() - _t1, len(R.hit_rows)))
     return R
@@ -1443,25 +1324,15 @@ _NO_MATCHES = _Empty()
 _NO_SURFACE = (None, None, 0.0, None, None)      # nothing to record (smart.py:200-201)
 
 
-def _collect_batch(out, batch, n, count, first, sq, st, sm, have_post, status, cnt, lists, z_rows,
-                   surface):
+def _collect_batch(out, batch, n, count, first, sq, st, sm, have_post, cnt, lists):
     """host side of a batch: the per-pair python lists the callers' contract asks for"""
-    from . import smart as _smart
     count = count.tolist()
-    quiet = None
-    if have_post:
-        # pairs the device filters finished with nothing left (most pairs of an all-pairs
-        # schedule): one shared result, no per-pair work beyond the counts of the log
-        quiet = ((status == 0) & (cnt == 0)).tolist()
     for k in range(n):
         n_fwd, n_rev = count[k], count[n + k]
-        if quiet is not None and quiet[k]:
-            out.append((_NO_MATCHES, _NO_MATCHES, n_fwd, n_rev, _NO_SURFACE) if surface
-                       else (_NO_MATCHES, _NO_MATCHES, n_fwd, n_rev))
-            continue
-        if have_post and status[k] == 0:
+        if have_post:
             # array-backed lists (matchpairs.py): `lists` is a page-locked buffer that the next
-            # batch reuses, the pair's rows are copied out of it once
+            # batch reuses, the pair's rows are copied out of it once.  Pairs the device filters
+            # finished with nothing left (most pairs of an all-pairs schedule) share one result.
             c = cnt[k]
             if c:
                 both = np.empty((2, c, 2), np.int32)
@@ -1469,7 +1340,7 @@ def _collect_batch(out, batch, n, count, first, sq, st, sm, have_post, status, c
                 both[1] = both[0, :, ::-1]
                 fwd, rev = MatchPairs(both[0]), MatchPairs(both[1])
             else:
-                fwd, rev = [], []
+                fwd = rev = _NO_MATCHES
         else:
             i1, i2 = batch[k]
             _ensure_features(i1)         # the keypoints may have been flushed since the launch
@@ -1483,18 +1354,7 @@ def _collect_batch(out, batch, n, count, first, sq, st, sm, have_post, status, c
                 rev = _post_filter(i2, i1, _threshold_sort_clip(sq[a:b], st[a:b], sm[a:b]),
                                    (xy2, xy1))
             fwd, rev = filter_cross_check(fwd, rev)
-        if not surface:
-            out.append((fwd, rev, n_fwd, n_rev))
-            continue
-        surf = None
-        if have_post and status[k] == 0:
-            i1, i2 = batch[k]
-            if i1 == i2 or k not in z_rows:
-                surf = _NO_SURFACE
-            else:
-                zk, aff_fwd, aff_rev = z_rows[k]
-                surf = (-np.average(zk), np.std(zk), _smart._pair_distance(i1, i2), aff_fwd, aff_rev)
-        out.append((fwd, rev, n_fwd, n_rev, surf))
+        out.append((fwd, rev, n_fwd, n_rev))
 
 
 def _camera_size():
@@ -1510,41 +1370,6 @@ def _camera_size():
     return w, h
 
 
-def _launch_lines(lines, match_ratio, surface=False, raw=None):
-    """lines: [(dist, i, j, i1, i2)]: enqueue the batch (see _launch_batch); raw: the descriptor
-    row counts of every line's two images when the caller already has them"""
-    batch = [(l[3], l[4]) for l in lines]
-    if raw is None:
-        raw = [(_rows_of(l[3]), _rows_of(l[4])) for l in lines]
-    handle = _launch_batch(batch, match_ratio, surface=True) if surface \
-        else _launch_batch(batch, match_ratio)
-    return lines, raw, handle
-
-
-def _finish_lines(launched):
-    """Returns [(i, j, match_fwd, match_rev, surf)]; surf is the pair's (avg, std, dist_m)
-    surface statistics when the launch asked for them, else None."""
-    lines, raw, handle = launched
-    results = _finish_batch(handle)
-    out, records = [], []
-    for (dist, i, j, i1, i2), (raw1, raw2), res in zip(lines, raw, results):
-        match_fwd, match_rev, n_fwd, n_rev = res[:4]
-        # the reference's seven qlog() lines per pair (matcher.py:311-343), one log record per
-        # batch: at millions of pairs the per-line bookkeeping costs more than the GPU work
-        records.append("Matching %s vs %s\n  separation (approx) = %.0f (m)\n  raw matches: %d\n"
-                       "  quality matches: %d\n  raw matches: %d\n  quality matches: %d\n"
-                       "  cross checked matches: %d"
-                       % (i1.name, i2.name, dist, raw1, n_fwd, raw2, n_rev, len(match_fwd)))
-        out.append((i, j, match_fwd, match_rev, res[4] if len(res) > 4 else None))
-    if records:
-        _qlog("\n".join(records))
-    return out
-
-
-def _process_batch(lines, match_ratio, surface=False):
-    return _finish_lines(_launch_lines(lines, match_ratio, surface))
-
-
 def find_matches(proj, K, strategy="smart", transform="homography", sort=False, review=False):
     """transform / review are accepted and unused, as on the reference's live path.
 
@@ -1557,8 +1382,6 @@ def find_matches(proj, K, strategy="smart", transform="homography", sort=False, 
         try:
             _find_matches(proj, K, strategy, transform, sort, review)
         finally:
-            if isinstance(the_matcher, DeviceMatcher):
-                the_matcher._pose_epoch = None
             if _deps.smart() is not None:
                 _deps.smart().freeze_poses(False)
 
@@ -1570,8 +1393,6 @@ def _find_matches(proj, K, strategy, transform, sort, review):
         quit()
     if the_matcher is None:
         configure()
-    if isinstance(the_matcher, DeviceMatcher):
-        the_matcher._pose_epoch = object()
     _route_reset()
     smart = _deps.smart()
     if smart is not None:
@@ -1607,20 +1428,13 @@ class _Part(object):
         h = len(R.hit_rows)
         z1, z4, z2 = np.zeros(h), np.zeros((h, 4)), np.zeros((h, 2), bool)
         fit = R.fit and R.dist is not None
-        # (only the rows of pairs with matches, back to back in hit order)
-        if h and not (R.lo[0] == 0 and np.array_equal(R.lo[1:], R.hi[:-1]) and R.hi[-1] == len(R.fwd_all)):
-            fwd = np.concatenate([R.fwd_all[a:b] for a, b in zip(R.lo.tolist(), R.hi.tolist())])
-            c = R.hi - R.lo
-            lo = np.concatenate([[0], np.cumsum(c)[:-1]]).astype(np.int64)
-            hi = lo + c
-        else:
-            fwd, lo, hi = R.fwd_all, R.lo, R.hi
+        # (fwd_all: only the rows of pairs with matches, back to back in hit order -- _RoundResult)
         return _dist.pack_arrays([
             np.asarray(self.seq, np.int64), np.asarray(self.pi, np.int32), np.asarray(self.pj, np.int32),
             np.asarray(self.dist, np.float64), np.asarray(self.raw1, np.int64), np.asarray(self.raw2, np.int64),
             np.asarray(R.n_fwd, np.int64), np.asarray(R.n_rev, np.int64), np.asarray(R.cc, np.int64),
-            np.asarray(R.quiet, bool), np.asarray(R.hit_rows, np.int64), np.asarray(lo, np.int64),
-            np.asarray(hi, np.int64), np.ascontiguousarray(fwd, np.int32).reshape(-1, 2),
+            np.asarray(R.quiet, bool), np.asarray(R.hit_rows, np.int64), np.asarray(R.lo, np.int64),
+            np.asarray(R.hi, np.int64), np.ascontiguousarray(R.fwd_all, np.int32).reshape(-1, 2),
             np.array([bool(R.fit)]), np.asarray(R.dist if fit else z1, np.float64),
             np.asarray(R.same if fit else np.zeros(h, bool), bool),
             np.asarray(R.yv_f if fit else z4, np.float64).reshape(h, 4),
@@ -2139,21 +1953,11 @@ class _MatchRun(object):
                 mine = np.nonzero(part_of == k)[0]            # ascending hit_t: the part's hit order
                 if not len(mine):
                     continue
-                lo, hi2 = R.lo, R.hi
-                contiguous = bool(np.array_equal(lo[1:], hi2[:-1]))
-                src = R.src if contiguous else None
-                if contiguous:
-                    base = int(lo[0]) if src is None else 0
-                    m_off = np.concatenate([lo, hi2[-1:]]).astype(np.int64) - base
-                    if src is not None and src['kind'] == 'pinned':
-                        m_off[-1] = int(hi2[-1])              # (the packed buffer: offsets as they are)
-                    pairs = R.fwd_all[int(lo[0]):int(hi2[-1])] if src is None else None
-                else:
-                    c = hi2 - lo
-                    m_off = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
-                    pairs = np.concatenate([R.fwd_all[a:b] for a, b in zip(lo.tolist(), hi2.tolist())])
+                # (the part's match rows and offsets as they are -- _RoundResult's invariant --, read
+                #  where R.src says they already lie, else uploaded from fwd_all)
+                m_off = np.concatenate([R.lo, R.hi[-1:]]).astype(np.int64)
                 jobs.append(dict(pi=hi_[mine], pj=hj_[mine], proj=proj[mine], m_off=m_off,
-                                 pairs=pairs, src=src))
+                                 pairs=R.fwd_all if R.src is None else None, src=R.src))
                 where.append((k, m_off))
             zs = _surface_device(self.image_list, jobs, waiter=self.drain_until)
             for (k, m_off), z in zip(where, zs):

@@ -17,8 +17,9 @@ module around it.
     set_yaw_error_estimates(proj)       smart.py:326-331  process.py:240
 
 The triangulation and the similarity fit run on the GPU (csrc/triangulate.hip:
-iamx_triangulate_pairs, iamx_similarity_pairs; find_matches does a whole batch of pairs in one
-launch each and hands the results to record_surface_estimate / record_yaw_error_estimate).
+iamx_triangulate_pairs for one pair, iamx_similarity_pairs).  find_matches fits a whole batch of
+pairs in one launch, triangulates a round's pairs in another (iamx_triangulate_packed: every pair
+with the two poses the feedback has reached, PoseFeedback) and records them through record_round.
 The reference obtains the matrix from cv2.estimateAffinePartial2D (RANSAC); here it is a
 deterministic robust fit (least squares, then re-fits on the matches within 200, 50, 10, 3, ...
 px), so yaw estimates agree with the reference's to the extent the two fits do (both see

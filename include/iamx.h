@@ -322,7 +322,8 @@ int iamx_knn2sym_exact(const int8_t *desc, const int32_t *norm_q, const int32_t 
  *   [query row, train row] (the reverse list is its mirror); scratch DEV [n_pairs][2][clip][2];
  *   out_stat DEV [n_pairs][4]: forward after GMS / after de-dup, reverse after GMS / after
  *   de-dup (-1 = stage not reached); status DEV [n_pairs]: 1 = a direction has more than 2^24
- *   survivors and must take the host path.  clip = iamx_match_postfilter_clip() = 2000.
+ *   survivors (out_cnt 0): the caller refuses the batch -- an image of at most 2^24 rows
+ *   cannot cause it.  clip = iamx_match_postfilter_clip() = 2000.
  * ------------------------------------------------------------------------------------ */
 int iamx_match_postfilter_clip(void);
 /* The per-pair results of a batch packed back to back (what find_matches downloads: on an

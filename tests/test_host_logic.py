@@ -813,3 +813,55 @@ def test_device_memory_model_of_the_matching_stage():
     small = matcher.device_memory_model(128, 38000)
     assert small['workspace_bytes_each'] == m['workspace_bytes_each'] or small['pairs_per_batch'] >= m['pairs_per_batch']
     assert small['arena_bytes'] < 1.6e9
+
+
+def test_device_matcher_refuses_an_image_of_more_than_2_to_24_rows():
+    """what the single-image packers and the filter kernel's survivor lists assume is an invariant
+    of the matcher: no image of more than 1 << 24 descriptor rows is registered, and a refusal
+    leaves the matcher as it was (the views below take no memory)"""
+    from types import SimpleNamespace
+    from imageanalysis_amd import matcher
+    rows = lambda n: np.broadcast_to(np.zeros((1, 128), np.uint8), (n, 128))
+    dm = matcher.DeviceMatcher()
+    big = SimpleNamespace(name='big', des_list=rows((1 << 24) + 1), kp_list=[])
+    with pytest.raises(ValueError, match=r'big.*16777216'):
+        dm.slot_of(big)
+    with pytest.raises(ValueError, match=r'big.*16777216'):
+        dm.adopt('big', big.des_list, np.zeros((0, 2), np.float32))
+    assert dm._counts == [] and dm._pending == [] and dm._slots == {}
+    assert dm._adopted == {} and dm._kp == {}
+    full = SimpleNamespace(name='full', des_list=rows(1 << 24), kp_list=[])
+    assert dm.slot_of(full) == 0
+    assert dm.adopt('full2', full.des_list, np.zeros((0, 2), np.float32)) == 1
+    assert dm._counts == [1 << 24, 1 << 24] and dm._slots == {'full': (0, 1 << 24), 'full2': (1, 1 << 24)}
+
+
+def test_finishers_refuse_a_batch_the_filters_gave_up_on(monkeypatch):
+    """a nonzero filter status (a direction with more than 2^24 survivors: no registered image can
+    cause it) is an error of the batch in both finishers, like the `unresolved` flag, and the
+    landing buffers go back to their pool as on the other error exits"""
+    import torch
+    from imageanalysis_amd import matcher
+    real_empty = torch.empty                     # (page-locked memory needs a device: plain here)
+    monkeypatch.setattr(torch, 'empty', lambda *a, pin_memory=False, **kw: real_empty(*a, **kw))
+    monkeypatch.setattr(matcher, '_host_sets', {})
+
+    class Done(object):
+        def synchronize(self):
+            pass
+    n, clip = 3, 4
+    for finish in (matcher._finish_batch, matcher._finish_batch_arrays):
+        hs = matcher._host_set(n, clip, False)
+        for name in ('zero_div', 'count', 'cand', 'cnt', 'status', 'off'):
+            hs[name].zero_()
+        hs['status'][1] = 1
+        assert matcher._host_sets[hs['key']] == []
+        h = dict(batch=[(None, None)] * n, n=n, ws=None, pb=None, post={}, host=hs, done=Done(),
+                 surface=False, sym=False, rows=0)
+        with pytest.raises(RuntimeError, match=r'1 of the batch\'s 3 pairs'):
+            finish(h)
+        assert len(matcher._host_sets[hs['key']]) == 1 and matcher._host_sets[hs['key']][0] is hs
+    hs['status'].zero_()                         # the same handle without the status: delivered
+    h = dict(batch=[(None, None)] * n, n=n, ws=None, pb=None, post={}, host=matcher._host_set(n, clip, False),
+             done=Done(), surface=False, sym=False, rows=0)
+    assert matcher._finish_batch(h) == [([], [], 0, 0)] * n
