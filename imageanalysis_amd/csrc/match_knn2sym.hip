@@ -37,6 +37,7 @@
 // 5.2 VALU per MFMA (round 3; before: 8 waves x 4 blocks at two waves per SIMD, 6.4 per MFMA).
 // Forms 1 / 0 (512 / 256 rows per workgroup): 4 waves x 4 / 2 blocks, two waves per SIMD.
 #include "iamx_common.h"
+#include "sym_cand_rule.h"
 
 namespace {
 
@@ -1156,8 +1157,9 @@ struct CandArgs {
     const int64_t *col_off, *rowp_off, *out_off;
     const int32_t *col, *rowp;
     double thresh;
+    double K;                    // sym_cand_K(thresh), of the reject in front of the rule (sym_cand_rule.h)
     uint8_t *keep;
-    int32_t *cand_cnt;
+    int32_t *cand_cnt;           // [n_pairs]: cleared with the keep map, counted by pass 1
     int32_t *cand_q;
     int32_t *task_total;         // [2] wave tasks / workgroup tasks appended so far (zeroed by symcompact_kernel)
     int32_t *tasks;              // [..][2] (ordered pair, block): wave tasks from entry 0, workgroup tasks from entry n_pairs
@@ -1170,69 +1172,144 @@ struct CandArgs {
     int n_pairs, wgrows;
 };
 
-// pass 1, one thread per query row of every ordered pair (grid: 256-row chunks of the largest
-// query image x ordered pairs): bounds -> candidate flag at the row's original position, the upper
-// bound of its second distance, its class mask.
-__device__ __forceinline__ void symcand_rows_pair(const CandArgs &A, int p, int pos)
+// pass 1, one thread per FOUR consecutive sorted query rows of every ordered pair (grid: 1024-row
+// chunks of the largest query image x ordered pairs): bounds -> candidate flag at the row's original
+// position, the upper bound of its second distance, its class mask, the pair's candidate count.
+// Shaped for rows that are thrown away (about 0.1 % of the rows of a survey launch are candidates,
+// and the kernel runs beside the next launch's sweep, which is bound by vector issue slots: every
+// vector instruction here is taken from it): every load is 16 bytes per lane and all of them are
+// issued before the first is unpacked, the decision is sym_cand_reject (two f64 products) with the
+// rule's own roots and division behind it for the rows it lets through, and everything a candidate
+// alone needs -- sperm, colmask, the second walk over the partials, the stores -- is under its flag.
+constexpr int CAND_ROWS = 4;             // rows of a thread (CHUNK is a multiple: a thread's rows end inside cap)
+
+// the four rows' partials of NW workgroups merged into (L, U1, U2) -- the merge of the sorted pairs
+// (U1, U2) and (e1, e2) -- with the 2 NW loads in front of the first unpack
+template <int NW>
+__device__ __forceinline__ void cand_merge_partials(const int32_t *__restrict__ rowq, int64_t cap, int (&L)[CAND_ROWS],
+                                                    int (&U1)[CAND_ROWS], int (&U2)[CAND_ROWS])
 {
-    const int qimg = A.pairs[2 * p];
-    const int u = A.osrc[2 * p], role = A.osrc[2 * p + 1];
-    const int soff = A.img_off[qimg], n = A.img_n[qimg];
-    if (pos >= n) return;
-    const int cap = (n + CHUNK - 1) / CHUNK * CHUNK;
-    const int nwg = A.wg_off[u + 1] - A.wg_off[u];
-    const int64_t ob = A.out_off[p];
-    const int32_t *rowq = A.rowp + 2 * A.rowp_off[u];
+    v4i e[NW][2];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        e[w][0] = *reinterpret_cast<const v4i *>(rowq + 2 * (w * cap));
+        e[w][1] = *reinterpret_cast<const v4i *>(rowq + 2 * (w * cap) + 4);
+    }
+#pragma unroll
+    for (int w = 0; w < NW; ++w)
+#pragma unroll
+        for (int i = 0; i < CAND_ROWS; ++i) {
+            int eL, e1, e2;
+            unpack_row_bounds(v2i{e[w][i >> 1][2 * (i & 1)], e[w][i >> 1][2 * (i & 1) + 1]}, eL, e1, e2);
+            L[i] = min(L[i], eL);
+            const int n1 = min(U1[i], e1);
+            U2[i] = min(max(U1[i], e1), min(U2[i], e2));
+            U1[i] = n1;
+        }
+}
+
+__device__ __forceinline__ void symcand_rows_pair(const CandArgs &A, int p, int pos0)
+{
+    // per-pair constants: one value for the whole workgroup, kept in scalar registers
+    const int qimg = uniform32(A.pairs[2 * p]);
+    const int u = uniform32(A.osrc[2 * p]), role = uniform32(A.osrc[2 * p + 1]);
+    const int soff = uniform32(A.img_off[qimg]), n = uniform32(A.img_n[qimg]);
+    if ((int)blockIdx.x * (256 * CAND_ROWS) >= n) return;
+    const bool in = pos0 < n;                       // (a thread past the image loads nothing)
+    const int64_t cap = (n + CHUNK - 1) / CHUNK * CHUNK;
+    const int nwg = uniform32(A.wg_off[u + 1]) - uniform32(A.wg_off[u]);
+    const int64_t ob = uniform64(A.out_off[p]);
+    const int64_t cb = uniform64(A.col_off[u]);
+    const int32_t *rowq = A.rowp + 2 * uniform64(A.rowp_off[u]);
+    int U2[CAND_ROWS];
+    long long Lb[CAND_ROWS], Ub[CAND_ROWS];
+    // (pos0 is a multiple of 4, the image's first sorted row, col_off and rowp_off multiples of
+    //  CHUNK: every vector load below is 16-byte aligned and ends at or before row cap - 1)
+    v4i n2 = {0, 0, 0, 0};
+    if (in) n2 = *reinterpret_cast<const v4i *>(A.sn2 + soff + pos0);
+    if (role == 0) {
+        v4i c[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        if (in) {
+            c[0] = *reinterpret_cast<const v4i *>(A.col + 2 * (cb + pos0));
+            c[1] = *reinterpret_cast<const v4i *>(A.col + 2 * (cb + pos0) + 4);
+        }
+#pragma unroll
+        for (int i = 0; i < CAND_ROWS; ++i) {
+            const int par = n2[i] & 1;
+            const long long cq = n2[i] >> 1;
+            U2[i] = 0x7FFFFFFF;
+            Lb[i] = 2 * (c[i >> 1][2 * (i & 1)] + cq) + par;
+            Ub[i] = 2 * (c[i >> 1][2 * (i & 1) + 1] + cq) + par + 1;
+        }
+    } else {
+        int L[CAND_ROWS], U1[CAND_ROWS];
+#pragma unroll
+        for (int i = 0; i < CAND_ROWS; ++i) L[i] = U1[i] = U2[i] = 0x7FFFFFFF;
+        if (in) {
+            const int32_t *rq = rowq + 2 * pos0;
+            switch (nwg) {                          // (1024-row workgroups: 4 for a 4096-row image)
+            case 1: cand_merge_partials<1>(rq, cap, L, U1, U2); break;
+            case 2: cand_merge_partials<2>(rq, cap, L, U1, U2); break;
+            case 3: cand_merge_partials<3>(rq, cap, L, U1, U2); break;
+            case 4: cand_merge_partials<4>(rq, cap, L, U1, U2); break;
+            default: {
+                int w = 0;
+                for (; w + 4 <= nwg; w += 4) cand_merge_partials<4>(rq + 2 * (w * cap), cap, L, U1, U2);
+                for (; w < nwg; ++w) cand_merge_partials<1>(rq + 2 * (w * cap), cap, L, U1, U2);
+            }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < CAND_ROWS; ++i) {
+            const int par = n2[i] & 1;
+            Lb[i] = 2ll * L[i] + par;
+            Ub[i] = 2ll * U2[i] + par + 1;
+        }
+    }
+    unsigned kbits = 0u;
+#pragma unroll
+    for (int i = 0; i < CAND_ROWS; ++i) {
+        if (Lb[i] < 0) Lb[i] = 0;
+        if (pos0 + i < n && !sym_cand_reject(Lb[i], Ub[i], A.K) && sym_cand_keep(Lb[i], Ub[i], A.thresh))
+            kbits |= 1u << i;
+    }
+    // ---- candidates only (none in nearly every wave of a survey launch)
+    if (kbits == 0u) return;
+    // the pair's candidate count: one add per wave that holds a candidate
+    const unsigned long long holders = __ballot(1);
+    int wave_cnt = 0;
+#pragma unroll
+    for (int i = 0; i < CAND_ROWS; ++i) wave_cnt += __popcll(__ballot((kbits >> i) & 1u));
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)holders) - 1) atomicAdd(A.cand_cnt + p, wave_cnt);
     // narrow exact stage: classes of this ordered pair's train image (8 groups of the streamed image
     // when the query was a B row, the nwg row blocks of the register-resident image otherwise)
     const int ncls = role == 0 ? 8 : nwg;
     const bool nar_ok = A.nar != nullptr && A.img_n[A.pairs[2 * p + 1]] >= NAR_MIN_TRAIN && ncls <= 64;
-    const int n2 = A.sn2[soff + pos], par = n2 & 1;
-    long long Lb, Ub;
-    int U2 = 0x7FFFFFFF;
-    if (role == 0) {
-        const v2i v = *reinterpret_cast<const v2i *>(A.col + 2 * (A.col_off[u] + pos));
-        const long long cq = n2 >> 1;
-        Lb = 2 * (v.x + cq) + par;
-        Ub = 2 * (v.y + cq) + par + 1;
-    } else {
-        int L = 0x7FFFFFFF, U1 = 0x7FFFFFFF;
-        for (int w = 0; w < nwg; ++w) {
-            int eL, e1, e2;
-            unpack_row_bounds(*reinterpret_cast<const v2i *>(rowq + 2 * ((int64_t)w * cap + pos)), eL, e1, e2);
-            L = min(L, eL);
-            // merge the sorted pairs (U1, U2) and (e1, e2)
-            const int n1 = min(U1, e1);
-            U2 = min(max(U1, e1), min(U2, e2));
-            U1 = n1;
+#pragma unroll
+    for (int i = 0; i < CAND_ROWS; ++i) {
+        if (!((kbits >> i) & 1u)) continue;
+        const int pos = pos0 + i;
+        const int orig = A.sperm[soff + pos];
+        // the flag at the row's ORIGINAL position, one bit per row in a map cleared by the launch (a byte
+        // per row until round 6: 33 M scattered byte writes per launch of 4096 synthetic pairs were most of
+        // this kernel's time; now only the candidates write)
+        atomicOr(reinterpret_cast<unsigned *>(A.keep) + ((ob + orig) >> 5), 1u << ((ob + orig) & 31));
+        // what the exact stage prunes its scan with: no row farther than this can be the best or
+        // the second of the candidate (replaced by the exact pair of distances there)
+        A.d2[2 * (ob + orig) + 1] = (int)(Ub[i] < 0x7FFFFFFFll ? Ub[i] : 0x7FFFFFFFll);
+        if (nar_ok) {
+            // the classes that can hold a row at or below Ub (every other row is farther than the
+            // exact second distance): group minimum <= v2, block lower bound <= U2
+            unsigned long long mk = 0ull;
+            if (role == 0) {
+                mk = A.colmask[cb + pos];
+            } else {
+                for (int w = 0; w < nwg; ++w)
+                    if (rowq[2 * (w * cap + pos)] <= U2[i]) mk |= 1ull << w;
+            }
+            const NarLayout NL = narrow_layout(A.rows_total, A.n_pairs);
+            reinterpret_cast<unsigned long long *>(A.nar + NL.mask)[ob + orig] = mk;
         }
-        Lb = 2ll * L + par;
-        Ub = 2ll * U2 + par + 1;
-    }
-    if (Lb < 0) Lb = 0;
-    const float f0 = (float)sqrt((double)Lb);
-    const float f1 = (float)sqrt((double)Ub);
-    const bool k = f1 == 0.0f || (double)f0 * ((double)f0 / (double)f1) < A.thresh;
-    const int orig = A.sperm[soff + pos];
-    // the flag at the row's ORIGINAL position, one bit per row in a map cleared by the launch (a byte
-    // per row until round 6: 33 M scattered byte writes per launch of 4096 synthetic pairs were most of
-    // this kernel's time; now only the candidates write)
-    if (k) atomicOr(reinterpret_cast<unsigned *>(A.keep) + ((ob + orig) >> 5), 1u << ((ob + orig) & 31));
-    // what the exact stage prunes its scan with: no row farther than this can be the best or
-    // the second of the candidate (replaced by the exact pair of distances there)
-    if (k) A.d2[2 * (ob + orig) + 1] = (int)(Ub < 0x7FFFFFFFll ? Ub : 0x7FFFFFFFll);
-    if (k && nar_ok) {
-        // the classes that can hold a row at or below Ub (every other row is farther than the
-        // exact second distance): group minimum <= v2, block lower bound <= U2
-        unsigned long long mk = 0ull;
-        if (role == 0) {
-            mk = A.colmask[A.col_off[u] + pos];
-        } else {
-            for (int w = 0; w < nwg; ++w)
-                if (rowq[2 * ((int64_t)w * cap + pos)] <= U2) mk |= 1ull << w;
-        }
-        const NarLayout NL = narrow_layout(A.rows_total, A.n_pairs);
-        reinterpret_cast<unsigned long long *>(A.nar + NL.mask)[ob + orig] = mk;
     }
 }
 
@@ -1242,8 +1319,15 @@ __global__ __launch_bounds__(256) void symcand_rows_kernel(CandArgs A)
     //  units -- every workgroup of this grid waits for a unit to come free; 131 k small ones per
     //  launch of 4096 synthetic pairs cost the sweep more than the kernel's own work)
     for (int p = blockIdx.y; p < A.n_pairs; p += gridDim.y)
-#pragma unroll 1
-        for (int k = 0; k < 4; ++k) symcand_rows_pair(A, p, (blockIdx.x * 4 + k) * 256 + threadIdx.x);
+        symcand_rows_pair(A, p, ((int)blockIdx.x * 256 + (int)threadIdx.x) * CAND_ROWS);
+}
+
+// words [0, n_words) of the keep map and the candidate counts of the pairs, cleared in one launch
+__global__ __launch_bounds__(256) void symcand_clear_kernel(unsigned *keep, int64_t n_words, int32_t *cand_cnt, int n_pairs)
+{
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_words; i += stride) keep[i] = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_pairs; i += stride) cand_cnt[i] = 0;
 }
 
 // passes 2 and 3, one workgroup per ordered pair
@@ -1252,31 +1336,58 @@ __global__ __launch_bounds__(256) void symcand_kernel(CandArgs A)
     __shared__ int wcnt[4];
     __shared__ int s_base;
     const int p = blockIdx.x;
+    const NarLayout NL = narrow_layout(A.rows_total, A.n_pairs);
+    // a pair without a candidate (pass 1 counted them; nearly every pair of a survey launch) costs
+    // this one load: no scan of the bit map, no barrier
+    if (A.cand_cnt[p] == 0) {
+        if (threadIdx.x == 0) {
+            A.cand_cnt[p] = 0;
+            if (A.nar != nullptr) reinterpret_cast<int32_t *>(A.nar + NL.pair_base)[p] = -1;
+        }
+        return;
+    }
     const int qimg = A.pairs[2 * p];
     const int u = A.osrc[2 * p], role = A.osrc[2 * p + 1];
     const int n = A.img_n[qimg];
     const int nwg = A.wg_off[u + 1] - A.wg_off[u];
     const int64_t ob = A.out_off[p];
-    const NarLayout NL = narrow_layout(A.rows_total, A.n_pairs);
     const int ncls = role == 0 ? 8 : nwg;
     const bool nar_ok = A.nar != nullptr && A.img_n[A.pairs[2 * p + 1]] >= NAR_MIN_TRAIN && ncls <= 64;
     unsigned long long *maskv = reinterpret_cast<unsigned long long *>(A.nar + NL.mask);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    // the flagged rows by WORDS of the bit map: a lane takes 32 rows, a popcount prefix runs over the
+    // wave and then over the four waves, the set bits expand into the list (8192 rows per pair of
+    // barriers; a ballot per 256 rows until round 14).  The pair's bits are [ob, ob + n): its first
+    // and last word are shared with its neighbours and masked to its own rows.
+    const unsigned *keepw = reinterpret_cast<const unsigned *>(A.keep);
+    const int64_t w_first = ob >> 5, w_last = (ob + n - 1) >> 5;
     int out = 0;
-    for (int base = 0; base < n; base += 256) {
-        const int i = base + threadIdx.x;
-        const bool k = i < n && ((reinterpret_cast<const unsigned *>(A.keep)[(ob + i) >> 5] >> ((ob + i) & 31)) & 1u);
-        const unsigned long long mask = __ballot(k);
-        const int before = __popcll(mask & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[wave] = __popcll(mask);
+    for (int64_t wbase = w_first; wbase <= w_last; wbase += 256) {
+        const int64_t w = wbase + threadIdx.x;
+        unsigned bits = 0u;
+        if (w <= w_last) {
+            bits = keepw[w];
+            if (w == w_first) bits &= ~0u << (ob & 31);
+            if (w == w_last) bits &= ~0u >> (31 - (int)((ob + n - 1) & 31));
+        }
+        const int c = __popc(bits);
+        int x = c;
+#pragma unroll
+        for (int sft = 1; sft < 64; sft <<= 1) {
+            const int y = __shfl_up(x, sft);
+            if (lane >= sft) x += y;
+        }
+        if (lane == 63) wcnt[wave] = x;
         __syncthreads();
         int woff = 0, tot = 0;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < wave) woff += wcnt[w];
-            tot += wcnt[w];
+        for (int k = 0; k < 4; ++k) {
+            if (k < wave) woff += wcnt[k];
+            tot += wcnt[k];
         }
-        if (k) A.cand_q[ob + out + woff + before] = i;
+        int at = out + woff + x - c;
+        const int row0 = (int)((w << 5) - ob);               // row of bit 0 of this word (negative in the first)
+        for (unsigned b = bits; b; b &= b - 1) A.cand_q[ob + at++] = row0 + __ffs((int)b) - 1;
         out += tot;
         __syncthreads();
     }
@@ -2113,6 +2224,21 @@ __global__ __launch_bounds__(256) void symcompact_kernel(const int64_t *cand_off
 {
     __shared__ int wcnt[4];
     const int p = blockIdx.x;
+    // a pair without a candidate has no survivor, nothing to merge and nothing to compact: it leaves
+    // before any barrier (pair 0 still resets the lists and the narrow stage's control words)
+    if (cand_cnt[p] == 0) {
+        if (threadIdx.x == 0) {
+            surv_cnt[p] = 0;
+            if (p == 0) {
+                task_total[0] = task_total[1] = 0;
+                if (N.nar != nullptr) {
+                    int32_t *ctl = reinterpret_cast<int32_t *>(N.nar + narrow_layout(N.rows_total, N.n_pairs).ctl);
+                    ctl[0] = ctl[1] = ctl[2] = 0;
+                }
+            }
+        }
+        return;
+    }
     if (N.nar != nullptr) {
         narrow_finish_pair(N, p);
         __threadfence_block();
@@ -2327,12 +2453,17 @@ extern "C" int iamx_knn2sym_candidates(const int32_t *sn2, const int32_t *sperm,
     IAMX_REQUIRE(form >= 0 && form <= 2, "form must be 0, 1 or 2");
     if (n_pairs <= 0) return IAMX_OK;
     CandArgs a{sn2, sperm, img_off, img_n, pairs, osrc, wg_off, col_off, rowp_off, out_off, col, rowp,
-               thresh, keep, cand_cnt, cand_q, task_total, tasks, d2, 8,
+               thresh, sym_cand_K(thresh), keep, cand_cnt, cand_q, task_total, tasks, d2, 8,
                colmask, narrow_enabled() ? static_cast<int8_t *>(nar) : nullptr, rows_total, n_pairs,
                iamx_knn2sym_rows_per_wg(form)};
     IAMX_REQUIRE(rows_total > 0 && rows_total < (1ll << 31), "rows_total = rows of all ordered pairs");
     IAMX_REQUIRE(max_query_rows > 0, "max_query_rows = rows of the largest query image");
-    (void)hipMemsetAsync(keep, 0, (size_t)((rows_total + 31) / 32 * 4), iamx::as_stream(stream));
+    // (the keep map and the pairs' candidate counts in ONE launch: every launch of this stage shows in
+    //  the sweep running beside it)
+    const int64_t keep_words = (rows_total + 31) / 32;
+    const int64_t clear_wg = (keep_words + 4095) / 4096;
+    hipLaunchKernelGGL(symcand_clear_kernel, dim3((unsigned)(clear_wg < 256 ? clear_wg : 256)), dim3(256), 0,
+                       iamx::as_stream(stream), reinterpret_cast<unsigned *>(keep), keep_words, cand_cnt, n_pairs);
     hipLaunchKernelGGL(symcand_rows_kernel,
                        dim3((unsigned)((max_query_rows + 1023) / 1024), (unsigned)(n_pairs < 65535 ? n_pairs : 65535)),
                        dim3(256), 0, iamx::as_stream(stream), a);

@@ -277,6 +277,11 @@ int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2, const int3
                              const int32_t *items, const int64_t *col_off, const int64_t *rowp_off,
                              int n_u, int n_items, int32_t *col, int32_t *rowp,
                              uint8_t *colmask /* may be NULL */, void *stream);
+/* iamx_knn2sym_candidates reads sn2, col and rowp 16 bytes (four sorted rows) at a time: img_off
+ * (= img_off3 of the sorted store), col_off and rowp_off must be multiples of 4 rows, every image's
+ * slice of sn2 / col and every workgroup's slice of rowp padded to iamx_desc3_rows_cap(n) rows, and the
+ * three arrays 16-byte aligned -- what the sweep's own layout (caps of 128 rows) gives.  cand_cnt
+ * DEV [n_pairs] is cleared by the call and ends holding every pair's candidate count. */
 int iamx_knn2sym_candidates(const int32_t *sn2, const int32_t *sperm, const int32_t *img_off,
                             const int32_t *img_n, const int32_t *pairs, const int32_t *osrc,
                             const int32_t *wg_off, const int64_t *col_off, const int64_t *rowp_off,
