@@ -207,6 +207,11 @@ SIGNATURES = {
                                + [c_void_p] * 5),
     'iamx_chain_pair_angles': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p, c_void_p, c_int,
                                        c_double] + [c_void_p] * 4),
+    'iamx_ortho_max_steps': (c_int, []),
+    'iamx_ortho_clear': (c_int, [c_int, c_int, c_int] + [c_void_p] * 5),
+    'iamx_ortho_raster_image': (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]
+                                + [c_int] * 7 + [c_void_p] * 5),
+    'iamx_ortho_resolve': (c_int, [c_int, c_int] + [c_void_p] * 4),
 }
 
 

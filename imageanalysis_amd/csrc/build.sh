@@ -8,7 +8,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 OUT="$HERE/../libiamx.so"
 OBJDIR="$HERE/obj"
-SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip"
+SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip $HERE/ortho_raster.hip"
 mkdir -p "$OBJDIR"
 OBJS=""
 for f in $SRCS; do
@@ -27,6 +27,8 @@ for f in $SRCS; do
         [ "$(basename $f)" = "image_prep.hip" ] && EXTRA="-ffp-contract=off"
         # the chain geometry restates numpy / OpenCV double expressions, operation by operation
         [ "$(basename $f)" = "chain_geom.hip" ] && EXTRA="-ffp-contract=off"
+        # the orthomosaic's texture coordinate, sample, metric and weight restate numpy's float64 expressions
+        [ "$(basename $f)" = "ortho_raster.hip" ] && EXTRA="-ffp-contract=off"
         # the one-wave-per-SIMD sweep (form 2) needs its MFMA
         # accumulators in VGPRs (the allocator's default for > 256 registers is the AGPR half,
         # at a v_accvgpr_read per element the VALU touches)

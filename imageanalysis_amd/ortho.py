@@ -1,0 +1,445 @@
+"""Orthomosaic raster of the Step 5 map: what the reference shows only in explorer.py's Panda3D
+window (every image's surface grid drawn top-down, no depth test, ordered by distance from the view
+centre) written as one georeferenced image, on a machine without a display.
+
+    raster_frame(grids, gsd)                       origin, size, snapped vertices (host)
+    compose(grids, uvs, frames, width, height, gsd, mode)     the rasteriser on ready arrays
+    render(proj, group_list, group_index, gsd, ...)           grids, frames and filters of a project
+    save(mosaic, analysis_dir, tile, fmt)          tiles, world files, ortho.json
+
+The rasteriser is csrc/ortho_raster.hip; tests/ortho_restatement.py restates the rules below in
+numpy, operation by operation, and the device result is held to it byte for byte.
+
+THE RULES
+
+Inputs per image of the group: grid_list, ENU vertices [(S+1)^2][3], NaN allowed; distorted_uv,
+source pixels [(S+1)^2][2] in the camera's width x height; a BGR uint8 frame of any size
+h_s x w_s, source coordinates scaled by w_s / width and h_s / height.
+
+Polygons: the .egg file's.  Cell (j, i) has c = j (S+1) + i and d = c + S + 1; it is USED only if
+c, c+1, d, d+1 are all finite (x, y and z).  A used cell is two triangles, (d, d+1, c+1) then
+(d, c+1, c), cells in file order (j outer, i inner).  The split of the quad is this package's
+convention: Panda3D's own triangulation of a four-vertex polygon is unpinned.  A used vertex is a
+vertex of a used cell.
+
+Raster frame (host, float64), over the used vertices of all images:
+    x0 = floor(min x / gsd) gsd         y1 = ceil(max y / gsd) gsd
+    W = ceil((max x - x0) / gsd)        H = ceil((y1 - min y) / gsd)        (at least 1)
+Row 0 is north; pixel (r, c) has its centre at east x0 + (c + 0.5) gsd, north y1 - (r + 0.5) gsd.
+A side above 2^20 pixels is refused; a mosaic whose accumulators do not fit the free device
+memory is refused with its size in the message (no band splitting).
+
+Coverage is exact.  The host snaps vertices to 1/256 pixel, X = rint((x - x0) / gsd * 256),
+Y = rint((y1 - y) / gsd * 256), int32.  The device evaluates int64 edge functions at the pixel
+centres (256 c + 128, 256 r + 128).  With area2 = (Xb - Xa)(Yc - Ya) - (Yb - Ya)(Xc - Xa) for the
+triangle (a, b, c): area2 == 0 is skipped, area2 < 0 swaps b and c.  The edge opposite vertex k
+(b -> c, c -> a, a -> b) from (Xs, Ys) with (ex, ey) = end - start has the value
+    w_k = ex (py - Ys) - ey (px - Xs)
+and a centre is inside when every w_k > 0, or w_k == 0 on a top-left edge (ey < 0, or ey == 0 and
+ex > 0).  Within one image the first triangle in file order that covers a pixel owns it (this
+settles folded cells).  The rule is watertight and never covers a pixel twice.
+
+Texture coordinate and sample (float64, every product and sum rounded on its own), with w_k
+converted to double and (u_k, v_k) the distorted_uv of vertex k after the swap:
+    u = ((w0 u0 + w1 u1) + w2 u2) / ((w0 + w1) + w2)              v likewise
+    fu = min(max(u (w_s / width) - 0.5, 0), w_s - 1)              fv from v, h_s / height, h_s - 1
+    x0 = floor(fu), x1 = min(x0 + 1, w_s - 1), tx = fu - x0       y likewise
+    top = T[y0][x0] + (T[y0][x1] - T[y0][x0]) tx                  bot on row y1
+    sample = top + (bot - top) ty                                 per channel
+(the clamp is the explorer's WM_clamp).
+
+Composition, images in group order:
+  best      the static form of the explorer's "best" ordering.  Per image, from the tight bounds
+            lo, hi of its used vertices (x, y, z): centre = (lo + hi) 0.5, span = |hi - lo|,
+            metric(p) = sqrt((cx - px)^2 + (cy - py)^2) + span 0.1 at the pixel's centre p.  The
+            covering image with the smallest metric wins, the earlier image on a tie.
+            bgr = floor(sample + 0.5); index (int32, -1 where uncovered); count (uint16, the
+            covering images, saturating).
+  feather   d = min(u, width - u, v, height - v) at the interpolated source coordinate,
+            w = max(d / (0.5 min(width, height)), 2^-20), colour = sum w sample / sum w in
+            float64, accumulated in group order, bgr = floor(colour + 0.5); count as above.
+Uncovered pixels are 0.
+
+Memory: best holds 8 + 4 + 2 + 3 = 17 bytes per pixel, feather 32 + 2 + 3 = 37; one image is one
+launch that reads and writes only the pixels it covers, plus the frame.
+"""
+import ctypes
+import json
+import os
+import time
+from math import ceil, floor, sqrt
+
+import numpy as np
+
+from . import _deps
+from ._deps import getNode
+
+MODES = {'best': 0, 'feather': 1}
+MAX_SIDE = 1 << 20
+SNAP = 256
+BYTES_PER_PIXEL = {'best': 8 + 4 + 2 + 3, 'feather': 32 + 2 + 3}
+PREFILTER_BELOW = 0.75         # the frame is shrunk when native / gsd is below this
+WORLD_EXT = {'jpg': 'jgw', 'jpeg': 'jgw', 'png': 'pgw', 'tif': 'tfw', 'tiff': 'tfw', 'bmp': 'bpw'}
+
+# the last render(): images, frames rasterised / shrunk, seconds per stage
+render_stats = {'images': 0, 'prefiltered': 0, 'seconds': 0.0, 'frames_per_s': 0.0}
+
+
+def _log(*a):
+    _deps.logger().log(*a)
+
+
+class RasterFrame(object):
+    """x0, y1 (metres), W, H (pixels), S, and per image X, Y int32 [N][(S+1)^2] (0 where the vertex
+    is not used) and used uint8 [N][S^2]"""
+    __slots__ = ('x0', 'y1', 'gsd', 'W', 'H', 'S', 'X', 'Y', 'used')
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class Mosaic(object):
+    """device bgr uint8 [H,W,3], index int32 [H,W] (None in mode feather), count uint16 [H,W];
+    x0, y1, gsd; mode; names (the group's images, `index` counts into them)"""
+    __slots__ = ('bgr', 'index', 'count', 'x0', 'y1', 'gsd', 'mode', 'names')
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+    @property
+    def shape(self):
+        return int(self.bgr.shape[0]), int(self.bgr.shape[1])
+
+
+def _grids(grids):
+    g = np.asarray(grids, np.float64)
+    if g.ndim != 3 or g.shape[2] != 3 or g.shape[0] < 1:
+        raise ValueError("grids must be [images][(S+1)^2][3]")
+    side = int(round(sqrt(g.shape[1])))
+    if side * side != g.shape[1] or side < 2:
+        raise ValueError("a grid must hold (S+1)^2 vertices, S >= 1 (got %d)" % g.shape[1])
+    return g, side - 1
+
+
+def used_cells(grids):
+    """-> (used cells bool [N][S][S], used vertices bool [N][S+1][S+1])"""
+    g, S = _grids(grids)
+    fin = np.isfinite(g).all(axis=2).reshape(-1, S + 1, S + 1)
+    cells = fin[:, :-1, :-1] & fin[:, :-1, 1:] & fin[:, 1:, :-1] & fin[:, 1:, 1:]
+    verts = np.zeros_like(fin)
+    verts[:, :-1, :-1] |= cells
+    verts[:, :-1, 1:] |= cells
+    verts[:, 1:, :-1] |= cells
+    verts[:, 1:, 1:] |= cells
+    return cells, verts
+
+
+def raster_frame(grids, gsd):
+    """The raster frame and the snapped vertices of a group's grids (host, float64)."""
+    g, S = _grids(grids)
+    gsd = float(gsd)
+    if not (gsd > 0.0 and np.isfinite(gsd)):
+        raise ValueError("gsd must be a positive number of metres per pixel")
+    cells, verts = used_cells(g)
+    vm = verts.reshape(len(g), -1)
+    if not vm.any():
+        raise ValueError("no image of the group has a cell fully on the surface: nothing to rasterise")
+    x, y = g[:, :, 0], g[:, :, 1]
+    min_x, max_x = float(x[vm].min()), float(x[vm].max())
+    min_y, max_y = float(y[vm].min()), float(y[vm].max())
+    x0 = floor(min_x / gsd) * gsd
+    y1 = ceil(max_y / gsd) * gsd
+    W = max(1, int(ceil((max_x - x0) / gsd)))
+    H = max(1, int(ceil((y1 - min_y) / gsd)))
+    if W > MAX_SIDE or H > MAX_SIDE:
+        raise ValueError("a %d x %d pixel raster: a side above 2^20 pixels is refused (gsd %g m)" % (W, H, gsd))
+    with np.errstate(invalid='ignore'):
+        X = np.where(vm, np.rint((x - x0) / gsd * SNAP), 0.0).astype(np.int32)
+        Y = np.where(vm, np.rint((y1 - y) / gsd * SNAP), 0.0).astype(np.int32)
+    return RasterFrame(x0=x0, y1=y1, gsd=gsd, W=W, H=H, S=S, X=X, Y=Y,
+                       used=np.ascontiguousarray(cells.reshape(len(g), -1), np.uint8))
+
+
+def image_terms(grid, verts):
+    """best: (cx, cy, 0.1 span) from the tight bounds of the image's used vertices; None without one"""
+    p = np.asarray(grid, np.float64).reshape(-1, 3)[np.asarray(verts, bool).reshape(-1)]
+    if len(p) == 0:
+        return None
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    centre = (lo + hi) * 0.5
+    vol = hi - lo
+    span = sqrt(vol[0] * vol[0] + vol[1] * vol[1] + vol[2] * vol[2])
+    return float(centre[0]), float(centre[1]), span * 0.1
+
+
+def pixel_box(X, Y, verts, W, H):
+    """the inclusive box (c0, r0, c1, r1) of the pixels whose centre can lie in the image's used
+    vertices' box, cut to the raster; c1 < c0 when there is none"""
+    m = np.asarray(verts, bool).reshape(-1)
+    if not m.any():
+        return 0, 0, -1, -1
+    xs, ys = X[m].astype(np.int64), Y[m].astype(np.int64)
+    # centres 256 c + 128 in [min, max]
+    c0, c1 = -((128 - int(xs.min())) // SNAP), (int(xs.max()) - 128) // SNAP
+    r0, r1 = -((128 - int(ys.min())) // SNAP), (int(ys.max()) - 128) // SNAP
+    return max(c0, 0), max(r0, 0), min(c1, W - 1), min(r1, H - 1)
+
+
+def native_gsd(grid, cells, frame_w, frame_h):
+    """sqrt(footprint area of the used cells / (frame_w frame_h)): the metres one frame pixel spans"""
+    g = np.asarray(grid, np.float64)
+    S = int(round(sqrt(len(g)))) - 1
+    p = g[:, :2].reshape(S + 1, S + 1, 2)
+    c, c1, d, d1 = p[:-1, :-1], p[:-1, 1:], p[1:, :-1], p[1:, 1:]
+
+    def area(a, b, e):
+        return 0.5 * np.abs((b[..., 0] - a[..., 0]) * (e[..., 1] - a[..., 1])
+                            - (b[..., 1] - a[..., 1]) * (e[..., 0] - a[..., 0]))
+    with np.errstate(invalid='ignore'):
+        cell_area = area(d, d1, c1) + area(d, c1, c)
+    total = float(cell_area[np.asarray(cells, bool).reshape(S, S)].sum())
+    return sqrt(total / (float(frame_w) * float(frame_h)))
+
+
+def prefilter_factor(grid, cells, frame_w, frame_h, gsd):
+    """f = min(1, native / gsd); the frame is shrunk by f in both directions when f < 0.75"""
+    return min(1.0, native_gsd(grid, cells, frame_w, frame_h) / float(gsd))
+
+
+def _check_frame(frame):
+    import torch
+    if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.uint8
+            and frame.dim() == 3 and frame.shape[2] == 3 and frame.numel() > 0):
+        raise ValueError("a frame must be a device uint8 tensor [h, w, 3]")
+    return frame.contiguous()
+
+
+class _Composer(object):
+    """the accumulators of one mosaic and the group's tables on the device; add(k, frame) rasterises
+    image k (call it in group order), finish() -> Mosaic"""
+
+    def __init__(self, grids, uvs, width, height, gsd, mode, names=None):
+        import torch
+        from . import kernels
+        from ._lib import check, lib, require_gpu, stream_ptr
+        if mode not in MODES:
+            raise ValueError("mode must be 'best' or 'feather'")
+        g, S = _grids(grids)
+        L = lib()
+        if S > int(L.iamx_ortho_max_steps()):
+            raise ValueError("grid_steps %d: the rasteriser takes at most %d" % (S, L.iamx_ortho_max_steps()))
+        self.g, self.mode, self.names = g, mode, list(names) if names is not None else None
+        self.width, self.height = float(width), float(height)
+        self.rf = rf = raster_frame(g, gsd)
+        self.cells, self.verts = used_cells(g)
+        dev = self.dev = require_gpu()
+        need = rf.W * rf.H * BYTES_PER_PIXEL[mode]
+        free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+        if need > free:
+            raise MemoryError("a %d x %d pixel mosaic (mode %s) needs %.2f GB of accumulators, %.2f GB of device "
+                              "memory are free: use a coarser gsd (band splitting is not implemented)"
+                              % (rf.W, rf.H, mode, need / 1e9, free / 1e9))
+        uv = np.asarray(uvs, np.float64)
+        if uv.ndim == 2:
+            uv = np.broadcast_to(uv, (len(g),) + uv.shape)
+        if uv.shape != (len(g), g.shape[1], 2) or not np.isfinite(uv).all():
+            raise ValueError("uvs must be finite, [(S+1)^2][2] for the group or per image")
+        self.shared_uv = all(np.array_equal(uv[0], u) for u in uv[1:])
+        self.uv = kernels._dev(uv[:1] if self.shared_uv else uv, kernels.F64)
+        self.xy = kernels._dev(np.stack([rf.X, rf.Y], axis=1), kernels.I32)           # [N][2][V]
+        self.used = kernels._dev(rf.used, kernels.U8)
+        torch.cuda.current_stream().synchronize()          # (the uploads' staging copies have been read)
+        n = (rf.H, rf.W)
+        self.acc = torch.empty(n if mode == 'best' else n + (4,), dtype=torch.float64, device=dev)
+        self.index = torch.empty(n, dtype=torch.int32, device=dev) if mode == 'best' else None
+        self.count = torch.empty(n, dtype=torch.uint16, device=dev)
+        self.bgr = torch.empty(n + (3,), dtype=torch.uint8, device=dev)
+        self._p = kernels._ptr
+        self._call = (L, check, stream_ptr)
+        check(L.iamx_ortho_clear(MODES[mode], rf.H, rf.W, self._p(self.acc), self._p(self.index),
+                                 self._p(self.count), self._p(self.bgr), stream_ptr()), 'iamx_ortho_clear')
+        self.done = 0
+
+    def add(self, k, frame):
+        L, check, stream_ptr = self._call
+        rf, p = self.rf, self._p
+        frame = _check_frame(frame)
+        terms = image_terms(self.g[k], self.verts[k])
+        if terms is None:
+            self.done += 1
+            return
+        c0, r0, c1, r1 = pixel_box(rf.X[k], rf.Y[k], self.verts[k], rf.W, rf.H)
+        params = (ctypes.c_double * 8)(self.width, self.height, rf.x0, rf.y1, rf.gsd, *terms)
+        xy = self.xy[k]
+        check(L.iamx_ortho_raster_image(MODES[self.mode], rf.S, p(xy[0]), p(xy[1]),
+                                        p(self.uv[0 if self.shared_uv else k]), p(self.used[k]), p(frame),
+                                        int(frame.shape[0]), int(frame.shape[1]), params, int(k), c0, r0, c1, r1,
+                                        rf.H, rf.W, p(self.acc), p(self.index), p(self.count), p(self.bgr),
+                                        stream_ptr()), 'iamx_ortho_raster_image')
+        self.done += 1
+
+    def finish(self):
+        L, check, stream_ptr = self._call
+        rf, p = self.rf, self._p
+        if self.mode == 'feather':
+            check(L.iamx_ortho_resolve(rf.H, rf.W, p(self.acc), p(self.count), p(self.bgr), stream_ptr()),
+                  'iamx_ortho_resolve')
+        return Mosaic(bgr=self.bgr, index=self.index, count=self.count, x0=rf.x0, y1=rf.y1, gsd=rf.gsd,
+                      mode=self.mode, names=self.names)
+
+
+def compose(grids, uvs, frames, width, height, gsd, mode='best', names=None):
+    """The rasteriser on ready arrays: grids [N][(S+1)^2][3] ENU, uvs [(S+1)^2][2] (one for the group)
+    or [N][(S+1)^2][2], frames: N device uint8 [h,w,3] tensors, width x height: the camera's image
+    size.  -> Mosaic"""
+    comp = _Composer(grids, uvs, width, height, gsd, mode, names)
+    frames = list(frames)
+    if len(frames) != len(comp.g):
+        raise ValueError("%d frames for %d grids" % (len(frames), len(comp.g)))
+    for k, frame in enumerate(frames):
+        comp.add(k, frame)
+    return comp.finish()
+
+
+def _vignette_mask(analysis_dir):
+    from . import histogram as _histogram, kernels
+    path = os.path.join(analysis_dir, 'models', 'vignette-mask.jpg')
+    if not os.path.exists(path):
+        raise FileNotFoundError("%s: make it with 99-vignette.py first" % path)
+    with open(path, 'rb') as fp, kernels.polite_waits():
+        return _histogram._decode_frame(fp.read())
+
+
+_IDENTITY_LUT = np.tile(np.arange(256, dtype=np.uint8), (3, 1))
+
+
+def prepare_frame(frame, name, grid, cells, gsd, prefilter=True, histogram=False, mask=None):
+    """what render() does to a decoded frame before it is rasterised: histogram.lookup_tables and
+    the vignette mask through kernels.colour_lut, then kernels.resize_area by prefilter_factor()
+    when that is below 0.75.  -> (frame, shrunk?)"""
+    from . import histogram as _histogram, kernels
+    frame = _check_frame(frame)
+    lut = _histogram.lookup_tables(name) if histogram else None
+    if histogram and lut is None:
+        _log("histogram: no neighbour template for", name, "(image left as it is)")
+    if lut is not None or mask is not None:
+        if mask is not None and tuple(mask.shape) != tuple(frame.shape):
+            raise ValueError("%s: the frame is %d x %d, the vignette mask %d x %d"
+                             % (name, frame.shape[1], frame.shape[0], mask.shape[1], mask.shape[0]))
+        frame = kernels.colour_lut(frame, lut if lut is not None else _IDENTITY_LUT, mask)
+    if prefilter:
+        f = prefilter_factor(grid, cells, frame.shape[1], frame.shape[0], gsd)
+        if f < PREFILTER_BELOW and round(frame.shape[0] * f) >= 1 and round(frame.shape[1] * f) >= 1:
+            return kernels.resize_area(frame, f, f), True
+    return frame, False
+
+
+def group_grids(proj, group_list, group_index, matches=None):
+    """The group's grids from the code that makes the .egg files: render_panda3d.elevation_stats and
+    render_panda3d.map_grids (nothing is written).  -> (images, grids [N][(S+1)^2][3], uv)"""
+    import pickle
+    from . import render_panda3d as rp
+    if matches is None:
+        with open(os.path.join(proj.analysis_dir, "matches_grouped"), "rb") as f:
+            matches = pickle.load(f)
+    group = group_list[group_index]
+    ref_node = getNode("/config/ned_reference", True)
+    ref = [ref_node.getFloat('lat_deg'), ref_node.getFloat('lon_deg'), ref_node.getFloat('alt_m')]
+    raw_points, raw_values = rp.elevation_stats(proj, group, group_index, matches)
+    images = rp.map_grids(proj, group, raw_points, raw_values, rp.switches(), ref)
+    grids = np.array([im.grid_list for im in images], np.float64)
+    return images, grids, np.array(images[0].distorted_uv, np.float64)
+
+
+def render(proj, group_list, group_index, gsd, mode='best', prefilter=True, histogram=False, vignette=False,
+           frames=None, matches=None):
+    """The orthomosaic of one group.  The frames are decoded by histogram.frame_pass (in group
+    order, on this thread's stream); frames=: ready device tensors, one per image of the group,
+    instead.  histogram / vignette: the explorer's colour tables (histogram.load() must have found
+    the project's file; models/vignette-mask.jpg must exist).  -> Mosaic"""
+    from . import histogram as _histogram
+    t0 = time.perf_counter()
+    camera = _deps.camera()
+    images, grids, uv = group_grids(proj, group_list, group_index, matches)
+    width, height = camera.get_image_params()
+    names = [im.name for im in images]
+    comp = _Composer(grids, uv, width, height, gsd, mode, names)
+    mask = _vignette_mask(proj.analysis_dir) if vignette else None
+    state = {'k': 0, 'shrunk': 0}
+
+    def on_frames(batch):
+        for frame in batch:
+            k = state['k']
+            frame, shrunk = prepare_frame(frame, names[k], grids[k], comp.cells[k], gsd, prefilter, histogram, mask)
+            comp.add(k, frame)
+            state['k'] = k + 1
+            state['shrunk'] += 1 if shrunk else 0
+
+    if frames is not None:
+        frames = list(frames)
+        if len(frames) != len(images):
+            raise ValueError("%d frames for the group's %d images" % (len(frames), len(images)))
+        on_frames(frames)
+    else:
+        _histogram.frame_pass(images, want_hist=False, on_frames=on_frames)
+    if state['k'] != len(images):
+        raise RuntimeError("%d of %d frames arrived" % (state['k'], len(images)))
+    mosaic = comp.finish()
+    dt = time.perf_counter() - t0
+    render_stats.update(images=len(images), prefiltered=state['shrunk'], seconds=dt,
+                        frames_per_s=len(images) / dt if dt > 0 else 0.0)
+    return mosaic
+
+
+def world_file_text(gsd, west, north):
+    """the six lines of a world file for a north-up tile whose upper-left CORNER is (west, north)"""
+    vals = (gsd, 0.0, 0.0, -gsd, west + 0.5 * gsd, north - 0.5 * gsd)
+    return "".join("%r\n" % float(v) for v in vals)
+
+
+def save(mosaic, analysis_dir, tile=4096, fmt='jpg'):
+    """<analysis_dir>/ortho/tile_<row>_<col>.<fmt> through Pillow (jpg: panda3d.encode_jpeg's
+    settings), a world file per tile (local ENU metres, the pixel-centre convention) and ortho.json:
+    /config/ned_reference, gsd, bounds, mode, per-tile bounds, the image names.  -> the json's dict"""
+    from PIL import Image as PILImage
+    from . import panda3d
+    tile = int(tile)
+    if tile < 1:
+        raise ValueError("tile must be at least 1 pixel")
+    fmt = fmt.lower().lstrip('.')
+    out_dir = os.path.join(analysis_dir, 'ortho')
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = mosaic.shape
+    gsd, x0, y1 = float(mosaic.gsd), float(mosaic.x0), float(mosaic.y1)
+    ref_node = getNode("/config/ned_reference", True)
+    tiles = []
+    for tr in range((H + tile - 1) // tile):
+        for tc in range((W + tile - 1) // tile):
+            r0, c0 = tr * tile, tc * tile
+            r1, c1 = min(r0 + tile, H), min(c0 + tile, W)
+            pixels = mosaic.bgr[r0:r1, c0:c1].contiguous().cpu().numpy()
+            name = 'tile_%d_%d.%s' % (tr, tc, fmt)
+            if fmt in ('jpg', 'jpeg'):
+                blob = panda3d.encode_jpeg(pixels)
+            else:
+                import io
+                buf = io.BytesIO()
+                PILImage.fromarray(np.ascontiguousarray(pixels[:, :, ::-1]), 'RGB').save(
+                    buf, format={'tif': 'TIFF'}.get(fmt, fmt.upper()))
+                blob = buf.getvalue()
+            panda3d._write_atomic(os.path.join(out_dir, name), blob)
+            west, north = x0 + c0 * gsd, y1 - r0 * gsd
+            world = 'tile_%d_%d.%s' % (tr, tc, WORLD_EXT.get(fmt, 'wld'))
+            panda3d._write_atomic(os.path.join(out_dir, world), world_file_text(gsd, west, north).encode())
+            tiles.append({'file': name, 'world_file': world, 'row': tr, 'col': tc, 'width': c1 - c0,
+                          'height': r1 - r0, 'west': west, 'east': x0 + c1 * gsd, 'north': north,
+                          'south': y1 - r1 * gsd})
+    info = {'ned_reference': {k: ref_node.getFloat(k) for k in ('lat_deg', 'lon_deg', 'alt_m')},
+            'units': 'local ENU metres about ned_reference', 'gsd': gsd, 'mode': mosaic.mode,
+            'width': W, 'height': H, 'tile': tile, 'format': fmt,
+            'bounds': {'west': x0, 'east': x0 + W * gsd, 'north': y1, 'south': y1 - H * gsd},
+            'tiles': tiles, 'images': list(mosaic.names) if mosaic.names is not None else []}
+    panda3d._write_atomic(os.path.join(out_dir, 'ortho.json'), json.dumps(info, indent=1).encode())
+    return info

@@ -285,35 +285,19 @@ def surface_grids(tri, values, M, ned, avg_ground, grid, no_extrapolate=False, g
     return pts
 
 
-def build_map(proj, group_list, group_index, matches=None):
-    """The reference's build_map.  `matches` (optional, not in the reference's signature): the
-    matches_grouped structure already in memory -- an array-backed match_cleanup.Chains is read
-    through its arrays -- instead of <analysis_dir>/matches_grouped."""
+def map_grids(proj, group, raw_points, raw_values, sw=None, ref=None):
+    """build_map between the statistics and the egg files (render_panda3d.py:143-228): the Delaunay
+    surface of (raw_points, raw_values), the pixel grid and its distorted twin, every ray of every
+    image of `group` against the surface, and image.distorted_uv / image.grid_list (ENU) for each.
+    sw: switches(); ref: the NED reference [lat, lon, alt], read in the SRTM mode only.  Needs
+    image.z_avg (elevation_stats).  -> the group's images.  ortho.render takes its grids from here,
+    so a mosaic and the .egg files of one project show the same polygons."""
     import scipy.spatial
     camera = _deps.camera()
-    sw = switches()
+    if sw is None:
+        sw = switches()
     clock = time.perf_counter
     stage = grid_stats['stage_s']
-    for k in stage:
-        stage[k] = 0.0
-    grid_stats.update(images=0, rays=0, sky=0, high_angle=0, fallback=0, lookups=0, steps=0, triangles=0,
-                      rounds=None)
-    # lookup ned reference
-    ref_node = getNode("/config/ned_reference", True)
-    ref = [ref_node.getFloat('lat_deg'), ref_node.getFloat('lon_deg'), ref_node.getFloat('alt_m')]
-
-    _log("Loading optimized match points ...")
-    if matches is None:
-        with open(os.path.join(proj.analysis_dir, "matches_grouped"), "rb") as f:
-            matches = pickle.load(f)
-    group = group_list[group_index]
-
-    t = clock()
-    raw_points, raw_values = elevation_stats(proj, group, group_index, matches)
-    stage['stats'] = clock() - t
-
-    save_surface(proj.analysis_dir, raw_points, raw_values)
-
     ground = bool(sw['force_ground_elevation_m'])
     srtm_mode = not ground and bool(sw['use_srtm_surface'])
     _log('Generating Delaunay mesh and interpolator ...')
@@ -364,6 +348,37 @@ def build_map(proj, group_list, group_index, matches=None):
         image.distorted_uv = distorted_uv
         image.grid_list = enu[i].tolist()
     stage['lists'] = clock() - t
+    return images
+
+
+def build_map(proj, group_list, group_index, matches=None):
+    """The reference's build_map.  `matches` (optional, not in the reference's signature): the
+    matches_grouped structure already in memory -- an array-backed match_cleanup.Chains is read
+    through its arrays -- instead of <analysis_dir>/matches_grouped."""
+    sw = switches()
+    clock = time.perf_counter
+    stage = grid_stats['stage_s']
+    for k in stage:
+        stage[k] = 0.0
+    grid_stats.update(images=0, rays=0, sky=0, high_angle=0, fallback=0, lookups=0, steps=0, triangles=0,
+                      rounds=None)
+    # lookup ned reference
+    ref_node = getNode("/config/ned_reference", True)
+    ref = [ref_node.getFloat('lat_deg'), ref_node.getFloat('lon_deg'), ref_node.getFloat('alt_m')]
+
+    _log("Loading optimized match points ...")
+    if matches is None:
+        with open(os.path.join(proj.analysis_dir, "matches_grouped"), "rb") as f:
+            matches = pickle.load(f)
+    group = group_list[group_index]
+
+    t = clock()
+    raw_points, raw_values = elevation_stats(proj, group, group_index, matches)
+    stage['stats'] = clock() - t
+
+    save_surface(proj.analysis_dir, raw_points, raw_values)
+
+    map_grids(proj, group, raw_points, raw_values, sw, ref)
 
     # generate the panda3d egg models
     dir_node = getNode('/config/directories', True)

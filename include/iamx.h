@@ -1224,6 +1224,41 @@ int iamx_chain_pair_angles(const int64_t *ptr, const int32_t *img, const int32_t
                            const uint8_t *in_group, int n_images, double min_angle_deg, int32_t *count,
                            int64_t *total, int32_t *status, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Orthomosaic raster (csrc/ortho_raster.hip): the textured surface grids of Step 5 composed
+ * top-down into one raster of H x W pixels, row 0 north.  The rules (polygons, exact coverage,
+ * texture coordinate, sample, the two composition modes) are stated once in
+ * imageanalysis_amd/ortho.py and restated by tests/ortho_restatement.py.  All pointers DEV unless
+ * noted; null, size and range checks need no GPU.
+ *
+ * mode IAMX_ORTHO_BEST:    acc [H*W] f64 (the winner's metric), index [H*W] i32 (-1: uncovered),
+ *                          count [H*W] u16, bgr [H*W][3] u8 written by the raster kernel itself.
+ * mode IAMX_ORTHO_FEATHER: acc [H*W][4] f64 (sum w b, sum w g, sum w r, sum w; 32-byte aligned),
+ *                          index unused (may be NULL), count as above, bgr written by resolve.
+ *
+ * clear:        the accumulators' start values (best: metric +inf, index -1; feather: zeros).
+ * raster_image: one image per launch, stream ordered -- the images of a group are composed in the
+ *   order of the calls.  X, Y i32 [(S+1)^2]: vertices snapped to 1/256 pixel; uv f64 [(S+1)^2][2]:
+ *   source pixels in the camera's size; used u8 [S^2]: the cells that count; frame u8
+ *   [h_s][w_s][3]; params HOST f64 [8] = camera width, height, raster x0, y1, gsd, the image's
+ *   centre east, north and 0.1 span (the last three read in mode best only); image_index: what
+ *   `index` receives; c0, r0, c1, r1: the inclusive pixel box of the image's used vertices
+ *   (c1 < c0 or r1 < r0: nothing is launched).  1 <= S <= iamx_ortho_max_steps().
+ * resolve:      feather only: bgr = floor(sum w colour / sum w + 0.5) where count > 0.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_ORTHO_BEST 0
+#define IAMX_ORTHO_FEATHER 1
+int iamx_ortho_max_steps(void);
+int iamx_ortho_clear(int mode, int H, int W, double *acc, int32_t *index, uint16_t *count,
+                     uint8_t *bgr, void *stream);
+int iamx_ortho_raster_image(int mode, int S, const int32_t *X, const int32_t *Y, const double *uv,
+                            const uint8_t *used, const uint8_t *frame, int h_s, int w_s,
+                            const double *params, int image_index, int c0, int r0, int c1, int r1,
+                            int H, int W, double *acc, int32_t *index, uint16_t *count, uint8_t *bgr,
+                            void *stream);
+int iamx_ortho_resolve(int H, int W, const double *acc, const uint16_t *count, uint8_t *bgr,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
