@@ -332,6 +332,10 @@ struct SymArgs {
     uint8_t *colmask;            // [..] per column-result row: the groups (bit (tile & 3) + 4 * lane half)
                                  //      whose minimum is <= v2 (NULL: not wanted) -- the only train rows
                                  //      that can be the query's best or second (narrow exact stage)
+#if defined(IAMX_T_STAMPS)
+    unsigned long long *stamps;  // [workgroups][waves][4]: segment sum, chunks, loop cycles, loop 100 MHz ticks --
+                                 //      a buffer of its own: nothing in the library reads it
+#endif
 };
 
 __device__ __forceinline__ int uniform32(int x) { return __builtin_amdgcn_readfirstlane(x); }
@@ -521,6 +525,47 @@ __device__ __forceinline__ void row_min16_block(int (&r)[16], int &after)
     if constexpr (PASS) after = keep;
 }
 
+// One piece of form 2's stage in the chunk loop (round 16): the LDS-DMA load as an asm statement, so that it
+// can be HELD in a gap of the step that carries valu instructions only -- it follows and feeds the running
+// minimum `after`, the way row_min16_block is held -- instead of landing in the step's last gap beside the
+// operand reads, where an LDS-DMA instruction costs several times its issue slot.  `lds_dst`: the wave's LDS
+// byte address (wave-uniform, M0's value); `gsrc`: the lane's source.  M0 belongs to the compiler and is not
+// preserved around a statement: it is saved, written and read in this ONE statement and put back.  The
+// compiler does not count an asm load: what waits for these pieces is the chunk loop's own explicit
+// s_waitcnt vmcnt(0) at its barrier step (and the one behind the loop) -- every piece is issued in program
+// order before it, vmcnt(0) waits for ALL of the wave's outstanding vector memory loads, counted by the
+// hardware and not by the compiler, and the barrier behind it covers the other waves' pieces.
+template <int BYTES>
+__device__ __forceinline__ void stage_piece_held(const void *gsrc, unsigned lds_dst, int &after)
+{
+    static_assert(BYTES == 16 || BYTES == 4, "one dwordx4 or one dword a lane");
+    unsigned m0_was;
+    int keep = after;
+    if constexpr (BYTES == 16)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_was), "+v"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_was), "+v"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+    after = keep;
+}
+
+// IAMX_T_STAMPS=<segment>: a DIAGNOSTIC build of form 2 (tools/sweep_stamps.py; never the shipped library)
+// that brackets ONE segment of the chunk loop with s_memtime and adds the differences into a 64-bit scalar
+// sum.  Segment 1..16: step segment - 1; 17: the barrier step's s_waitcnt; 18: its s_barrier; 19: two stamps
+// back to back (the stamp's own cost).  Every such build also brackets the whole loop with s_memtime and
+// s_memrealtime (the in-kernel clock).  A stamp is one asm statement between two scheduling fences; its
+// lgkmcnt(0) is part of it (s_memtime returns out of order with LDS reads).  Read SHARES from such a build,
+// never its run time: the fences forbid overlaps the shipped loop has.
+#if defined(IAMX_T_STAMPS)
+#define SWEEP_STAMP(t)                                                                     \
+    do {                                                                                   \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");       \
+        __builtin_amdgcn_sched_barrier(0);                                                 \
+    } while (0)
+#endif
+
 // Form 2's chunk loop: the valu instructions that go behind MFMA `g` (0..7) of a step with `nv` of them
 // and `tail` other vector instructions (they end up in the last gap).  With `blocks`, gaps 3 and 4 hold
 // one minimum and an asm block of the row butterfly each.  Six issue slots a gap.
@@ -532,6 +577,23 @@ constexpr int sweep_gap_valu(int nv, int tail, bool blocks, int g)
     if (blocks && (g == 3 || g == 4)) return 1;
     const int i = blocks && g > 4 ? g - 2 : g;
     return rest / n + (i < rest % n ? 1 : 0);
+}
+
+// Form 2's chunk loop: which of a step's 32 minima is written `i`-th (0..15 the row minimum of accumulator
+// register i, 16 + w the column minimum w: chain 0, w < 8, reads acc0 only, chain 1 acc1 only).  A step opens
+// with chain 0 (round 16): acc0 was written two MFMAs before the step's first valu instruction, acc1 by the
+// MFMA right in front of it, and a row minimum reads both -- the compiler padded 13 of the 16 step heads
+// with an s_nop of 1 to 5 wait states (54 a chunk) in gaps that are full without it.  Chain 1 follows, then
+// the rows.  With `blocks`, minima 6 and 7 of chain 0 are held back to positions `p3` and `p3 + 1`, the single
+// minima of gaps 3 and 4, which the asm blocks of the row butterfly follow.  `min` is exact in any order, and
+// every chain keeps its own order.
+constexpr int sweep_min_order(bool blocks, int p3, int i)
+{
+    const int head = blocks ? 6 : 8;
+    if (i < head) return 16 + i;
+    if (blocks && (i == p3 || i == p3 + 1)) return 16 + 6 + (i - p3);
+    const int f = i - (blocks && i < p3 ? 6 : 8);       // chain 1, then the rows
+    return f < 8 ? 24 + f : f - 8;
 }
 
 // a loop whose index is a compile-time constant in its body: f(int_c<I>) for I = FROM .. TO - 1
@@ -616,6 +678,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
     // offsets and rows behind that pair's first barrier (they land during its chunk loop) -- and
     // taken through readfirstlane: behind the pair's stores they are vector loads, and the row
     // partials' buffer resource must stay in scalar registers (no waterfall loop around the merge)
+#if defined(IAMX_T_STAMPS)
+    unsigned long long stamp_sum = 0, stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0;
+#endif
     int nx_b = 0, nx_a = 0, nx_boff = 0, nx_nb = 0, nx_aoff = 0, nx_na = 0;
     int64_t nx_rowp = 0;
     if constexpr (ITEMS) {
@@ -780,7 +845,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                 a[s] = *reinterpret_cast<const v4i *>(lds_tile + buf * (CHUNK * D) + rr * D + (((2 * s + g) ^ swz) * 16));
             }
         };
-        auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1) {
+        // (the statement that pins the accumulators to the VGPR half has side effects: it keeps its order
+        //  against a held stage piece, so form 2's chunk loop writes it behind its minima -- in front of them
+        //  it would push the piece behind the step's last MFMA)
+        auto pin_accs = [&](v16i &acc0, v16i &acc1) {
+            if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
+        };
+        auto issue = [&](int t, int qp, v16i &acc0, v16i &acc1, bool pin = true) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) acc0[reg] = acc1[reg] = tbop[t & 1][reg >> 2][reg & 3];
 #pragma unroll
@@ -788,7 +859,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                 acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp][s], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aop[t & 1][s], bq[qp + 1][s], acc1, 0, 0, 0);
             }
-            if constexpr (WPE == 1) asm volatile("" : "+v"(acc0), "+v"(acc1));
+            if (pin) pin_accs(acc0, acc1);
         };
 
         if constexpr (ITEMS) {           // (the last pair of the item reads its own entries again)
@@ -835,7 +906,14 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
             else a[k - 4] = *reinterpret_cast<const __attribute__((address_space(3))) v4i *>((lds_bytes)lds + opoff[k - 4] + tile * (32 * D));
         };
         const unsigned stage_voff = (unsigned)((tid >> 3) * D + (((tid & 7) ^ ((tid >> 4) & 7)) * 16));
+        // (the wave's LDS byte addresses of a stage's first piece and of its Ct words, in scalar registers)
+        const unsigned lds_tile_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tile + wave_u * (64 * 16));
+        const unsigned lds_tb_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tb + (wave_u & (CHUNK / 64 - 1)) * 64);
         const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
+#if defined(IAMX_T_STAMPS)
+        const unsigned long long loop_c0 = __builtin_amdgcn_s_memtime(), loop_r0 = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0) alone: the loop's first LDS waits stay counted
+#endif
         for (int ch = 0; ch < nchunks; ++ch) {
             const int buf = ch & 1;
             if constexpr (PP == 4) {
@@ -847,9 +925,10 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
             // floor behind the second level, the levels "xor 16" and inside the quads in the fourth step.
             // What is no valu instruction belongs to no group (a group of LDS or memory instructions breaks
             // the pipeline of groups behind it with this compiler) and ends up behind the step's last group:
-            // the step's two operand reads, and at most one instruction of the chunk's own work -- so the
-            // stage of chunk + 2 goes one instruction a step into the five steps from the barrier on, never
-            // two in one gap, and the merge of the previous chunk reads, computes and stores in three steps.
+            // the step's two operand reads, and at most one instruction of the chunk's own work -- the merge of
+            // the previous chunk reads, computes and stores in three steps.  The stage of chunk + 2 goes one
+            // piece a step into the five steps from the barrier on, never two in one gap; since round 16 a
+            // piece is an asm statement held in a gap that carries valu instructions only (stage_piece_held).
             // The chunk's barrier is the head of the last step of tile NT4 - 2; the step in front of it
             // issues no LDS read.
             constexpr int BAR = (NT4 - 1) * PP - 1;
@@ -862,56 +941,103 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                 constexpr int st = decltype(st_c)::value;
                 constexpr int t = st / PP, ph = st % PP, qp = 2 * ph, cur = st & 1;
                 constexpr int nst = st + 1 < NS ? st + 1 : 0;
+#if defined(IAMX_T_STAMPS)
+                unsigned long long stamp_t0 = 0, stamp_t1 = 0;
+                if constexpr (IAMX_T_STAMPS == st + 1 || (st == BAR && IAMX_T_STAMPS == 17)) SWEEP_STAMP(stamp_t0);
+                if constexpr (st == 0 && IAMX_T_STAMPS == 19) {      // (two stamps back to back: a stamp's own cost)
+                    SWEEP_STAMP(stamp_t0);
+                    SWEEP_STAMP(stamp_t1);
+                    stamp_sum += stamp_t1 - stamp_t0;
+                }
+#endif
                 if constexpr (st == BAR) {
                     // every read of this chunk's stage is done (lgkmcnt), the next chunk's stage has landed
                     // (vmcnt): the stage of chunk + 2 may overwrite this one
                     __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
+#if defined(IAMX_T_STAMPS)
+                    if constexpr (IAMX_T_STAMPS == 17) {
+                        SWEEP_STAMP(stamp_t1);
+                        stamp_sum += stamp_t1 - stamp_t0;
+                    }
+                    if constexpr (IAMX_T_STAMPS == 18) SWEEP_STAMP(stamp_t0);
+#endif
                     __syncthreads();
+#if defined(IAMX_T_STAMPS)
+                    if constexpr (IAMX_T_STAMPS == 18) {
+                        SWEEP_STAMP(stamp_t1);
+                        stamp_sum += stamp_t1 - stamp_t0;
+                    }
+#endif
                 }
-                issue(nst / PP, 2 * (nst % PP), accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                issue(nst / PP, 2 * (nst % PP), accs[cur ^ 1][0], accs[cur ^ 1][1], false);
                 // the operand reads of tile T (flattened across chunks), 8 / PP a step as before; from tile
                 // NT4 on they read the next chunk's stage.  The step in front of the barrier has none (the
                 // barrier's wait would sit right behind them): the step before that issues them
-                static_for<(st == BAR - 1 ? 1 : 0), (st == BAR - 2 ? 2 : 1)>([&](auto d_c) {
-                    constexpr int sr = st + decltype(d_c)::value;
-                    constexpr int T = (sr + 1) / PP + 1, i = (sr + 1) % PP;
-                    if constexpr (T == NT4 && i == 0) {
+                // (they are written behind the step's minima: a held stage piece is an asm statement, which no
+                //  LDS read crosses, and the reads belong in the step's last gap, behind it)
+                auto operand_reads = [&]() {
+                    static_for<(st == BAR - 1 ? 1 : 0), (st == BAR - 2 ? 2 : 1)>([&](auto d_c) {
+                        constexpr int sr = st + decltype(d_c)::value;
+                        constexpr int T = (sr + 1) / PP + 1, i = (sr + 1) % PP;
 #pragma unroll
-                        for (int s = 0; s < 4; ++s) opoff[s] ^= CHUNK * D;
-                        tboff ^= CHUNK * 4;
-                    }
+                        for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k) load_op_at(T % NT4, k, aop[T & 1], tbop[T & 1]);
+                    });
+                };
+                if constexpr (st == BAR) {           // (its reads are tile NT4's first: the next chunk's stage)
 #pragma unroll
-                    for (int k = i * 8 / PP; k < (i + 1) * 8 / PP; ++k) load_op_at(T % NT4, k, aop[T & 1], tbop[T & 1]);
-                });
+                    for (int s = 0; s < 4; ++s) opoff[s] ^= CHUNK * D;
+                    tboff ^= CHUNK * 4;
+                }
                 // the valu instructions of the step (the two swaps of the fourth step count twice) and what
                 // its last gap holds beside them
                 constexpr int nv = (ph == 2 ? 36 : ph == 3 ? 40 : 32) + (st == BAR + 2 ? 11 : 0) + (st == BAR + 3 ? 5 : 0) +
                                    (st >= BAR && st <= BAR + PIECES ? 1 : 0) +    // (a stage instruction's address)
                                    (st == NS - 1 ? 2 : 0);                          // (the loop's own)
-                constexpr int tail = (st == BAR - 1 ? 0 : st == BAR - 2 ? 4 : 2) + (ph == 3 ? 1 + 2 : 0) + (st >= BAR && st <= BAR + PIECES ? 1 : 0) +
+                constexpr int tail = (st == BAR - 1 ? 0 : st == BAR - 2 ? 4 : 2) + (ph == 3 ? 1 + 2 : 0) +
                                      (st == BAR + 1 ? 2 : 0) + (st == BAR + 3 ? 1 : 0);
+                // (a step from the barrier on holds one piece of the stage of chunk + 2 in gap STAGE_GAP, which
+                //  carries valu instructions only: behind the second minimum of column chain 1, which it follows,
+                //  and one valu instruction fewer in that gap)
+                constexpr bool staging = st >= BAR && st <= BAR + PIECES;
+                constexpr int STAGE_GAP = 1, STAGE_AT = 8 + 1;
                 // (the asm blocks of the row butterfly belong to no group: the first sits between the column
                 //  minimum that is the one valu instruction of gap 3 and the next one -- it passes the running
                 //  minimum through -- and the second reads that next one, the one of gap 4)
+                // (in a staging step the piece's address is a valu instruction in front of them, and gap 1 holds one fewer)
                 constexpr int blk_at = sweep_gap_valu(nv, tail, true, 0) + sweep_gap_valu(nv, tail, true, 1) +
-                                       sweep_gap_valu(nv, tail, true, 2) - 16;
-                static_assert(ph == 3 || (blk_at >= 0 && blk_at < 15 && blk_at != 7), "gaps 3 and 4 hold two minima of one column chain");
-                // minima of this step: the rows first, then the two column chains; with them the previous
-                // tile's row butterfly (tile NT4 - 1 of the previous chunk for t = 0)
+                                       sweep_gap_valu(nv, tail, true, 2) - (staging ? 2 : 0);
+                static_assert(ph == 3 || (blk_at >= 6 && blk_at < 31), "gaps 3 and 4 hold the last two minima of column chain 0");
+                // minima of this step, in the order of sweep_min_order: column chain 0 first (it reads acc0
+                // alone), then column chain 1 (a held stage piece follows its second minimum, which that order
+                // puts in gap 1 or 2), then the rows; with them the previous tile's row butterfly
+                // (tile NT4 - 1 of the previous chunk for t = 0)
                 const v16i acc0 = accs[cur][0], acc1 = accs[cur][1];
                 int (&rc_)[16] = r[t & 1];
                 int (&rp)[16] = r[(t + 1) & 1];
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg)
-                    rc_[reg] = qp == 0 ? min(acc0[reg], acc1[reg]) : min(min(rc_[reg], acc0[reg]), acc1[reg]);
-                static_for<0, 16>([&](auto w_c) {
-                    constexpr int w = decltype(w_c)::value;
-                    int &mm = m[qp + (w >> 3)][t & 3];
-                    const v16i &acc = w < 8 ? acc0 : acc1;
-                    mm = min(min(mm, acc[2 * (w & 7)]), acc[2 * (w & 7) + 1]);
-                    if constexpr (ph < 3 && w == blk_at) row_min16_block<2 * ph, true>(rp, mm);
-                    if constexpr (ph < 3 && w == blk_at + 1) row_min16_block<2 * ph + 1, true>(rp, mm);
+                static_for<0, 32>([&](auto i_c) {
+                    constexpr int i = decltype(i_c)::value, op = sweep_min_order(ph < 3, blk_at, i);
+                    if constexpr (op < 16) {
+                        rc_[op] = qp == 0 ? min(acc0[op], acc1[op]) : min(min(rc_[op], acc0[op]), acc1[op]);
+                    } else {
+                        constexpr int w = op - 16;
+                        int &mm = m[qp + (w >> 3)][t & 3];
+                        const v16i &acc = w < 8 ? acc0 : acc1;
+                        mm = min(min(mm, acc[2 * (w & 7)]), acc[2 * (w & 7) + 1]);
+                        if constexpr (ph < 3 && i == blk_at) row_min16_block<2 * ph, true>(rp, mm);
+                        if constexpr (ph < 3 && i == blk_at + 1) row_min16_block<2 * ph + 1, true>(rp, mm);
+                        // the stage of chunk + 2, one piece a step: its buffer is free behind the barrier, its
+                        // data is due a chunk later (the next chunk's barrier step waits for it)
+                        if constexpr (staging && w == STAGE_AT) {
+                            if constexpr (st < BAR + PIECES)
+                                stage_piece_held<16>(sg_tile + (st - BAR) * ((NT / 8) * D) + stage_voff,
+                                                     lds_tile_at + buf * (CHUNK * D) + (st - BAR) * NT * 16, mm);
+                            else
+                                stage_piece_held<4>(sg_ct + ct_voff, lds_tb_at + buf * (CHUNK * 4), mm);
+                        }
+                    }
                 });
+                pin_accs(accs[cur ^ 1][0], accs[cur ^ 1][1]);
+                operand_reads();
                 if constexpr (ph == 2) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) bu[k] = rp[4 * k] + lo_lane;
@@ -924,15 +1050,8 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                 // minima were stored in this chunk's first tile) and the stage of chunk + 2
                 // what is no valu instruction belongs to no group and goes behind the step's last group, into
                 // its last gap: the step's two operand reads, the store of the row minima, and one piece of the
-                // chunk's own work a step from the barrier on -- the stage of chunk + 2 (one instruction a step:
-                // its buffer is free behind the barrier, its data is due a chunk later) and the merge of the
-                // previous chunk (its rows' last minima were stored in this chunk's first tile)
-                if constexpr (st >= BAR && st < BAR + PIECES)
-                    __builtin_amdgcn_global_load_lds(sg_tile + (st - BAR) * ((NT / 8) * D) + stage_voff,
-                                                     (lds_ptr)(lds_tile + buf * (CHUNK * D) + ((st - BAR) * NT + wave_u * 64) * 16), 16, 0, 0);
-                if constexpr (st == BAR + PIECES)
-                    __builtin_amdgcn_global_load_lds(sg_ct + ct_voff,
-                                                     (lds_ptr)(lds_tb + buf * CHUNK + (wave_u & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
+                // chunk's own work a step from the barrier on -- the merge of the previous chunk (its rows' last
+                // minima were stored in this chunk's first tile); the stage of chunk + 2 is held among the minima
                 if constexpr (st == BAR + 1) {
 #pragma unroll
                     for (int w = 0; w < NW; ++w) mR[w] = lds_row[rbo_prev + w * CHUNK + mrow];
@@ -953,9 +1072,16 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
                     constexpr int g = decltype(g_c)::value;
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     // (the last group takes what the counts above missed)
-                    __builtin_amdgcn_sched_group_barrier(0x002, sweep_gap_valu(nv, tail, ph < 3, g) + (g == 7 ? 3 : 0), 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, sweep_gap_valu(nv, tail, ph < 3, g) + (g == 7 ? 3 : 0) -
+                                                                    (staging && g == STAGE_GAP ? 1 : 0), 0);
                 });
                 __builtin_amdgcn_sched_barrier(0);
+#if defined(IAMX_T_STAMPS)
+                if constexpr (IAMX_T_STAMPS == st + 1) {
+                    SWEEP_STAMP(stamp_t1);
+                    stamp_sum += stamp_t1 - stamp_t0;
+                }
+#endif
             });
             } else {
 #pragma unroll
@@ -1028,6 +1154,23 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
             rbo_prev = rbo;
             rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
         }
+#if defined(IAMX_T_STAMPS)
+        if constexpr (PP == 4) {
+            unsigned long long loop_c1;
+            SWEEP_STAMP(loop_c1);
+            stamp_cycles += loop_c1 - loop_c0;
+            stamp_ticks += __builtin_amdgcn_s_memrealtime() - loop_r0;
+            stamp_chunks += (unsigned)nchunks;
+            // (lane 0, ordinary vector stores, after every pair: the sums so far)
+            if (A.stamps && lane == 0) {
+                unsigned long long *o = A.stamps + ((size_t)blockIdx.x * NW + wave) * 4;
+                o[0] = stamp_sum;
+                o[1] = stamp_chunks;
+                o[2] = stamp_cycles;
+                o[3] = stamp_ticks;
+            }
+        }
+#endif
         // (ITEMS: this pair's first column-result row, read here -- it lands with the vmcnt(0) below --
         //  rather than carried through the chunk loop in scalar registers, which the loop needs)
         int64_t col_v = 0;
@@ -2367,6 +2510,19 @@ extern "C" int iamx_desc3_pack_batch_u8(const uint8_t *src, const int64_t *src_o
 #define SWEEP_STR2(...) #__VA_ARGS__
 #define SWEEP_STR(...) SWEEP_STR2(__VA_ARGS__)
 
+#if defined(IAMX_T_STAMPS)
+// the diagnostic build's stamp buffer ([workgroups][4 waves][4] u64 of the next launches; NULL: none)
+static unsigned long long *g_sweep_stamps = nullptr;
+extern "C" int iamx_knn2sym_set_stamps(void *buf)
+{
+    g_sweep_stamps = static_cast<unsigned long long *>(buf);
+    return IAMX_OK;
+}
+#define SWEEP_STAMPS_ARG , g_sweep_stamps
+#else
+#define SWEEP_STAMPS_ARG
+#endif
+
 extern "C" const char *iamx_knn2sym_kernel_id(int form)
 {
     switch (form) {
@@ -2391,7 +2547,7 @@ extern "C" int iamx_knn2sym_sweep(const int8_t *sdesc, const int32_t *sn2, const
     IAMX_REQUIRE(form >= 0 && form <= 2, "form must be 0 (256 rows), 1 (512) or 2 (1024)");
     if (n_u == 0 || total_wg == 0) return IAMX_OK;
     SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, wg_off, col_off, rowp_off, col, rowp, n_u, total_wg,
-              colmask};
+              colmask SWEEP_STAMPS_ARG};
     const dim3 g((unsigned)total_wg);
     hipStream_t st = iamx::as_stream(stream);
     // PIPE = 6: six epilogue VALU instructions beside every MFMA of the next pair of query
@@ -2416,7 +2572,7 @@ extern "C" int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2,
     if (n_u == 0 || n_items == 0) return IAMX_OK;
     // (the item walk reads its table through wg_off, its count through total_wg)
     SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, items, col_off, rowp_off, col, rowp, n_u, n_items,
-              colmask};
+              colmask SWEEP_STAMPS_ARG};
     hipLaunchKernelGGL((knn2sym_kernel<SWEEP_ITEMS2>), dim3((unsigned)n_items), dim3(256), 0,
                        iamx::as_stream(stream), a);
     return iamx::check_launch("iamx_knn2sym_sweep_items");

@@ -1,13 +1,20 @@
 // micro-benchmark: sustained v_mfma_i32_32x32x32_i8 rate and shader clock on gfx950 for
 //   (a) independent accumulators vs dependent chains of 4, (b) zero vs random operand data,
 //   (c) 2 vs 4 waves per SIMD.  clock = s_memtime ticks / s_memrealtime (100 MHz) ticks.
+//   (d) round 16: v_mfma_i32_16x16x64_i8 on the same output tile per wave (two 32 x 32 tiles as 2 x 4
+//       accumulators of 16 x 16, K = 128 a round: 16 MFMAs of half the work each), random data, ONE
+//       wave per SIMD -- beside 32x32x32 at one wave per SIMD.  Rates are per 32x32x32 of work.
+//   Build: hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-mfma-vgpr-form -o mfma_clock mfma_clock.hip
+//   (the library's flag for the sweep).  Without it the compiler keeps the v4i accumulators of (d) in AGPRs
+//   and shifts the result tuples: 56 v_accvgpr copies an iteration beside the 16 MFMAs, and the figure is
+//   theirs.  With it the loops are bare: 8 MFMAs (32x32x32), 16 MFMAs (16x16x64) and the loop counter.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-template <int MODE>   // 0: 2 independent accumulators  1: dependent chain of 4 then new C
+template <int MODE>   // 0: 2 independent accumulators  1: dependent chain of 4 then new C  2: 16x16x64, 8 accumulators
 __global__ __launch_bounds__(256) void k(const v4i *data, int iters, long long *clk, int *sink)
 {
     v4i a[4], b[4];
@@ -19,8 +26,17 @@ __global__ __launch_bounds__(256) void k(const v4i *data, int iters, long long *
     v16i c0 = {0};
     long long t0 = clock64(), w0 = wall_clock64();
     int keep = 0;
+    v4i q[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
     for (int i = 0; i < iters; ++i) {
-        if (MODE == 0) {
+        if (MODE == 2) {
+            // tile j of the two 32 x 32 outputs: operand halves differ per 16 x 16 sub-tile in a real kernel;
+            // here every sub-tile takes its own pair of registers so that no two MFMAs are identical
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    q[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[(j + 2 * s) & 3], b[(j >> 1) & 3], q[j], 0, 0, 0);
+        } else if (MODE == 0) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], b[s], acc0, 0, 0, 0);
@@ -39,7 +55,8 @@ __global__ __launch_bounds__(256) void k(const v4i *data, int iters, long long *
     long long t1 = clock64(), w1 = wall_clock64();
     if (threadIdx.x == 0) { clk[2 * blockIdx.x] = t1 - t0; clk[2 * blockIdx.x + 1] = w1 - w0; }
     int s = keep;
-    for (int q = 0; q < 16; ++q) s += acc0[q] + acc1[q];
+    for (int e = 0; e < 16; ++e) s += acc0[e] + acc1[e];
+    for (int j = 0; j < 8; ++j) s += q[j][0] + q[j][1] + q[j][2] + q[j][3];
     if (s == 0x12345678) sink[0] = s;
 }
 
@@ -58,7 +75,7 @@ void run(const char *name, const v4i *d, int blocks_per_cu)
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     long long h[2]; (void)hipMemcpy(h, clk, 16, hipMemcpyDeviceToHost);
-    const double mfma_per_simd = (double)iters * 8 * blocks_per_cu;
+    const double mfma_per_simd = (double)iters * 8 * blocks_per_cu;      // (in 32x32x32 of work: 16 of 16x16x64 = 8)
     const double ghz = (double)h[0] / ((double)h[1] / 100e6) / 1e9;
     printf("%-44s %d waves/SIMD: %7.2f ms  %.2f ns/MFMA/SIMD  shader clock %.3f GHz  => %.1f cycles/MFMA\n",
            name, blocks_per_cu, ms, ms * 1e6 / mfma_per_simd, ghz, ms * 1e6 / mfma_per_simd * ghz);
@@ -74,6 +91,10 @@ int main()
     srand(1);
     for (size_t i = 0; i < n * 4; ++i) ((int *)h)[i] = (rand() << 16) ^ rand();
     (void)hipMemcpy(dr, h, n * sizeof(v4i), hipMemcpyHostToDevice);
+    run<0>("32x32x32, independent accumulators, random data", dr, 1);
+    run<2>("16x16x64, 8 accumulators, random data", dr, 1);
+    run<0>("32x32x32, independent accumulators, random data", dr, 1);
+    run<2>("16x16x64, 8 accumulators, random data", dr, 1);
     for (int w : {2, 4}) {
         run<0>("independent accumulators, zero data", dz, w);
         run<0>("independent accumulators, random data", dr, w);
