@@ -2,11 +2,19 @@
 ba_solver.VecOps) against scipy/optimize/_lsq/common.py itself -- the helpers
 scipy.optimize.least_squares(method='trf') runs between two LSMR solves and that the reference
 reaches through scripts/lib/optimizer.py:352-399.  Element-wise results are compared bit for
-bit (same IEEE operations in the same order), reductions to round-off."""
+bit (same IEEE operations in the same order), reductions to round-off.
+
+Every test runs at n = 40000 and, as its `_lengths` twin, at the lengths around the fixed 256 x 256
+grid of the reductions: one element, fewer elements than one block (255: most blocks of a
+reduction are empty), exactly one grid stride (65536), one over, and two strides plus one."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+LENGTHS = [1, 255, 65536, 65537, 131073]
+lengths = pytest.mark.parametrize('n', LENGTHS)
+seeds = pytest.mark.parametrize('seed', range(4))
 
 
 def _case(seed, n=40000):
@@ -14,6 +22,8 @@ def _case(seed, n=40000):
     x = rng.normal(0, 5, n)
     lb = np.where(rng.random(n) < 0.4, x - rng.uniform(0, 3, n), -np.inf)
     ub = np.where(rng.random(n) < 0.4, x + rng.uniform(0, 3, n), np.inf)
+    if not (np.isfinite(lb) & np.isfinite(ub)).any():      # (a handful of elements: the tests pick a
+        lb[0], ub[0] = x[0] - 1.5, x[0] + 0.75             #  component with both bounds finite)
     on_lo = rng.random(n) < 0.05
     on_up = (rng.random(n) < 0.05) & ~on_lo
     x = np.where(on_lo & np.isfinite(lb), lb, x)           # some points exactly on a bound
@@ -41,10 +51,9 @@ def _h(t):
     return t.cpu().numpy()
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_cl_scaling_vector_and_scaled_quantities(V, seed):
+def _cl_scaling_vector_and_scaled_quantities(V, seed, n):
     from scipy.optimize._lsq import common
-    x, lb, ub, g, _ = _case(seed)
+    x, lb, ub, g, _ = _case(seed, n)
     v, dv = common.CL_scaling_vector(x, g, lb, ub)
     tx, tlb, tub, tg = _t(V, x, lb, ub, g)
     tv, tdv = V.cl_scaling(tx, tg, tlb, tub)
@@ -62,11 +71,10 @@ def test_cl_scaling_vector_and_scaled_quantities(V, seed):
     assert np.array_equal(_h(V.sqrt_shift(tv, 0.25)), np.sqrt(v + 0.25))
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_step_size_to_bound_and_reflection(V, seed):
+def _step_size_to_bound_and_reflection(V, seed, n):
     import torch
     from scipy.optimize._lsq import common
-    x, lb, ub, _, s = _case(seed)
+    x, lb, ub, _, s = _case(seed, n)
     x = common.make_strictly_feasible(x, lb, ub)
     step, hits = common.step_size_to_bound(x, s, lb, ub)
     tx, tlb, tub, ts = _t(V, x, lb, ub, s)
@@ -83,10 +91,9 @@ def test_step_size_to_bound_and_reflection(V, seed):
     assert tstep == step == np.inf and np.array_equal(_h(thits).astype(int), hits)
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_make_strictly_feasible_and_in_bounds(V, seed):
+def _make_strictly_feasible_and_in_bounds(V, seed, n):
     from scipy.optimize._lsq import common
-    x, lb, ub, _, s = _case(seed)
+    x, lb, ub, _, s = _case(seed, n)
     step = 0.3 * s * (np.random.default_rng(seed).random(len(x)) < 0.2)
     moved = np.clip(x + step, lb, ub)                              # some points onto the bounds
     want = common.make_strictly_feasible(moved, lb, ub, rstep=0)
@@ -112,12 +119,11 @@ def test_make_strictly_feasible_and_in_bounds(V, seed):
     assert np.array_equal(_h(got2), common.make_strictly_feasible(x2, lb2, ub2, rstep=0))
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_start_point_and_first_radius(V, seed):
+def _start_point_and_first_radius(V, seed, n):
     """trf_bounds before its loop: make_strictly_feasible(x0, lb, ub) with the default rstep, and
     Delta = norm(x0 * scale_inv / v**0.5)"""
     from scipy.optimize._lsq import common
-    x, lb, ub, g, _ = _case(seed)
+    x, lb, ub, g, _ = _case(seed, n)
     rng = np.random.default_rng(50 + seed)
     # points on, just inside (within rstep) and outside their bounds
     ubf = np.where(np.isfinite(ub), ub, 0.0)
@@ -125,12 +131,15 @@ def test_start_point_and_first_radius(V, seed):
                  ubf - rng.uniform(0, 2e-10, len(x)) * np.maximum(1, np.abs(ubf)), x)
     x = np.where(rng.random(len(x)) < 0.05, x + 10.0, x)
     k = int(np.nonzero(np.isfinite(ub) & np.isfinite(lb))[0][0])
-    lb[k] = ub[k] = x[k] = -2.5                                    # a degenerate box
+    if n > 1:
+        lb[k] = ub[k] = x[k] = -2.5                                # a degenerate box
+    else:
+        x[k] = ub[k]                                               # (one element: on its bound, it has to move)
     want = common.make_strictly_feasible(x, lb, ub)
     tx, tlb, tub, tg = _t(V, x, lb, ub, g)
     got = V.feasible_start(tx, tlb, tub, 1e-10)
     assert np.array_equal(_h(got), want)
-    assert (want != x).sum() > 100
+    assert (want != x).sum() >= min(101, max(n // 40, 1))  # (> 100 at n = 40000; ~7 % of the elements move)
     v, dv = common.CL_scaling_vector(want, g, lb, ub)
     scale_inv = rng.uniform(0.1, 30, len(x))
     v[dv != 0] *= scale_inv[dv != 0]
@@ -144,10 +153,9 @@ def test_start_point_and_first_radius(V, seed):
     assert np.isclose(np.sqrt(V.dots((tf, tf))[0]), np.linalg.norm(t[fin]), rtol=1e-13)
 
 
-@pytest.mark.parametrize('seed', range(4))
-def test_find_active_constraints(V, seed):
+def _find_active_constraints(V, seed, n):
     from scipy.optimize._lsq import common
-    x, lb, ub, _, _ = _case(seed)
+    x, lb, ub, _, _ = _case(seed, n)
     rng = np.random.default_rng(100 + seed)
     near = rng.random(len(x)) < 0.2
     lbf = np.where(np.isfinite(lb), lb, 0.0)
@@ -155,12 +163,11 @@ def test_find_active_constraints(V, seed):
     want = common.find_active_constraints(x, lb, ub, rtol=1e-8)
     got = V.active_constraints(*_t(V, x, lb, ub), 1e-8)
     assert np.array_equal(_h(got).astype(int), want)
-    assert (want != 0).any() and (want == 0).any()
+    assert n == 1 or ((want != 0).any() and (want == 0).any())
 
 
-def test_linear_combinations_products_sums_and_jac_scale(V):
+def _linear_combinations_products_sums_and_jac_scale(V, n):
     rng = np.random.default_rng(9)
-    n = 123457                                                     # not a multiple of anything
     a, b, c, w = (rng.normal(size=n) for _ in range(4))
     ta, tb, tc, tw = _t(V, a, b, c, w)
     assert np.array_equal(_h(V.lincomb(2.5, ta)), 2.5 * a)
@@ -173,10 +180,11 @@ def test_linear_combinations_products_sums_and_jac_scale(V):
     want = [a @ b, (a * w) @ b, c @ c, a @ a, b @ b, w @ w, a @ c, b @ c]
     assert np.allclose(got, want, rtol=1e-12, atol=1e-9)
     assert V.dots((ta, tb)) == V.dots((ta, tb))                    # fixed tree: reproducible
-    assert V.dots((ta, tb), n=1000)[0] == pytest.approx(a[:1000] @ b[:1000], rel=1e-12)
+    m = min(1000, n)
+    assert V.dots((ta, tb), n=m)[0] == pytest.approx(a[:m] @ b[:m], rel=1e-12)
     assert V.absmax(ta) == np.abs(a).max() and V.absmax(ta, tb) == np.abs(a * b).max()
     bad = a.copy()
-    bad[77777] = np.nan
+    bad[min(77777, n - 1)] = np.nan
     assert np.isnan(V.absmax(_t(V, bad)[0]))
     # compute_jac_scale: first call (zeros -> 1), later calls keep the maximum
     colsq = rng.uniform(0, 4, n)
@@ -189,3 +197,68 @@ def test_linear_combinations_products_sums_and_jac_scale(V):
     colsq2 = rng.uniform(0, 4, n)
     V.jac_scale(_t(V, colsq2)[0], si, first=False)
     assert np.array_equal(_h(si), np.maximum(want, colsq2 ** 0.5))
+
+
+# ---- the tests: n = 40000 (123457 for the last one) under their original names, then the lengths ----
+@seeds
+def test_cl_scaling_vector_and_scaled_quantities(V, seed):
+    _cl_scaling_vector_and_scaled_quantities(V, seed, 40000)
+
+
+@seeds
+def test_step_size_to_bound_and_reflection(V, seed):
+    _step_size_to_bound_and_reflection(V, seed, 40000)
+
+
+@seeds
+def test_make_strictly_feasible_and_in_bounds(V, seed):
+    _make_strictly_feasible_and_in_bounds(V, seed, 40000)
+
+
+@seeds
+def test_start_point_and_first_radius(V, seed):
+    _start_point_and_first_radius(V, seed, 40000)
+
+
+@seeds
+def test_find_active_constraints(V, seed):
+    _find_active_constraints(V, seed, 40000)
+
+
+def test_linear_combinations_products_sums_and_jac_scale(V):
+    _linear_combinations_products_sums_and_jac_scale(V, 123457)        # not a multiple of anything
+
+
+@lengths
+@seeds
+def test_cl_scaling_vector_and_scaled_quantities_lengths(V, seed, n):
+    _cl_scaling_vector_and_scaled_quantities(V, seed, n)
+
+
+@lengths
+@seeds
+def test_step_size_to_bound_and_reflection_lengths(V, seed, n):
+    _step_size_to_bound_and_reflection(V, seed, n)
+
+
+@lengths
+@seeds
+def test_make_strictly_feasible_and_in_bounds_lengths(V, seed, n):
+    _make_strictly_feasible_and_in_bounds(V, seed, n)
+
+
+@lengths
+@seeds
+def test_start_point_and_first_radius_lengths(V, seed, n):
+    _start_point_and_first_radius(V, seed, n)
+
+
+@lengths
+@seeds
+def test_find_active_constraints_lengths(V, seed, n):
+    _find_active_constraints(V, seed, n)
+
+
+@pytest.mark.parametrize('n', LENGTHS + [40000])
+def test_linear_combinations_products_sums_and_jac_scale_lengths(V, n):
+    _linear_combinations_products_sums_and_jac_scale(V, n)
