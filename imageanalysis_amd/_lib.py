@@ -175,6 +175,8 @@ SIGNATURES = {
                               + [c_int, c_int, c_int, c_void_p]),
     'iamx_ba_schur_finish': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_int]
                              + [c_void_p] * 8),
+    'iamx_ba_robust_cost': (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    'iamx_ba_robust_scale': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_double, c_void_p]),
     'iamx_comm_unique_id': (c_int, [c_void_p]),
     'iamx_comm_init': (c_int, [c_int, c_int, c_void_p, c_void_p]),
     'iamx_comm_destroy': (c_int, [c_void_p]),

@@ -19,6 +19,7 @@ ba_linalg.hip):
     g = J^T f, ||J_j||  iamx_ba_jtv (square=0 / 1)
     LSMR                iamx_ba_jv / iamx_ba_jtv + iamx_vec_* (scipy/sparse/linalg/_isolve/lsmr.py)
     quadratic models    Gram matrices of J_h s_i  (iamx_ba_jv + iamx_vec_dot)
+    loss= / f_scale=    iamx_ba_robust_cost, iamx_ba_robust_scale (csrc/ba_robust.hip)
 
 Multi-GPU: observations are sharded by point (dist.shard_observations_by_point); m-vectors are
 rank-local, n-vectors replicated; J^T u and every m-dot are summed over ranks (RCCL all-reduce).
@@ -33,6 +34,20 @@ from . import _lib, dist as _dist
 from ._lib import check, lib, stream_ptr
 
 F64, I32 = torch.float64, torch.int32
+
+# least_squares(loss=): the robust loss functions of SciPy (construct_loss_function) and their ids
+# in include/iamx.h; 'linear' is the plain sum of squares and runs none of the robust code
+LOSSES = {'linear': 0, 'huber': 1, 'soft_l1': 2, 'cauchy': 3, 'arctan': 4}
+
+
+def check_loss(loss, f_scale):
+    """ValueError for what least_squares(loss=, f_scale=) would refuse (before any device work)"""
+    if loss not in LOSSES:
+        raise ValueError("`loss` must be one of %s, not %r" % (', '.join(LOSSES), loss))
+    f_scale = float(f_scale)
+    if not (np.isfinite(f_scale) and f_scale > 0):
+        raise ValueError("`f_scale` must be positive and finite, not %r" % (f_scale,))
+    return loss, f_scale
 
 
 def _ptr(t):
@@ -163,6 +178,9 @@ class DeviceBA(object):
         # of every n-vector stays on the rank that owns the points (zeros elsewhere), only the
         # camera part and scalars are reduced inside the outer loop (set by _trf_device)
         self.local_points = False
+        # least_squares(loss=, f_scale=): 'linear' (default), 'huber', 'soft_l1', 'cauchy', 'arctan'
+        self.loss = 'linear'
+        self.f_scale = 1.0
         self._calib_idx = None
         self._fixed_calib_up = False
 
@@ -333,6 +351,16 @@ class DeviceBA(object):
                   'iamx_ba_residual_jac')
         return self.r
 
+    def robust_scale(self):
+        """scale_for_robust_loss_function on what residual_jac() left on the device: from the
+        UNSCALED residuals, r *= rho' / sqrt(J_scale) and the rows of Jc / Jp / Jk *= sqrt(J_scale),
+        in place (this rank's observations; nothing crosses ranks).  Take the cost first."""
+        self._acc_valid = False
+        if self.O:
+            check(lib().iamx_ba_robust_scale(_ptr(self.r), _ptr(self.Jc), _ptr(self.Jp), _ptr(self.Jk),
+                                             self.O, LOSSES[self.loss], float(self.f_scale),
+                                             stream_ptr()), 'iamx_ba_robust_scale')
+
     def jv(self, x_dev, y_dev):
         if self.O:
             check(lib().iamx_ba_jv(_ptr(self.Jc), _ptr(self.Jp), _ptr(self.Jk), _ptr(self.cam_idx),
@@ -374,7 +402,16 @@ class DeviceBA(object):
 
     # ---- composite operations --------------------------------------------------------
     def cost_of_r(self, r):
+        if self.loss != 'linear':
+            V = self.vec_ops()
+            V.begin()
+            at = self.q_cost(r)
+            return self.cost_from(V.fetch()[at])
         return 0.5 * self.dot(r, r, self.m, True)
+
+    def cost_from(self, s):
+        """the cost from what q_cost() queued: 0.5 r.r, or 0.5 C^2 sum rho((r / C)^2)"""
+        return 0.5 * s if self.loss == 'linear' else 0.5 * self.f_scale * self.f_scale * s
 
     def grad(self):
         """J^T r -> host n-vector."""
@@ -458,8 +495,26 @@ class DeviceBA(object):
         return self.q_pairs(*[(ys[i], ys[j]) for i in range(k) for j in range(i, k)])
 
     def q_cost(self, r):
-        """queue r.r over this rank's observations, summed over the ranks (cost = half of it)"""
+        """queue r.r over this rank's observations, summed over the ranks (cost = half of it);
+        with a robust loss sum rho((r / C)^2) of the unscaled residuals r (cost_from())"""
+        if self.loss != 'linear':
+            return self.q_robust(r)
         return self.q_gram([r[:self.m]])
+
+    def q_robust(self, r):
+        """queue sum rho((r / f_scale)^2) over this rank's observations, summed over the ranks like
+        q_pairs (fixed reduction tree on a rank: the same bits every time)"""
+        V = self.vec_ops()
+        if not self.m:
+            at = V.q_zero(1)
+        else:
+            at = V._take(1)
+            check(lib().iamx_ba_robust_cost(_ptr(r), self.m, LOSSES[self.loss], float(self.f_scale),
+                                            V._slot_ptr(at), _ptr(V.scratch), stream_ptr()),
+                  'iamx_ba_robust_cost')
+        if self.world > 1:
+            _dist.allreduce_sum_(V.out[at:at + 1])
+        return at
 
     @staticmethod
     def gram_of(vals, at, k):
@@ -935,7 +990,10 @@ def lsmr(prob, d_dev, dreg_dev, **opts):
     if prob.inner == 'schur' and prob.C and (prob.O or prob.world > 1):
         # (with calibration columns: the bordered form, csrc/ba_schur.hip)
         return schur_solve(prob, d_dev, dreg_dev, to_host=opts.get('to_host', True))
-    if not prob.with_calib and not prob.force_stepwise_lsmr and (prob.O or prob.world > 1):
+    # (the fused form is matrix free: it re-derives J from the parameters and would not see the
+    #  rows a robust loss has scaled -- those solves take the stepwise form on the stored blocks)
+    if (not prob.with_calib and not prob.force_stepwise_lsmr and prob.loss == 'linear'
+            and (prob.O or prob.world > 1)):
         r = lsmr_device_fused(prob, d_dev, dreg_dev, **opts)
     else:
         r = lsmr_device(prob, d_dev, dreg_dev, **opts)
@@ -1007,15 +1065,20 @@ def _select_step(prob, x, d, diag_h, g_h, p, p_h, Delta, lb, ub, theta, d_dev=No
     return ag, ag_h, -ag_value
 
 
-def trf_device(prob, x0, lb, ub, **kw):
-    """scipy/optimize/_lsq/trf.py trf_bounds with tr_solver='lsmr', x_scale='jac',
-    loss='linear', on a DeviceBA problem.
+def trf_device(prob, x0, lb, ub, loss=None, f_scale=None, **kw):
+    """scipy/optimize/_lsq/trf.py trf_bounds with tr_solver='lsmr', x_scale='jac', on a DeviceBA
+    problem.  loss / f_scale as in least_squares (default: prob.loss = 'linear', prob.f_scale): with
+    a robust loss the cost is 0.5 C^2 sum rho((f / C)^2) and every Jacobian evaluation is followed by
+    SciPy's row scaling (DeviceBA.robust_scale); they stay set on `prob`.  prob.r holds the SCALED
+    residuals afterwards: evaluate prob.residual() for the true ones (solve() does).
 
     The host-side O(n) vector algebra runs with the BLAS thread pool limited to one thread: a
     multi-threaded np.dot/norm leaves ~100 OpenBLAS workers spinning for a while, and the
     device queue then stalls 60-90 ms in the next LSMR solve (measured, tools/diag_stall2.py;
     profiles/r1_ba_notes.txt).  The vectors are memory-bound; one thread loses nothing."""
     fn = _trf_host if prob.host_logic else _trf_device
+    prob.loss, prob.f_scale = check_loss(prob.loss if loss is None else loss,
+                                         prob.f_scale if f_scale is None else f_scale)
     with _lib.hold_stream():              # (one stream for the whole solve; see _lib.hold_stream)
         try:
             from threadpoolctl import threadpool_limits
@@ -1039,10 +1102,13 @@ def _trf_host(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, 
     lsmr_opts = dict(lsmr_opts or {})
     n = prob.n
     x = make_strictly_feasible(np.asarray(x0, np.float64).copy(), lb, ub)
+    robust = prob.loss != 'linear'
     prob.set_x(x)
     prob.residual_jac()
     nfev = njev = 1
     cost = prob.cost_of_r(prob.r)
+    if robust:
+        prob.robust_scale()               # (after the cost: it is taken from the unscaled residuals)
     g = prob.grad()
     scale_inv = prob.colnorm()
     scale_inv[scale_inv == 0] = 1
@@ -1134,6 +1200,8 @@ def _trf_host(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, 
                 x = x_new
                 cost = cost_new                   # (the device already holds x_new: the accepted
                 prob.residual_jac()               #  trial was the last one evaluated)
+                if robust:
+                    prob.robust_scale()
                 njev += 1
                 g = prob.grad()
                 cn = prob.colnorm()
@@ -1142,6 +1210,8 @@ def _trf_host(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None, 
             if callback is not None:
                 callback(x, cost)
         else:
+            # (only reached with a termination status or nfev == max_nfev: the loop ends at its
+            #  next test, before anything reads prob.r -- which holds the unscaled residuals now)
             prob.set_x(x)
             prob.residual()
             step_norm = 0
@@ -1523,12 +1593,15 @@ def _trf_device(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None
         V.part = (prob.rank, nc, np3)
     else:
         V.part = None
+    robust = prob.loss != 'linear'
     prob.set_x_dev(x)
     prob.residual_jac()
     nfev = njev = 1
     V.begin()
     prob.q_cost(prob.r)
-    cost = 0.5 * V.fetch()[0]
+    cost = prob.cost_from(V.fetch()[0])
+    if robust:
+        prob.robust_scale()               # (after the cost: it is taken from the unscaled residuals)
     g = prob.grad_dev()
     scale_inv = V.jac_scale(prob.colsq_dev(), torch.empty(n, dtype=F64, device=prob.dev), first=True)
 
@@ -1634,7 +1707,7 @@ def _trf_device(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None
                 i_c = prob.q_cost(r_new)
                 S = V.fetch()
                 step_h_norm = float(np.sqrt(S[i_s]))
-                cost_new = 0.5 * S[i_c]
+                cost_new = prob.cost_from(S[i_c])
             if not np.isfinite(cost_new):
                 Delta = 0.25 * step_h_norm
                 continue
@@ -1653,12 +1726,16 @@ def _trf_device(prob, x0, lb, ub, ftol=1e-4, xtol=1e-8, gtol=1e-8, max_nfev=None
                 x = x_new
                 cost = cost_new                   # (the device already holds x_new: the accepted
                 prob.residual_jac()               #  trial was the last one evaluated)
+                if robust:
+                    prob.robust_scale()           # before accumulate() / grad / colsq read r and J
                 njev += 1
                 g = prob.grad_dev()
                 V.jac_scale(prob.colsq_dev(), scale_inv, first=False)       # compute_jac_scale
             if callback is not None:
                 callback(prob.download_n(x), cost)
         else:
+            # (only reached with a termination status or nfev == max_nfev: the loop ends at its
+            #  next test, before anything reads prob.r -- which holds the unscaled residuals now)
             prob.set_x_dev(x)
             prob.residual()
             step_norm = 0
@@ -1704,9 +1781,12 @@ def gather_residual(prob, n_obs_total):
     return full
 
 
-def solve(opt, x0, bounds, ftol=1e-4, verbose=0, max_nfev=None, inner=None):
+def solve(opt, x0, bounds, ftol=1e-4, verbose=0, max_nfev=None, inner=None, loss='linear',
+          f_scale=1.0):
     """Entry point used by Optimizer.run() when opt.solver is 'device' (inner='schur') or
-    'device-lsmr' (inner='lsmr')."""
+    'device-lsmr' (inner='lsmr').  loss / f_scale as in least_squares: res.cost is the robust
+    cost, res.fun the true (unscaled) residual."""
+    loss, f_scale = check_loss(loss, f_scale)
     rank, world = _dist.world()
     n = x0.size
     if isinstance(bounds, (list, tuple)) and np.ndim(bounds[0]) > 0:
@@ -1722,7 +1802,8 @@ def solve(opt, x0, bounds, ftol=1e-4, verbose=0, max_nfev=None, inner=None):
                     fixed_calib=fixed, rank=rank, world=world)
     if inner is not None:
         prob.inner = inner
-    res = trf_device(prob, x0, lb, ub, ftol=ftol, verbose=verbose, max_nfev=max_nfev)
+    res = trf_device(prob, x0, lb, ub, ftol=ftol, verbose=verbose, max_nfev=max_nfev, loss=loss,
+                     f_scale=f_scale)
     res.inner_solver = prob.inner
     prob.set_x(res.x)
     prob.residual()

@@ -8,7 +8,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 OUT="$HERE/../libiamx.so"
 OBJDIR="$HERE/obj"
-SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip $HERE/ortho_raster.hip"
+SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/ba_robust.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip $HERE/ortho_raster.hip"
 mkdir -p "$OBJDIR"
 OBJS=""
 for f in $SRCS; do
@@ -17,6 +17,8 @@ for f in $SRCS; do
         EXTRA=""
         # the TRF helpers restate numpy expressions: separately rounded multiply and add
         [ "$(basename $f)" = "trf_vec.hip" ] && EXTRA="-ffp-contract=off"
+        # the robust loss factors restate numpy expressions (tests/robust_loss_restatement.py), operation by operation
+        [ "$(basename $f)" = "ba_robust.hip" ] && EXTRA="-ffp-contract=off"
         # the area downscale restates OpenCV's tap table in doubles, operation by operation
         [ "$(basename $f)" = "image_area.hip" ] && EXTRA="-ffp-contract=off"
         # the radial moments and the fitted mask restate Python's double expressions, operation by operation

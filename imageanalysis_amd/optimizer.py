@@ -104,6 +104,11 @@ class Optimizer():
         # solver, LSMR on the whole system (the reference's formulation, ~10x more inner
         # iterations); 'scipy': SciPy's own TRF driven by the device residual / analytic Jacobian
         self.solver = 'device'
+        # least_squares(loss=, f_scale=) for every solver: 'linear' (default, the reference's),
+        # 'huber', 'soft_l1', 'cauchy', 'arctan'; f_scale in pixels (the residual at which the
+        # loss bends).  Meant for a --refine pass after a linear solve.
+        self.loss = 'linear'
+        self.f_scale = 1.0
         self._dev = None
 
     # ---------------------------------------------------------------------------------
@@ -396,6 +401,8 @@ class Optimizer():
         return [lower, upper]
 
     def run(self):
+        from .ba_solver import check_loss
+        loss, f_scale = check_loss(self.loss, self.f_scale)       # (ValueError before any device work)
         x0 = self._x0()
         args = (self.n_cameras, self.n_points, self.by_camera_point_indices,
                 self.by_camera_points_2d)
@@ -407,12 +414,13 @@ class Optimizer():
         if self.solver in ('device', 'device-lsmr'):
             from . import ba_solver
             res = ba_solver.solve(self, x0, bounds, ftol=self.ftol, verbose=2,
-                                  inner='schur' if self.solver == 'device' else 'lsmr')
+                                  inner='schur' if self.solver == 'device' else 'lsmr',
+                                  loss=loss, f_scale=f_scale)
         else:
             from scipy.optimize import least_squares
             res = least_squares(self.fun, x0, jac=self.jac, verbose=2, method='trf',
-                                loss='linear', ftol=self.ftol, x_scale='jac', bounds=bounds,
-                                args=args)
+                                loss=loss, f_scale=f_scale, ftol=self.ftol, x_scale='jac',
+                                bounds=bounds, args=args)
         t1 = time.time()
         _log("Optimization took %.1f seconds" % (t1 - t0))
         _log("res:", res)
@@ -434,6 +442,8 @@ class Optimizer():
         mre_final = np.mean(np.abs(res.fun))
         _log("Starting mean reprojection error: %.2f" % mre_start)
         _log("Final mean reprojection error: %.2f" % mre_final)
+        if loss != 'linear':
+            _log("Loss: %s, f_scale: %g px, final robust cost: %.6g" % (loss, f_scale, res.cost))
         _log("Iterations:", res.njev)
         if getattr(res, 'inner_solver', None):
             # which linear solver produced the Gauss-Newton steps (the reference's least_squares

@@ -18,6 +18,10 @@ ap.add_argument('--cam-calibration', action='store_true',
                 help='include camera calibration in the optimization.')
 ap.add_argument('--solver', default='device', choices=['device', 'device-lsmr', 'scipy'],
                 help="'device' (default, like Optimizer.solver): GPU-resident TRF, Schur-complement subproblem solver; 'device-lsmr': the same with SciPy's LSMR formulation; 'scipy': SciPy TRF fed with the device residual/Jacobian")
+ap.add_argument('--loss', default='linear', choices=['linear', 'huber', 'soft_l1', 'cauchy', 'arctan'],
+                help="least_squares loss function (default 'linear', the reference's).  A robust loss is meant for --refine after a linear solve; 'soft_l1' is the one that keeps every observation in the Gauss-Newton model")
+ap.add_argument('--f-scale', type=float, default=1.0, metavar='PX',
+                help='residual (pixels) at which a robust loss bends (least_squares f_scale; ignored by --loss linear)')
 args = ap.parse_args()
 
 proj = project.ProjectMgr(args.project)
@@ -31,6 +35,7 @@ group_list = groups.load(proj.analysis_dir)
 
 opt = optimizer.Optimizer(args.project)
 opt.solver = args.solver
+opt.loss, opt.f_scale = args.loss, args.f_scale
 opt.setup(proj, group_list, args.group, matches, optimized=args.refine,
           cam_calib=args.cam_calibration)
 cameras, features, cam_index_map, feat_index_map, fx_opt, fy_opt, cu_opt, cv_opt, distCoeffs_opt \

@@ -1085,6 +1085,26 @@ int iamx_ba_schur_finish(const double *Jc, const double *Jp, const double *Jk,
                          double *step, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Robust loss functions of the bundle adjustment (csrc/ba_robust.hip) -- the loss= / f_scale= of
+ * scipy.optimize.least_squares (construct_loss_function, scale_for_robust_loss_function), per
+ * scalar residual component f with C = f_scale, z = (f / C)^2:
+ *   iamx_ba_robust_cost: out[0] = sum rho(z) over r DEV [m] (cost = 0.5 C^2 out[0]); fixed grid and
+ *     fixed reduction tree, no atomics: two calls give the same bits.  scratch DEV [256] float64.
+ *   iamx_ba_robust_scale: in place, from the unscaled residuals of r DEV [n_obs][2]:
+ *     J_scale = max(rho' + 2 rho'' z, 2^-52);  f *= rho' / sqrt(J_scale);  the row of f in Jc DEV
+ *     [n_obs][2][7], Jp DEV [n_obs][2][3] and Jk DEV [n_obs][2][8] (may be NULL) *= sqrt(J_scale).
+ *     All four 16-byte aligned (any n_obs: an observation owns an even number of doubles in each).
+ * loss is one of IAMX_LOSS_HUBER .. IAMX_LOSS_ARCTAN (IAMX_LOSS_LINEAR needs neither call and is
+ * refused); f_scale finite and > 0.  Argument checks need no GPU.
+ * ------------------------------------------------------------------------------------ */
+enum { IAMX_LOSS_LINEAR = 0, IAMX_LOSS_HUBER = 1, IAMX_LOSS_SOFT_L1 = 2, IAMX_LOSS_CAUCHY = 3,
+       IAMX_LOSS_ARCTAN = 4 };
+int iamx_ba_robust_cost(const double *r, int64_t m, int loss, double f_scale, double *out,
+                        double *scratch, void *stream);
+int iamx_ba_robust_scale(double *r, double *Jc, double *Jp, double *Jk, int64_t n_obs, int loss,
+                         double f_scale, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Collectives of the hot path for callers that are not python: RCCL over
  * xGMI, bound at run time (a process that already holds an RCCL -- torch bundles one -- re-uses
  * it).  The python layer does the same two exchanges through torch.distributed.
