@@ -214,6 +214,9 @@ SIGNATURES = {
     'iamx_ortho_raster_image': (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]
                                 + [c_int] * 7 + [c_void_p] * 5),
     'iamx_ortho_resolve': (c_int, [c_int, c_int] + [c_void_p] * 4),
+    'iamx_verify_pairs': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int,
+                                  ctypes.c_uint64] + [c_void_p] * 5),
+    'iamx_verify_sample': (c_int, [c_int64, c_int, c_int64, ctypes.c_uint64, c_void_p]),
 }
 
 

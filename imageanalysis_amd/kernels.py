@@ -628,6 +628,44 @@ def ba_mark_outliers(e, summary, trim_stddev, max_error=None, cap=None):
 
 
 # --------------------------------------------------------------------------------------
+# RANSAC verification of pair matches (csrc/match_verify.hip)
+# --------------------------------------------------------------------------------------
+VERIFY_MODELS = {'homography': 0, 'fundamental': 1}
+VERIFY_OK, VERIFY_TOO_FEW, VERIFY_NO_MODEL = 0, 1, 2
+
+
+def verify_pairs(pts, m_off, model, tol, hypotheses=2048, seed=0):
+    """pts [total, 4] float32 (x1 y1 x2 y2, undistorted pixels), m_off [n_pairs + 1] int64, model
+    'homography' | 'fundamental' (or the ABI's number), tol [n_pairs] float64 pixels (or one number
+    for all pairs).  Returns device tensors (mask uint8 [total], model f64 [n_pairs, 3, 3],
+    best int32 [n_pairs, 2] = hypothesis, inlier count, status int32 [n_pairs]); stream ordered,
+    nothing is synchronised."""
+    dev = require_gpu()
+    code = VERIFY_MODELS.get(model, model)
+    if code not in (0, 1):
+        raise ValueError("verify_pairs: model must be 'homography' or 'fundamental', not %r" % (model,))
+    pts = _dev(pts, torch.float32).reshape(-1, 4)
+    m_off = _dev(m_off, I64).reshape(-1)
+    n_pairs, total = m_off.numel() - 1, pts.shape[0]
+    if n_pairs < 0:
+        raise ValueError("verify_pairs: m_off needs n_pairs + 1 entries")
+    if np.ndim(tol) == 0 and not isinstance(tol, torch.Tensor):
+        tol = torch.full((max(n_pairs, 1),), float(tol), dtype=F64, device=dev)
+    tol = _dev(tol, F64).reshape(-1)
+    if tol.numel() < n_pairs:
+        raise ValueError("verify_pairs: one tolerance per pair")
+    mask = torch.empty(max(total, 1), dtype=U8, device=dev)
+    out_model = torch.empty((max(n_pairs, 1), 3, 3), dtype=F64, device=dev)
+    best = torch.empty((max(n_pairs, 1), 2), dtype=I32, device=dev)
+    status = torch.empty(max(n_pairs, 1), dtype=I32, device=dev)
+    check(lib().iamx_verify_pairs(_ptr(pts), _ptr(m_off), n_pairs, total, code, _ptr(tol),
+                                  int(hypotheses), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask),
+                                  _ptr(out_model), _ptr(best), _ptr(status), stream_ptr()),
+          'iamx_verify_pairs')
+    return mask[:total], out_model[:n_pairs], best[:n_pairs], status[:n_pairs]
+
+
+# --------------------------------------------------------------------------------------
 # a reusable, allocation-free batch of ordered pairs: knn2 -> metric -> scan -> compaction
 # --------------------------------------------------------------------------------------
 class PairWorkspace(object):

@@ -1371,7 +1371,10 @@ def _camera_size():
 
 
 def find_matches(proj, K, strategy="smart", transform="homography", sort=False, review=False):
-    """transform / review are accepted and unused, as on the reference's live path.
+    """transform / review are accepted and unused, as on the reference's live path.  What
+    `--filter` asks for (the RANSAC homography / fundamental filter of filter_by_transform) is a
+    pass of its own over the stored match lists: verify_matches() below, run by
+    scripts/3a-verify-matches.py after this call and before 3b.
 
     With torch.distributed initialised (one process per GPU) the pairs that still need
     matching are dealt to the ranks in contiguous blocks (dist.shard_pairs); after every round
@@ -2265,3 +2268,222 @@ def saveMatches(image_list, check_if_dirty=False):
                 image.save_matches()
         else:
             image.save_matches()
+
+
+# --------------------------------------------------------------------------------------
+# geometric verification of stored match lists (scripts/lib/matcher.py:90-142)
+# --------------------------------------------------------------------------------------
+VERIFY_BATCH_MATCHES = 1 << 22          # matches per launch of verify_matches (64 MiB of points)
+_ESSENTIAL_REASON = ("transform 'essential' needs the five-point solver, which this package does not "
+                     "have; eight points projected onto the essential manifold are no stand-in on "
+                     "planar ground.  Use 'fundamental' or 'homography'.")
+
+
+def _verify_transform(transform):
+    if transform == 'essential':
+        raise NotImplementedError(_ESSENTIAL_REASON)
+    if transform not in ('homography', 'fundamental', 'none'):
+        raise ValueError("transform must be 'homography', 'fundamental', 'essential' or 'none', "
+                         "not %r" % (transform,))
+    return transform
+
+
+def _verify_tol(image):
+    """max(1, width ** 0.25) pixels (lib/matcher.py:94).  The reference reads i1.width, which its
+    Image class no longer has; where the attribute is missing the camera's image width stands in."""
+    width = getattr(image, 'width', None)
+    if not width:
+        width = _deps.camera().get_image_params()[0]
+    return max(1.0, float(width) ** 0.25)
+
+
+def _pairs_of(matches):
+    if isinstance(matches, MatchPairs):
+        return matches.array()
+    return np.asarray(matches, np.int32).reshape(-1, 2)
+
+
+def _uv_of(image):
+    """the image's undistorted keypoints, float32 [n, 2] (made on the device where they are missing)"""
+    uv = getattr(image, 'uv_list', None)
+    if uv is None or len(uv) == 0:
+        from . import undistort
+        undistort.undistort_image_keypoints(None, image)
+        uv = image.uv_list
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    return uv
+
+
+def _keep_rows(matches, keep):
+    """the rows of a match list where keep is set, order kept, IN PLACE (a MatchPairs stays
+    array-backed); returns the number removed"""
+    keep = np.asarray(keep, bool)
+    removed = int(len(keep) - keep.sum())
+    if removed:
+        if isinstance(matches, MatchPairs):
+            matches[:] = matches.array()[keep]
+        else:
+            matches[:] = [m for m, k in zip(matches, keep.tolist()) if k]
+    return removed
+
+
+def _pair_keys(a):
+    return (a[:, 0].astype(np.int64) << 32) | (a[:, 1].astype(np.int64) & 0xFFFFFFFF)
+
+
+def filter_by_transform(K, i1, i2, transform, hypotheses=2048, seed=0):
+    """The reference's filter for one direction of one pair: RANSAC on the undistorted keypoints of
+    i1.match_list[i2.name] with tolerance max(1, width ** 0.25) pixels, outliers removed in place.
+    Returns True when nothing was removed.  K is unused by the two models that exist here."""
+    from . import kernels
+    _verify_transform(transform)
+    matches = i1.match_list[i2.name]
+    n = len(matches)
+    if n < min_pairs:
+        i1.match_list[i2.name] = []
+        return True
+    if transform == 'none':
+        _log("  %s vs %s: %d / %d  inliers/matched" % (i1.name, i2.name, n, n))
+        return True
+    pairs = _pairs_of(matches)
+    uv1, uv2 = _uv_of(i1), _uv_of(i2)
+    if pairs.min() < 0 or pairs[:, 0].max() >= len(uv1) or pairs[:, 1].max() >= len(uv2):
+        raise ValueError("%s vs %s: a match names a keypoint that does not exist" % (i1.name, i2.name))
+    pts = np.concatenate([uv1[pairs[:, 0]], uv2[pairs[:, 1]]], axis=1)
+    mask, _model, _best, status = kernels.verify_pairs(pts, np.array([0, n], np.int64), transform,
+                                                       _verify_tol(i1), hypotheses, seed)
+    keep = mask.cpu().numpy().astype(bool)
+    st = int(status.cpu()[0])
+    if st == kernels.VERIFY_TOO_FEW:
+        _log("  %s vs %s: %d matches are fewer than a sample, list kept" % (i1.name, i2.name, n))
+        return True
+    if st == kernels.VERIFY_NO_MODEL:
+        _log("  %s vs %s: no model, list emptied" % (i1.name, i2.name))
+    _log("  %s vs %s: %d / %d  inliers/matched" % (i1.name, i2.name, int(keep.sum()), n))
+    removed = _keep_rows(matches, keep)
+    if removed:
+        i1.matches_clean = False
+    return removed == 0
+
+
+def _verify_launch(jobs, transform, hypotheses, seed, arena):
+    """masks and statuses of a batch of jobs (a, b, pairs, tol): ONE launch, the points gathered on
+    the device from the keypoint arena.  The seam of verify_matches: tests hand in their own."""
+    import torch
+    from . import kernels
+    uv, base = arena
+    lens = [len(j[2]) for j in jobs]
+    m_off = np.zeros(len(jobs) + 1, np.int64)
+    np.cumsum(lens, out=m_off[1:])
+    i1 = np.concatenate([base[j[0]] + j[2][:, 0].astype(np.int64) for j in jobs])
+    i2 = np.concatenate([base[j[1]] + j[2][:, 1].astype(np.int64) for j in jobs])
+    dev = uv.device
+    pts = torch.cat([uv[torch.from_numpy(i1).to(dev)], uv[torch.from_numpy(i2).to(dev)]], dim=1)
+    tol = np.array([j[3] for j in jobs], np.float64)
+    mask, _model, _best, status = kernels.verify_pairs(pts, m_off, transform, tol, hypotheses, seed)
+    mask, status = mask.cpu().numpy(), status.cpu().numpy()
+    return [mask[m_off[k]:m_off[k + 1]] for k in range(len(jobs))], status.tolist()
+
+
+def _verify_arena(proj):
+    """every image's undistorted keypoints as one device array, and each image's first row"""
+    import torch
+    from ._lib import require_gpu
+    uvs = [_uv_of(im) if (im.kp_list is not None and len(im.kp_list)) or
+           (getattr(im, 'uv_list', None) is not None and len(im.uv_list)) else np.zeros((0, 2), np.float32)
+           for im in proj.image_list]
+    base = np.zeros(len(uvs) + 1, np.int64)
+    np.cumsum([len(u) for u in uvs], out=base[1:])
+    cat = np.concatenate(uvs) if uvs else np.zeros((0, 2), np.float32)
+    return torch.from_numpy(np.ascontiguousarray(cat)).to(require_gpu()), base
+
+
+def verify_matches(proj, K, transform, hypotheses=2048, seed=0, launch=None):
+    """The geometric filter over a whole project's stored match lists, after find_matches and
+    before 3b: every unordered pair (a before b in proj.image_list) with a non-empty
+    a.match_list[b.name] goes through iamx_verify_pairs, in batches of at most VERIFY_BATCH_MATCHES
+    matches, one launch each.  The forward list keeps the mask's inliers; b.match_list[a.name], where
+    it exists, keeps in its own order the [j, i] whose [i, j] survived (entries that never had a
+    forward counterpart are dropped and counted).  A list with fewer than min_pairs matches is
+    emptied, in either direction, as the reference's filter does.  Running it twice filters twice.
+    Single process; nothing is saved here.  `launch(jobs, transform, hypotheses, seed, arena)`
+    replaces the device launch (tests).  Returns the counts."""
+    _verify_transform(transform)
+    counts = dict(pairs=0, matches_in=0, matches_out=0, lists_emptied=0, too_few=0, no_model=0,
+                  orphans_dropped=0)
+    if transform == 'none':
+        return counts
+    images = list(proj.image_list)
+    jobs = []
+    for ia, a in enumerate(images):
+        for ib in range(ia + 1, len(images)):
+            b = images[ib]
+            fwd = a.match_list.get(b.name) if a.match_list else None
+            if fwd is None or len(fwd) == 0:
+                continue
+            counts['pairs'] += 1
+            counts['matches_in'] += len(fwd)
+            if len(fwd) < min_pairs:
+                _verify_settle(a, b, fwd, np.zeros(len(fwd), bool), counts)
+                continue
+            jobs.append((ia, ib, _pairs_of(fwd), _verify_tol(a)))
+    arena = None
+    if launch is None:
+        launch = _verify_launch
+        arena = _verify_arena(proj) if jobs else None
+        for ia, ib, pairs, _tol in jobs:
+            na, nb = (int(arena[1][k + 1] - arena[1][k]) for k in (ia, ib))
+            if pairs.min() < 0 or pairs[:, 0].max() >= na or pairs[:, 1].max() >= nb:
+                raise ValueError("%s vs %s: a match names a keypoint that does not exist"
+                                 % (images[ia].name, images[ib].name))
+    at = 0
+    while at < len(jobs):
+        end, total = at, 0
+        while end < len(jobs) and (end == at or total + len(jobs[end][2]) <= VERIFY_BATCH_MATCHES):
+            total += len(jobs[end][2])
+            end += 1
+        masks, status = launch(jobs[at:end], transform, hypotheses, seed, arena)
+        for (ia, ib, pairs, _tol), mask, st in zip(jobs[at:end], masks, status):
+            a, b = images[ia], images[ib]
+            keep = np.asarray(mask).astype(bool)
+            if st == 1:
+                counts['too_few'] += 1
+                keep = np.ones(len(pairs), bool)
+                _log("  %s vs %s: %d matches are fewer than a sample, list kept" % (a.name, b.name, len(pairs)))
+            elif st == 2:
+                counts['no_model'] += 1
+                keep = np.zeros(len(pairs), bool)
+                _log("  %s vs %s: no model, list emptied" % (a.name, b.name))
+            _log("  %s vs %s: %d / %d  inliers/matched" % (a.name, b.name, int(keep.sum()), len(keep)))
+            _verify_settle(a, b, a.match_list[b.name], keep, counts)
+        at = end
+    return counts
+
+
+def _verify_settle(a, b, fwd, keep, counts):
+    """apply one pair's mask to a.match_list[b.name] and mirror it in b.match_list[a.name]"""
+    before = _pairs_of(fwd).copy()
+    survivors = before[keep]
+    counts['matches_out'] += len(survivors)
+    if len(survivors) == 0:
+        a.match_list[b.name] = []
+        counts['lists_emptied'] += 1
+        a.matches_clean = False
+    elif _keep_rows(fwd, keep):
+        a.matches_clean = False
+    rev = b.match_list.get(a.name) if b.match_list else None
+    if rev is None or len(rev) == 0:
+        return
+    r = _pairs_of(rev)
+    rk = _pair_keys(r[:, ::-1])
+    orphans = ~np.isin(rk, _pair_keys(before))
+    counts['orphans_dropped'] += int(orphans.sum())
+    rkeep = np.isin(rk, _pair_keys(survivors)) if len(survivors) else np.zeros(len(r), bool)
+    if len(rev) < min_pairs:
+        rkeep[:] = False
+    if not rkeep.any():
+        b.match_list[a.name] = []
+        counts['lists_emptied'] += 1
+        b.matches_clean = False
+    elif _keep_rows(rev, rkeep):
+        b.matches_clean = False

@@ -1279,6 +1279,59 @@ int iamx_ortho_raster_image(int mode, int S, const int32_t *X, const int32_t *Y,
 int iamx_ortho_resolve(int H, int W, const double *acc, const uint16_t *count, uint8_t *bgr,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * RANSAC verification of pair matches -- scripts/lib/matcher.py:90-142 filter_by_transform()
+ * (cv2.findHomography / cv2.findFundamentalMat with cv2.RANSAC).  Parity with cv2 is UNPINNED:
+ * cv2's sample sequence is its own; this one is the stateless rule of csrc/verify_rule.h.
+ *
+ * One workgroup per pair.  Pair p owns matches m_off[p] .. m_off[p+1]-1 of pts; a pair's result
+ * depends on its own points, tol[p], model, hypotheses and seed only, never on its place in the
+ * batch.  Everything is f64 on the float32 points widened:
+ *   1. Hartley normalisation per image (centroid, mean distance sqrt 2), fixed reduction trees;
+ *      all points of an image coincident (or not finite) -> IAMX_VERIFY_NO_MODEL.
+ *   2. hypothesis h < hypotheses: k matches by verify_sample (k = 4 homography, 8 fundamental), the
+ *      8x9 system in normalised coordinates
+ *        homography, two rows per match: [-x -y -1 0 0 0 ux uy u], [0 0 0 -x -y -1 vx vy v]
+ *        fundamental, one row per match: [ux uy u vx vy v x y 1]
+ *      and its null vector by Gauss-Jordan over the nine columns in order: column c takes the unused
+ *      row of largest |a| (ties: the lowest row) as its pivot; a pivot of at most 2^-40 times the
+ *      largest |entry| of the system leaves the column FREE; otherwise every other row, used ones
+ *      included, is reduced in all columns.  Then the last free column is 1, the other free columns
+ *      0, and each pivot column follows from its row.  A rank-deficient sample still gives a member
+ *      of its null space.
+ *   3. fundamental: the smallest singular value zeroed (one-sided Jacobi, eight sweeps), then
+ *      M = T2^T M T1.  Homography: M = T2^-1 M T1.  M is scaled to unit Frobenius norm with its
+ *      largest-magnitude entry positive; a model with an entry that is not finite is passed over.
+ *   4. error of every match: homography |pi(M x1) - x2|^2 (w zero or not finite: outlier);
+ *      fundamental max(e^2 / (l1x^2 + l1y^2), e^2 / (l2x^2 + l2y^2)), e = x2^T M x1, l2 = M x1,
+ *      l1 = M^T x2.  Inlier: err <= tol^2; a NaN never is.
+ *   5. the hypothesis with the most inliers, ties to the lowest h.  No refit, no adaptive stop.
+ * pts must be 16-byte aligned.  A pair whose offsets leave [0, total], or with 2^31 matches or
+ * more, gets status NO_MODEL and nothing of it is read or written.  n_pairs == 0 returns IAMX_OK
+ * without a launch.
+ *
+ * iamx_verify_sample (host): the k indices hypothesis hyp draws out of n, in draw order.
+ * 1 <= k <= 8, k <= n < 2^31, hyp >= 0.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_VERIFY_HOMOGRAPHY 0
+#define IAMX_VERIFY_FUNDAMENTAL 1
+#define IAMX_VERIFY_OK 0        /* a model was chosen, mask written                       */
+#define IAMX_VERIFY_TOO_FEW 1   /* n < sample size: mask all 1, model NaN, best -1        */
+#define IAMX_VERIFY_NO_MODEL 2  /* no hypothesis with a finite model and >= 1 inlier: mask all 0,
+                                   model NaN, best (-1, 0)                                 */
+int iamx_verify_pairs(const float *pts,      /* DEV [total][4] x1 y1 x2 y2 (undistorted px) */
+                      const int64_t *m_off,  /* DEV [n_pairs+1] */
+                      int n_pairs, int64_t total, int model,
+                      const double *tol,     /* DEV [n_pairs] px */
+                      int hypotheses, uint64_t seed,
+                      uint8_t *mask,         /* DEV [total] */
+                      double *out_model,     /* DEV [n_pairs][9] row major, unit Frobenius norm,
+                                                largest-magnitude entry positive */
+                      int32_t *out_best,     /* DEV [n_pairs][2] hypothesis index, inlier count */
+                      int32_t *status,       /* DEV [n_pairs] */
+                      void *stream);
+int iamx_verify_sample(int64_t n, int k, int64_t hyp, uint64_t seed, int32_t *out /* HOST [k] */);
+
 #ifdef __cplusplus
 }
 #endif
