@@ -485,7 +485,7 @@ extern "C" int iamx_desc_pack_f32(const float *src, int64_t n_rows, int8_t *dst,
 
 // rows of `n_img` images of the original-order store back as uint8, laid back to back (image i:
 // rows [dst_off[i], dst_off[i + 1]) of dst): value = stored + 128.  What rebuilds another layout of
-// images whose source descriptors are no longer on the device (DescriptorStore.ensure_train_layout).
+// images whose source descriptors are no longer on the device (the package itself has no such caller).
 namespace {
 __global__ __launch_bounds__(256) void unpack_u8_kernel(const int8_t *__restrict__ desc,
                                                         const int32_t *__restrict__ img_off,

@@ -80,63 +80,82 @@ class DescriptorStore(object):
     store'): int8 rows (value-128), each image zero-padded to 128 rows, + two int32 norms
     per row.  288 GB of HBM hold > 10^9 descriptors, so a whole survey stays resident."""
 
+    # The arena's three layouts, in one place: (suffix of the layout's offsets / img_off attributes,
+    # rows an image of n rows takes, per-row buffers that hold image data, per-row scratch) with
+    # (attribute, elements per row, dtype) per buffer.  Offsets, allocation, the growth copy and the
+    # bytes per row all come from here; a scratch buffer holds nothing of an image, so growth
+    # does not copy it.
+    LAYOUTS = (
+        # original order: the general kernel, the exact stage of the symmetric form
+        ('', 'iamx_desc_padded_rows', (('desc', 128, I8), ('norm_q', 1, I32), ('norm_t', 1, I32)),
+         (('key_t', 1, I32),)),                              # key_t: scratch of iamx_knn2sym_exact
+        # parity partitioned (include/iamx.h "desc2"): the one-direction fast sweep, train_layout only
+        ('2', 'iamx_desc2_rows_cap', (('desc2', 128, I8), ('norm2', 1, I32), ('cinit', 1, I32),
+                                      ('perm', 1, I32)), ()),
+        # rows ordered by |a-128|^2 (include/iamx.h "desc3"): the symmetric sweep
+        ('3', 'iamx_desc3_rows_cap', (('desc3', 128, I8), ('sn2', 1, I32), ('sct', 1, I32),
+                                      ('sperm', 1, I32), ('sinv', 1, I32)), ()),
+    )
+    # bytes per reserved row a caller may budget with: row_bytes(False) = 284 plus slack
+    RESERVE_ROW_BYTES = 290
+
+    @classmethod
+    def row_bytes(cls, train_layout):
+        """device bytes per (padded) descriptor row, all layouts together"""
+        return sum(w * torch.iinfo(dt).bits // 8 for sfx, _cap, data, scratch in cls.LAYOUTS
+                   if train_layout or sfx != '2' for _name, w, dt in data + scratch)
+
+    @classmethod
+    def _layout_offsets(cls, counts):
+        """cumulative row offsets (int64 [len(counts) + 1]) of images of `counts` rows, per layout"""
+        L = lib()
+        offs = []
+        for _sfx, cap, _data, _scratch in cls.LAYOUTS:
+            o = np.zeros(len(counts) + 1, np.int64)
+            np.cumsum([int(getattr(L, cap)(c)) for c in counts], out=o[1:])
+            offs.append(o)
+        return offs
+
+    def _has(self, sfx):
+        return sfx != '2' or self.has_train_layout
+
+    def _set_tables(self, counts, offs):
+        """the small per-image tables of `counts` (host offsets, device img_off* / img_n)"""
+        dev = self.desc.device
+        self.counts = counts
+        for (sfx, _cap, _data, _scratch), o in zip(self.LAYOUTS, offs):
+            setattr(self, 'offsets' + sfx, o)
+            setattr(self, 'img_off' + sfx, torch.from_numpy(o[:-1].astype(np.int32)).to(dev))
+        self.caps3 = np.diff(offs[2])
+        self.img_n = torch.tensor(counts, dtype=I32, device=dev) if counts else \
+            torch.zeros(0, dtype=I32, device=dev)
+
     def __init__(self, counts, train_layout=True, reserve_rows=0, reserve_images=0):
         """train_layout=False: the parity-partitioned copy `desc2` (a third of the arena) is not
         kept.  Only the ONE-direction fast sweep reads it; a store that serves batches holding
         both directions of every pair (find_matches: the symmetric sweep reads `desc3`, the exact
         stage `desc`) does without, and a batch the symmetric sweep refuses (an image of < 2 rows)
-        then takes the general kernel, which reads `desc` only.
+        then takes the general kernel, which reads `desc` only.  The choice holds for the store's
+        life, and for every store grown from it (copy_images_from).
         reserve_rows / reserve_images: capacity beyond `counts` -- try_extend() appends images
         without re-allocating (find_matches meeting undetected images registers ~250 per round:
         rebuilding a 40 GB arena each time was a quarter of that call form's time)."""
         dev = require_gpu()
-        L = lib()
         self.has_train_layout = bool(train_layout)
-        self.counts = [int(c) for c in counts]
+        counts = [int(c) for c in counts]
         reserve_rows, reserve_images = int(reserve_rows), int(reserve_images)
-        pads = [int(L.iamx_desc_padded_rows(c)) for c in self.counts]
-        offs = np.zeros(len(pads) + 1, np.int64)
-        np.cumsum(pads, out=offs[1:])
-        if offs[-1] >= 2 ** 31:
+        offs = self._layout_offsets(counts)
+        if max(int(o[-1]) for o in offs) >= 2 ** 31:
             raise ValueError("descriptor store limited to 2^31 rows")
-        self.offsets = offs
-        total = max(int(offs[-1]), reserve_rows, 1)
-        if total >= 2 ** 31:
-            total = max(int(offs[-1]), 1)
-        self.desc = torch.empty((total, 128), dtype=I8, device=dev)
-        self.norm_q = torch.empty(total, dtype=I32, device=dev)
-        self.norm_t = torch.empty(total, dtype=I32, device=dev)
-        self.key_t = torch.empty(total, dtype=I32, device=dev)      # scratch of iamx_knn2sym_exact
-        self.img_off = torch.from_numpy(offs[:-1].astype(np.int32)).to(dev)
-        self.img_n = torch.tensor(self.counts, dtype=I32, device=dev) if self.counts else \
-            torch.zeros(0, dtype=I32, device=dev)
-        # train-side layout of the fast kernel (parity partitioned, include/iamx.h "desc2")
-        caps = [int(L.iamx_desc2_rows_cap(c)) for c in self.counts]
-        offs2 = np.zeros(len(caps) + 1, np.int64)
-        np.cumsum(caps, out=offs2[1:])
-        if offs2[-1] >= 2 ** 31:
-            raise ValueError("descriptor store limited to 2^31 rows")
-        self.offsets2 = offs2
-        total2 = max(int(offs2[-1]), min(reserve_rows, 2 ** 31 - 1), 1) if train_layout else 1
-        self.desc2 = torch.empty((total2, 128), dtype=I8, device=dev)
-        self.norm2 = torch.empty(total2, dtype=I32, device=dev)
-        self.cinit = torch.empty(total2, dtype=I32, device=dev)
-        self.perm = torch.empty(total2, dtype=I32, device=dev)
-        self.meta = torch.zeros((max(len(caps), reserve_images, 1), 4), dtype=I32, device=dev)
-        self.img_off2 = torch.from_numpy(offs2[:-1].astype(np.int32)).to(dev)
-        # sorted layout of the symmetric sweep (rows ordered by |a-128|^2, include/iamx.h "desc3")
-        caps3 = [int(L.iamx_desc3_rows_cap(c)) for c in self.counts]
-        offs3 = np.zeros(len(caps3) + 1, np.int64)
-        np.cumsum(caps3, out=offs3[1:])
-        self.caps3 = np.asarray(caps3, np.int64)
-        self.offsets3 = offs3
-        total3 = max(int(offs3[-1]), min(reserve_rows, 2 ** 31 - 1), 1)
-        self.desc3 = torch.empty((total3, 128), dtype=I8, device=dev)
-        self.sn2 = torch.empty(total3, dtype=I32, device=dev)
-        self.sct = torch.empty(total3, dtype=I32, device=dev)
-        self.sperm = torch.empty(total3, dtype=I32, device=dev)
-        self.sinv = torch.empty(total3, dtype=I32, device=dev)
-        self.img_off3 = torch.from_numpy(offs3[:-1].astype(np.int32)).to(dev)
+        for (sfx, _cap, data, scratch), o in zip(self.LAYOUTS, offs):
+            total = max(int(o[-1]), reserve_rows, 1) if self._has(sfx) else 1
+            if total >= 2 ** 31:
+                total = max(int(o[-1]), 1)
+            for name, w, dt in data + scratch:
+                setattr(self, name, torch.empty((total, w) if w > 1 else total, dtype=dt, device=dev))
+        # per image: the parity classes of its desc2 rows (written with them, zero without)
+        self.meta = torch.zeros((max(len(counts), reserve_images, 1), 4), dtype=I32, device=dev)
+        self._set_tables(counts, offs)
 
     def __len__(self):
         return len(self.counts)
@@ -148,74 +167,37 @@ class DescriptorStore(object):
 
     def try_extend(self, new_counts):
         """Append images of new_counts rows each behind the existing ones if every layout's
-        buffers have room: the big buffers stay, the small per-image tables are rebuilt (batches
-        made earlier keep their own references; the rows of old images do not move).  -> False
-        (and nothing changed) when the capacity does not suffice."""
-        L = lib()
-        dev = self.desc.device
+        buffers (and `meta`, whichever layouts the store keeps) have room: the big buffers stay,
+        the small per-image tables are rebuilt (batches made earlier keep their own references; the
+        rows of old images do not move).  -> False (and nothing changed) when the capacity does
+        not suffice."""
         counts = self.counts + [int(c) for c in new_counts]
-        offs = np.zeros(len(counts) + 1, np.int64)
-        np.cumsum([int(L.iamx_desc_padded_rows(c)) for c in counts], out=offs[1:])
-        offs2 = np.zeros(len(counts) + 1, np.int64)
-        np.cumsum([int(L.iamx_desc2_rows_cap(c)) for c in counts], out=offs2[1:])
-        caps3 = [int(L.iamx_desc3_rows_cap(c)) for c in counts]
-        offs3 = np.zeros(len(counts) + 1, np.int64)
-        np.cumsum(caps3, out=offs3[1:])
-        if offs[-1] > self.desc.shape[0] or offs3[-1] > self.desc3.shape[0]:
+        offs = self._layout_offsets(counts)
+        if len(counts) > self.meta.shape[0] or max(int(o[-1]) for o in offs) >= 2 ** 31:
             return False
-        if self.has_train_layout and (offs2[-1] > self.desc2.shape[0] or len(counts) > self.meta.shape[0]):
-            return False
-        if max(offs[-1], offs2[-1], offs3[-1]) >= 2 ** 31:
-            return False
-        self.counts = counts
-        self.offsets, self.offsets2, self.offsets3 = offs, offs2, offs3
-        self.caps3 = np.asarray(caps3, np.int64)
-        self.img_off = torch.from_numpy(offs[:-1].astype(np.int32)).to(dev)
-        self.img_n = torch.tensor(counts, dtype=I32, device=dev)
-        self.img_off2 = torch.from_numpy(offs2[:-1].astype(np.int32)).to(dev)
-        self.img_off3 = torch.from_numpy(offs3[:-1].astype(np.int32)).to(dev)
+        for (sfx, _cap, data, _scratch), o in zip(self.LAYOUTS, offs):
+            if self._has(sfx) and o[-1] > getattr(self, data[0][0]).shape[0]:
+                return False
+        self._set_tables(counts, offs)
         return True
 
-    def ensure_train_layout(self, chunk_rows=4 << 20):
-        """Builds the parity-partitioned copy `desc2` of a store made without it, from the
-        original-order rows already on the device (iamx_desc_unpack_u8 -> iamx_desc2_pack_batch_u8,
-        a few million rows at a time).  Enqueued on the current stream; find_matches asks for it the
-        first time a round is routed to the one-direction sweep."""
+    def copy_images_from(self, old):
+        """Growth: this freshly built store's first len(old) images are `old`'s -- their rows in
+        every layout's data buffers (and their `meta` rows with the parity-partitioned layout) are
+        copied on the device, enqueued on the current stream.  Offsets depend on the counts alone,
+        so the rows land where set_image() would have put them."""
+        k = len(old.counts)
+        if self.counts[:k] != old.counts:
+            raise ValueError("copy_images_from: the older store's images must come first")
+        if self.has_train_layout and not old.has_train_layout:
+            raise ValueError("copy_images_from: the older store has no parity-partitioned layout")
+        for sfx, _cap, data, _scratch in self.LAYOUTS:
+            if self._has(sfx):
+                n = int(getattr(old, 'offsets' + sfx)[-1])
+                for name, _w, _dt in data:
+                    getattr(self, name)[:n].copy_(getattr(old, name)[:n])
         if self.has_train_layout:
-            return
-        dev = self.desc.device
-        L, sp = lib(), stream_ptr()
-        total2 = max(int(self.offsets2[-1]), 1)
-        self.desc2 = torch.empty((total2, 128), dtype=I8, device=dev)
-        self.norm2 = torch.empty(total2, dtype=I32, device=dev)
-        self.cinit = torch.empty(total2, dtype=I32, device=dev)
-        self.perm = torch.empty(total2, dtype=I32, device=dev)
-        counts = np.asarray(self.counts, np.int64)
-        keep = []
-        first = 0
-        while first < len(counts):
-            k, rows = 0, 0
-            while first + k < len(counts) and (k == 0 or rows + counts[first + k] <= chunk_rows):
-                rows += int(counts[first + k])
-                k += 1
-            if rows:
-                off = np.zeros(k + 1, np.int64)
-                np.cumsum(counts[first:first + k], out=off[1:])
-                d_off = torch.from_numpy(off).to(dev)
-                u8 = torch.empty((rows, 128), dtype=U8, device=dev)
-                mx = int(counts[first:first + k].max())
-                check(L.iamx_desc_unpack_u8(_ptr(self.desc), _ptr(self.img_off[first:]), _ptr(d_off), k, mx,
-                                            _ptr(u8), sp), 'iamx_desc_unpack_u8')
-                scratch = torch.empty(3 * rows, dtype=I32, device=dev)
-                check(L.iamx_desc2_pack_batch_u8(_ptr(u8), _ptr(d_off), _ptr(self.img_off2[first:]), k, rows, mx,
-                                                 _ptr(self.desc2), _ptr(self.norm2), _ptr(self.cinit),
-                                                 _ptr(self.perm), _ptr(self.meta[first]), _ptr(scratch), sp),
-                      'iamx_desc2_pack_batch_u8')
-                keep.append((d_off, u8, scratch))
-            first += k
-        torch.cuda.current_stream().synchronize()          # (the temporaries above)
-        del keep
-        self.has_train_layout = True
+            self.meta[:k].copy_(old.meta[:k])
 
     def set_image(self, i, des, sync=True):
         """Pack descriptors of image i.  `des`: [n,128] float32 (cv2/reference layout, integer
@@ -901,33 +883,51 @@ class PairBatch(object):
                                        self.total_wg, _ptr(ws.idx), _ptr(ws.d2), stream_ptr()),
               'iamx_knn2_l2_pairs')
 
-    def run_filter(self, ws, thresh):
+    def _threshold_compact(self, ws, thresh, index, stride, final):
+        """metric threshold -> scan of the per-pair counts -> compaction of the kept rows with their
+        train entry index[row * stride].  final: the kept rows ARE the survivors (no finish stage
+        follows that writes surv_cnt)."""
         L, s = lib(), stream_ptr()
         check(L.iamx_match_metric(_ptr(ws.d2), _ptr(self.d_out), self.n_pairs, float(thresh),
                                   _ptr(ws.metric), _ptr(ws.keep), _ptr(ws.seg_count),
                                   _ptr(ws.zero_div), s), 'iamx_match_metric')
         check(L.iamx_exclusive_scan_i32(_ptr(ws.seg_count), self.n_pairs, _ptr(ws.surv_off), s),
               'iamx_exclusive_scan_i32')
-        check(L.iamx_match_compact(_ptr(ws.idx), 2, _ptr(ws.metric), _ptr(ws.keep),
+        check(L.iamx_match_compact(_ptr(index), stride, _ptr(ws.metric), _ptr(ws.keep),
                                    _ptr(self.d_out), _ptr(ws.surv_off), self.n_pairs,
                                    _ptr(ws.surv_q), _ptr(ws.surv_t), _ptr(ws.surv_metric), s),
               'iamx_match_compact')
+        if final:
+            ws.surv_cnt[:self.n_pairs].copy_(ws.seg_count[:self.n_pairs])
+
+    def run_filter(self, ws, thresh):
+        self._threshold_compact(ws, thresh, ws.idx, 2, True)
 
     # ---- fast form: distances + tile in the sweep, train index only for the survivors
-    def run_knn2_fast(self, ws, exact_second=False):
-        st = self.store
+    def _route(self, exact_second):
+        """the one decision run_knn2_fast and run_filter_fast share: 'sym' = the symmetric sweep,
+        'general' = the kernel that tracks indices (a store without the parity-partitioned copy),
+        'exact' / 'bound' = the one-direction forms"""
         if self.sym and not exact_second:
+            return 'sym'
+        if not self.store.has_train_layout:
+            return 'general'
+        return 'exact' if exact_second else 'bound'
+
+    def run_knn2_fast(self, ws, exact_second=False):
+        route = self._route(exact_second)
+        if route == 'sym':
             return self.run_sym_sweep(ws)
-        if not st.has_train_layout:
-            # (no parity-partitioned copy in this store: the general kernel, exact as well)
+        if route == 'general':
             return self.run_knn2(ws)
-        if exact_second and self.fast_rows == 1024:          # the exact-second form stops at 512
+        if route == 'exact' and self.fast_rows == 1024:      # the exact-second form stops at 512
             self._use_rows(512)
+        st = self.store
         check(lib().iamx_knn2v2_pairs(_ptr(st.desc), _ptr(st.norm_q), _ptr(st.img_off),
                                       _ptr(st.img_n), _ptr(st.desc2), _ptr(st.cinit),
                                       _ptr(st.img_off2), _ptr(st.meta), _ptr(self.d_pairs),
                                       _ptr(self.d_wg_fast), _ptr(self.d_out), self.n_pairs,
-                                      self.total_wg_fast, self.fast_rows, 1 if exact_second else 0,
+                                      self.total_wg_fast, self.fast_rows, 1 if route == 'exact' else 0,
                                       _ptr(ws.d2), _ptr(ws.tile), stream_ptr()),
               'iamx_knn2v2_pairs')
 
@@ -939,32 +939,23 @@ class PairBatch(object):
         self.d_wg_fast = torch.from_numpy(wgf.astype(np.int32)).to(self.d_pairs.device)
 
     def run_filter_fast(self, ws, thresh, exact_second=False):
-        """threshold + compaction + train rows.  With the bound form of the sweep the first
+        """threshold + compaction + train rows; every route leaves pair p's survivors at
+        surv_*[surv_off[p] .. + surv_cnt[p]).  With the bound form of the sweep the first
         threshold keeps a superset; iamx_knn2v2_finish makes it exact (include/iamx.h)."""
-        if self.sym and not exact_second:
+        route = self._route(exact_second)
+        if route == 'sym':
             return self.run_sym_filter(ws, thresh)
-        if not self.store.has_train_layout:
-            self.run_filter(ws, thresh)
-            ws.surv_cnt[:self.n_pairs].copy_(ws.seg_count[:self.n_pairs])
-            return
+        if route == 'general':
+            return self.run_filter(ws, thresh)
         L, s, st = lib(), stream_ptr(), self.store
-        check(L.iamx_match_metric(_ptr(ws.d2), _ptr(self.d_out), self.n_pairs, float(thresh),
-                                  _ptr(ws.metric), _ptr(ws.keep), _ptr(ws.seg_count),
-                                  _ptr(ws.zero_div), s), 'iamx_match_metric')
-        check(L.iamx_exclusive_scan_i32(_ptr(ws.seg_count), self.n_pairs, _ptr(ws.surv_off), s),
-              'iamx_exclusive_scan_i32')
-        check(L.iamx_match_compact(_ptr(ws.tile), 1, _ptr(ws.metric), _ptr(ws.keep),
-                                   _ptr(self.d_out), _ptr(ws.surv_off), self.n_pairs,
-                                   _ptr(ws.surv_q), _ptr(ws.surv_t), _ptr(ws.surv_metric), s),
-              'iamx_match_compact')
-        if exact_second:
+        self._threshold_compact(ws, thresh, ws.tile, 1, route == 'exact')
+        if route == 'exact':
             check(L.iamx_knn2v2_resolve(_ptr(st.desc), _ptr(st.norm_q), _ptr(st.img_off),
                                         _ptr(st.desc2), _ptr(st.norm2), _ptr(st.perm),
                                         _ptr(st.img_off2), _ptr(self.d_pairs), _ptr(self.d_out),
                                         _ptr(ws.d2), _ptr(ws.surv_off), _ptr(ws.surv_q),
                                         _ptr(ws.surv_t), self.n_pairs, _ptr(ws.unresolved), s),
                   'iamx_knn2v2_resolve')
-            ws.surv_cnt[:self.n_pairs].copy_(ws.seg_count[:self.n_pairs])
         else:
             check(L.iamx_knn2v2_finish(_ptr(st.desc), _ptr(st.norm_q), _ptr(st.img_off),
                                        _ptr(st.desc2), _ptr(st.norm2), _ptr(st.perm),
@@ -990,7 +981,6 @@ class PairBatch(object):
         else:
             self.run_knn2(ws)
             self.run_filter(ws, thresh)
-            ws.surv_cnt[:self.n_pairs].copy_(ws.seg_count[:self.n_pairs])
 
 
 # --------------------------------------------------------------------------------------

@@ -56,41 +56,16 @@ PREWARM_ROUNDS = 32     # a call with at least this many rounds fills its buffer
 EARLY_SMART_ROUNDS = 8  # rounds in a row without a match before smart.json is written ahead of time
 early_smart_stats = {'written': 0, 'current_at_end': 0}     # (tests / diagnosis)
 MAX_IMAGE_ROWS = 1 << 24    # descriptor rows of one image: what the packers and the filter kernel index
-# Which sweep a round of find_matches takes.  The symmetric sweep (one MFMA pass per image pair)
-# leaves the rows whose bounds pass the metric test to an exact stage that runs at half the sweep's
-# rate; on overlapping frames of real imagery 15-30 % of the rows are such candidates.  Round 5
-# built the route the round-4 review proposed -- a round whose last measured candidate share exceeds
-# DENSE_SHARE takes the one-direction bound form (two sweeps per pair, survivors finished exactly),
-# every DENSE_PROBE-th routed round measures again -- and MEASURED it (profiles/r5_*): break-even on
-# 512 rendered frames (3.36 s symmetric, 3.44 s routed, f = 0.17), SLOWER on the workloads with many
-# true survivors: the dense-overlap workload of bench.py (f = 0.28) runs 0.63x as fast in the
-# one-direction form (its per-survivor finish costs more than the exact stage it replaces), the
-# dense 400-image survey 76 k instead of 80 k pairs/s through find_matches (same code otherwise;
-# configs[2], whose dense rounds are few, is unaffected) -- and the parity-partitioned layout it
-# needs is another 140 B per descriptor row.  So the default is
-# 'never'; 'auto' / 'always' remain for A/B runs (IAMX_DENSE_ROUTE).  Results are identical in all
-# modes (tests/test_mirror_gpu.py).
-DENSE_ROUTE = os.environ.get('IAMX_DENSE_ROUTE', 'never')
-DENSE_SHARE = 0.30
-DENSE_PROBE = 4
-_route = {'share': None, 'since_probe': 0, 'rounds': [0, 0]}     # rounds: [symmetric, one-direction]
+# Every round of find_matches takes the symmetric sweep.  Routing candidate-dense rounds to the
+# one-direction bound form was built and measured in round 5 (profiles/r5_*: break-even on 512
+# rendered frames, 0.63x on the dense-overlap workload, 76 k instead of 80 k pairs/s on the dense
+# 400-image survey, +140 B of arena per descriptor row) and removed.
+DENSE_ROUTE = 'never'   # (bench.py reports it with the round counts below)
+_route = {'share': None, 'rounds': [0, 0]}     # last candidate share; rounds: [symmetric, one-direction]
 
 
 def _route_reset():
-    _route.update(share=None, since_probe=0, rounds=[0, 0])
-
-
-def _route_next():
-    """True: the next round takes the one-direction form"""
-    if DENSE_ROUTE == 'always':
-        return True
-    if DENSE_ROUTE != 'auto' or _route['share'] is None or _route['share'] < DENSE_SHARE:
-        return False
-    _route['since_probe'] += 1
-    if _route['since_probe'] >= DENSE_PROBE:
-        _route['since_probe'] = 0
-        return False
-    return True
+    _route.update(share=None, rounds=[0, 0])
 
 
 def _workspace_bytes_per_pair(rows):
@@ -259,32 +234,12 @@ class DeviceMatcher(object):
             self._kp_dev = (n, d_off, d_xy, d_k2, rows)
         return self._kp_dev[1:4]
 
-    def want_train_layout(self):
-        """From now on the arena carries the parity-partitioned copy the one-direction sweep reads
-        (+50 % of the arena: 140 B per descriptor row).  -> False when that copy would take more
-        than a quarter of the free device memory -- the round then stays on the symmetric sweep,
-        which needs nothing extra (a 10 000-frame survey's arena is 104 GB without it)."""
-        if getattr(self, '_train_layout', False):
-            return True
-        try:
-            import torch
-            free, _total = torch.cuda.mem_get_info()
-        except Exception:                 # noqa: BLE001
-            return False
-        need = (sum(self._counts) + 128 * len(self._counts)) * 140
-        if need > free // 4:
-            return False
-        self._train_layout = True
-        return True
-
     def store(self):
         """(Re)build the arena when new images arrived; old rows are copied on the device."""
         from . import kernels
         pend = self._pending
-        want_train = getattr(self, '_train_layout', False)
         _tm = [time.perf_counter()] if _round_trace is not None else None
         if self._store is not None and len(self._store.counts) < len(self._counts) and \
-                self._store.has_train_layout == bool(want_train) and \
                 self._store.counts == self._counts[:len(self._store.counts)] and \
                 self._store.try_extend(self._counts[len(self._store.counts):]):
             pass                                   # the new images fit behind the old ones
@@ -304,31 +259,16 @@ class DeviceMatcher(object):
                 import torch
                 free, _t = torch.cuda.mem_get_info()
                 free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-                if reserve * 290 > free // 2:        # (never more than half of what is left)
-                    reserve = 0
+                if reserve * kernels.DescriptorStore.RESERVE_ROW_BYTES > free // 2:
+                    reserve = 0                       # (never more than half of what is left)
             except Exception:                         # noqa: BLE001
                 reserve = 0
-            new = kernels.DescriptorStore(self._counts, train_layout=want_train,
-                                          reserve_rows=reserve, reserve_images=n_exp if reserve else 0)
+            # (per-image entries for as many images as the reserved rows can hold at all -- one takes
+            #  at least 128 --, so that the rows decide whether an extension fits: 16 B each)
+            new = kernels.DescriptorStore(self._counts, train_layout=False, reserve_rows=reserve,
+                                          reserve_images=max(n_exp, reserve // 128) if reserve else 0)
             if self._store is not None and len(self._store.counts):
-                old = self._store
-                n_old, n_old2, k = int(old.offsets[-1]), int(old.offsets2[-1]), len(old.counts)
-                new.desc[:n_old].copy_(old.desc[:n_old])
-                new.norm_q[:n_old].copy_(old.norm_q[:n_old])
-                new.norm_t[:n_old].copy_(old.norm_t[:n_old])
-                # ... and the train-side (parity partitioned) form the fast kernel reads
-                if new.has_train_layout and not old.has_train_layout:
-                    old.ensure_train_layout()
-                if old.has_train_layout and new.has_train_layout:
-                    new.desc2[:n_old2].copy_(old.desc2[:n_old2])
-                    new.norm2[:n_old2].copy_(old.norm2[:n_old2])
-                    new.cinit[:n_old2].copy_(old.cinit[:n_old2])
-                    new.perm[:n_old2].copy_(old.perm[:n_old2])
-                    new.meta[:k].copy_(old.meta[:k])
-                # ... and the sorted form of the symmetric sweep
-                n_old3 = int(old.offsets3[-1])
-                for name in ('desc3', 'sn2', 'sct', 'sperm', 'sinv'):
-                    getattr(new, name)[:n_old3].copy_(getattr(old, name)[:n_old3])
+                new.copy_images_from(self._store)
             self._store = new
         if _tm is not None:
             _tm.append(time.perf_counter())
@@ -359,8 +299,6 @@ class DeviceMatcher(object):
                                  time.perf_counter()))
         del keep
         self._pending = []
-        if want_train and not self._store.has_train_layout:
-            self._store.ensure_train_layout()
         return self._store
 
 
@@ -844,8 +782,9 @@ def device_memory_model(n_images, rows_per_image, train_layout=False):
                  dominate), TWO of them pooled + a third while a round is in flight, and the
                  per-pair result slots of the filters (clip x 56 B per pair)
     Only the arena grows with the survey; the rest is bounded by BATCH_BYTES whatever N is."""
+    from .kernels import DescriptorStore
     rows = (int(rows_per_image) + 127) // 128 * 128
-    per_row = (128 + 12) + (128 + 16) + ((128 + 12) if train_layout else 0)
+    per_row = DescriptorStore.row_bytes(train_layout)
     arena = n_images * rows * per_row + n_images * int(rows_per_image) * 16
     ppb = _pairs_per_batch(1.25 * rows_per_image)
     ws = ppb * _workspace_bytes_per_pair(1.25 * rows_per_image)
@@ -928,7 +867,7 @@ def _prewarm_pools(n, rows, surface, dev, stream, sets=3):
         _ws_pool.extend(work)
 
 
-def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_direction=False):
+def _launch_batch(batch, match_ratio, device_filters=True, surface=False):
     """batch: list of (i1, i2) image objects.  ENQUEUES, on the current stream, the device k=2
     NN + metric threshold for both directions of every pair, the per-pair filters (sort/clip,
     GMS, de-dup, gates, cross check: iamx_match_postfilter) unless `device_filters` is False,
@@ -958,14 +897,12 @@ def _launch_batch(batch, match_ratio, device_filters=True, surface=False, one_di
         # new images: the descriptor / keypoint arenas are about to be rebuilt, and the previous
         # round's side-stream kernels may still be reading the old ones
         torch.cuda.current_stream().wait_stream(_side_stream())
-    if one_direction and not dm.want_train_layout():      # (the parity-partitioned copy, built on first use)
-        one_direction = False
     store = dm.store()
     arena = _upload_arena()
     arena.begin()
     sl = np.asarray(slots, np.int32).reshape(-1, 2)
     ordered = np.concatenate([sl, sl[:, ::-1]])
-    pb = kernels.PairBatch(store, ordered, sym=False if one_direction else None, arena=arena)
+    pb = kernels.PairBatch(store, ordered, sym=None, arena=arena)
     arena.commit()
     _route['rounds'][0 if pb.sym else 1] += 1
     ws = _workspace(pb.rows, pb.n_pairs)
@@ -1851,8 +1788,7 @@ class _MatchRun(object):
             if rows[k] <= 1:
                 # raw_matches() returns [] and basic_pair_matches divides by len([]) (:232)
                 raise ZeroDivisionError("float division by zero")
-        handle = _launch_batch(view, self.match_ratio, surface='fit' if self.surface else False,
-                               one_direction=_route_next())
+        handle = _launch_batch(view, self.match_ratio, surface='fit' if self.surface else False)
         return view, sl, handle
 
     def finish_round(self, launched):

@@ -483,6 +483,27 @@ def test_bulk_ingest_equals_image_by_image():
         assert torch.equal(a.meta, b.meta)
 
 
+def _same_store(ext, full, counts, train_layout):
+    """every layout of `ext` (grown) equals that of `full` (built with all images at once)"""
+    import torch
+    assert np.array_equal(ext.offsets, full.offsets) and np.array_equal(ext.offsets3, full.offsets3)
+    assert ext.rows_used == full.rows_used
+    n, n3 = int(full.offsets[-1]), int(full.offsets3[-1])
+    for name, m in (('desc', n), ('norm_q', n), ('norm_t', n)):
+        assert torch.equal(getattr(ext, name)[:m], getattr(full, name)[:m]), name
+    for i, c in enumerate(counts):
+        o3 = int(full.offsets3[i])
+        for name, m in (('desc3', int(full.caps3[i])), ('sn2', c), ('sct', c), ('sperm', c), ('sinv', c)):
+            assert torch.equal(getattr(ext, name)[o3:o3 + m], getattr(full, name)[o3:o3 + m]), (name, i)
+    assert torch.equal(ext.img_off, full.img_off) and torch.equal(ext.img_n, full.img_n)
+    assert torch.equal(ext.img_off3, full.img_off3)
+    if train_layout:
+        n2 = int(full.offsets2[-1])
+        for name in ('desc2', 'norm2', 'cinit', 'perm'):
+            assert torch.equal(getattr(ext, name)[:n2], getattr(full, name)[:n2]), name
+        assert torch.equal(ext.meta[:len(counts)], full.meta[:len(counts)])
+
+
 @pytest.mark.parametrize('train_layout', [True, False], ids=['with_desc2', 'without_desc2'])
 def test_store_extended_in_place_equals_store_built_at_once(train_layout):
     """DescriptorStore(reserve_rows, reserve_images) + try_extend (find_matches meeting undetected
@@ -507,26 +528,91 @@ def test_store_extended_in_place_equals_store_built_at_once(train_layout):
     for i in range(k, len(counts)):
         keep.append(ext.set_image(i, arrays[i], sync=False))
     torch.cuda.synchronize()
-    assert np.array_equal(ext.offsets, full.offsets) and np.array_equal(ext.offsets3, full.offsets3)
-    assert ext.rows_used == full.rows_used
-    n, n3 = int(full.offsets[-1]), int(full.offsets3[-1])
-    for name, m in (('desc', n), ('norm_q', n), ('norm_t', n)):
-        assert torch.equal(getattr(ext, name)[:m], getattr(full, name)[:m]), name
-    for i, c in enumerate(counts):
-        o3 = int(full.offsets3[i])
-        for name, m in (('desc3', int(full.caps3[i])), ('sn2', c), ('sct', c), ('sperm', c), ('sinv', c)):
-            assert torch.equal(getattr(ext, name)[o3:o3 + m], getattr(full, name)[o3:o3 + m]), (name, i)
-    assert torch.equal(ext.img_off, full.img_off) and torch.equal(ext.img_n, full.img_n)
-    assert torch.equal(ext.img_off3, full.img_off3)
-    if train_layout:
-        n2 = int(full.offsets2[-1])
-        for name in ('desc2', 'norm2', 'cinit', 'perm'):
-            assert torch.equal(getattr(ext, name)[:n2], getattr(full, name)[:n2]), name
-        assert torch.equal(ext.meta[:len(counts)], full.meta[:len(counts)])
+    _same_store(ext, full, counts, train_layout)
     pairs = [(0, 4), (4, 0), (1, 7), (7, 1), (3, 5), (5, 3), (2, 6), (6, 2)]
     _same_survivors(_run(ext, pairs, 0.7, sym=True), _run(full, pairs, 0.7, sym=True))
     _same_survivors(_run(ext, pairs, 0.7, fast=False, sym=False), _run(full, pairs, 0.7, fast=False, sym=False))
     # no room: nothing changes
     before = list(ext.counts)
+    # (reserve_images is used up while the rows still have room for a small image)
+    assert ext.meta.shape[0] == len(counts) and ext.rows_used + 128 <= ext.desc.shape[0]
+    off_before = ext.img_off.clone()
+    assert not ext.try_extend([5])
+    assert ext.counts == before and ext.desc.data_ptr() == ptr and torch.equal(ext.img_off, off_before)
+    assert len(ext.offsets) == len(before) + 1 and ext.img_n.numel() == len(before)
     assert not ext.try_extend([1 << 20])
     assert ext.counts == before and ext.desc.data_ptr() == ptr
+
+
+GROWTH_COUNTS = [130, 2, 257, 1024, 700, 127, 128, 129]
+
+
+@pytest.mark.parametrize('train_layout', [True, False], ids=['with_desc2', 'without_desc2'])
+def test_growth_copy_equals_store_built_at_once(train_layout):
+    """DescriptorStore.copy_images_from (the arena re-allocated because try_extend refused): a
+    larger store that takes the images of an older one by device copy and the rest by set_image
+    equals, in every layout, a store built with all images at once, and matches pairs across
+    copied and new images alike.  Counts around the 128-row padding of every layout; a 2-row image
+    of one parity class (the other class of its desc2 slice is empty)."""
+    import torch
+    from imageanalysis_amd import kernels
+    rng = np.random.default_rng(22)
+    counts = GROWTH_COUNTS
+    arrays = _survey(rng, counts)
+    arrays[1][:] = 128
+    k = 3
+    full = kernels.DescriptorStore(counts, train_layout=train_layout)
+    keep = [full.set_images(0, arrays)]
+    small = kernels.DescriptorStore(counts[:k], train_layout=train_layout)
+    keep.append(small.set_images(0, arrays[:k]))
+    big = kernels.DescriptorStore(counts, train_layout=train_layout)
+    big.copy_images_from(small)
+    for i in range(k, len(counts)):
+        keep.append(big.set_image(i, arrays[i], sync=False))
+    torch.cuda.synchronize()
+    assert big.has_train_layout == train_layout
+    _same_store(big, full, counts, train_layout)
+    assert torch.equal(big.img_off2, full.img_off2) and np.array_equal(big.offsets2, full.offsets2)
+    assert torch.equal(big.meta, full.meta)
+    thresh = 270.0 * 0.75
+    pairs = [(2, 3), (3, 2), (0, 3), (3, 0), (1, 4), (4, 1), (2, 7), (7, 2), (0, 6), (6, 0), (5, 6), (6, 5)]
+    got = _run(big, pairs, thresh, sym=True)
+    assert got['pb'].sym and (np.diff(got['soff']) > 50).sum() >= 2      # the planted overlap of 2 and 3
+    _same_survivors(got, _run(full, pairs, thresh, sym=True))
+    _same_survivors(_run(big, pairs, thresh, fast=False, sym=False), _run(full, pairs, thresh, fast=False, sym=False))
+    if train_layout:
+        _same_survivors(_run(big, pairs, thresh, fast=True, sym=False), _run(full, pairs, thresh, fast=True, sym=False))
+    # a store that keeps the parity-partitioned layout cannot grow out of one that does not
+    if not train_layout:
+        with pytest.raises(ValueError):
+            kernels.DescriptorStore(counts, train_layout=True).copy_images_from(small)
+
+
+def test_matcher_arena_growth_steps():
+    """DeviceMatcher.store(): the first arena is sized exactly; more images than it holds ->
+    re-allocated with reserve, the old images copied on the device; a further small image goes
+    behind them in place.  After each step every image's rows equal a store built at once."""
+    import torch
+    from imageanalysis_amd import kernels, matcher
+    from test_host_logic import _image
+    rng = np.random.default_rng(23)
+    counts = GROWTH_COUNTS[:6]
+    images = [_image('S%02d' % i, _sift_like(rng, n), rng.uniform(0, 4000, (n, 2)).astype(np.float32))
+              for i, n in enumerate(counts)]
+    dm = matcher.DeviceMatcher()
+    ptrs = []
+    for upto in (3, 5, 6):
+        for im in images[:upto]:
+            dm.slot_of(im)
+        st = dm.store()
+        assert st.counts == counts[:upto] and not st.has_train_layout and not dm._pending
+        full = kernels.DescriptorStore(counts[:upto], train_layout=False)
+        keep = full.set_images(0, [im.des_list for im in images[:upto]])
+        torch.cuda.synchronize()
+        del keep
+        _same_store(st, full, counts[:upto], False)
+        ptrs.append((st, st.desc.data_ptr()))           # (the stores stay alive: no address re-used)
+    (s3, p3), (s5, p5), (s6, p6) = ptrs
+    assert s3.desc.shape[0] == int(s3.offsets[-1]) and s3.desc3.shape[0] == int(s3.offsets3[-1])
+    assert s5 is not s3 and p5 != p3 and s5.desc.shape[0] > int(s5.offsets[-1])
+    assert s6 is s5 and p6 == p5

@@ -385,12 +385,10 @@ def test_smart_json_written_ahead_of_time_equals_the_final_one(tmp_path, sort):
     assert any('yaw_pairs' in v or 'tri_surface_pairs' in v for v in files['early'].values())
 
 
-@pytest.mark.parametrize('route', ['never', 'always', 'auto'])
-def test_find_matches_dense_routing_gives_the_same_lists(route):
-    """A round of find_matches may take the symmetric sweep or the one-direction bound form
-    (matcher.DENSE_ROUTE): every match list == the oracle's bidirectional pipeline either way, with
-    the arena growing in between (the parity-partitioned copy is rebuilt from the rows already on
-    the device) and, in 'auto', rounds of both kinds in one call."""
+def test_find_matches_dense_routing_gives_the_same_lists():
+    """Every round of find_matches takes the symmetric sweep, candidate-dense ones too (the route
+    to the one-direction bound form is gone): every match list == the oracle's bidirectional
+    pipeline, with the arena growing in between."""
     from imageanalysis_amd.hostlib.image_pose import PoseProject
     from oracle import match_oracle as mo
     from test_match_gpu import _sift_like
@@ -417,28 +415,21 @@ def test_find_matches_dense_routing_gives_the_same_lists(route):
         im.set_camera_pose([-3.2727 * i, -6.8182 * i, -100.0], 0.0, -90.0, 0.0)
         fresh = _image(names[i], des[i], xy[i])
         im.des_list, im.kp_list = fresh.des_list, fresh.kp_list
-    old = (matcher.PAIRS_PER_BATCH, matcher.DENSE_ROUTE, matcher.DENSE_SHARE, matcher.DENSE_PROBE)
-    matcher.PAIRS_PER_BATCH, matcher.DENSE_ROUTE = 3, route
-    if route == 'auto':
-        matcher.DENSE_SHARE, matcher.DENSE_PROBE = 0.0005, 3      # (any candidates at all: dense)
+    old = matcher.PAIRS_PER_BATCH
+    matcher.PAIRS_PER_BATCH = 3
     try:
         matcher.find_matches(proj, None, strategy='traditional', sort=True)
         rounds = list(matcher._route['rounds'])
     finally:
-        matcher.PAIRS_PER_BATCH, matcher.DENSE_ROUTE, matcher.DENSE_SHARE, matcher.DENSE_PROBE = old
+        matcher.PAIRS_PER_BATCH = old
     assert sum(rounds) >= 6
-    if route == 'never':
-        assert rounds[1] == 0
-    elif route == 'always':
-        assert rounds[0] == 0
-    else:
-        assert rounds[0] >= 2 and rounds[1] >= 2, rounds
+    assert rounds[1] == 0
     n_nonempty = 0
     for i in range(n_img):
         for j in range(i + 1, min(i + 5, n_img)):
             f, r = mo.bidirectional_pair_matches(des[i], xy[i], des[j], xy[j], 0.75, 25, (W, H))
             a, b = proj.image_list[i], proj.image_list[j]
-            assert np.array_equal(np.array(a.match_list[names[j]]).reshape(-1, 2), f), (route, i, j)
-            assert np.array_equal(np.array(b.match_list[names[i]]).reshape(-1, 2), r), (route, i, j)
+            assert np.array_equal(np.array(a.match_list[names[j]]).reshape(-1, 2), f), (i, j)
+            assert np.array_equal(np.array(b.match_list[names[i]]).reshape(-1, 2), r), (i, j)
             n_nonempty += len(f) > 0
     assert n_nonempty >= 4
