@@ -217,6 +217,9 @@ SIGNATURES = {
     'iamx_verify_pairs': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int,
                                   ctypes.c_uint64] + [c_void_p] * 5),
     'iamx_verify_sample': (c_int, [c_int64, c_int, c_int64, ctypes.c_uint64, c_void_p]),
+    'iamx_verify_pairs_essential': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int,
+                                            ctypes.c_uint64] + [c_void_p] * 6),
+    'iamx_five_point': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

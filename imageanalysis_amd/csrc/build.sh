@@ -13,7 +13,7 @@ mkdir -p "$OBJDIR"
 OBJS=""
 for f in $SRCS; do
     o="$OBJDIR/$(basename ${f%.hip}).o"
-    if [ -n "$IAMX_REBUILD" ] || [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/iamx_common.h" -nt "$o" ] || [ "$HERE/jpeg_entropy.h" -nt "$o" ] || [ "$HERE/sym_cand_rule.h" -nt "$o" ] || [ "$HERE/verify_rule.h" -nt "$o" ] || [ "$HERE/../../include/iamx.h" -nt "$o" ]; then
+    if [ -n "$IAMX_REBUILD" ] || [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ "$HERE/iamx_common.h" -nt "$o" ] || [ "$HERE/jpeg_entropy.h" -nt "$o" ] || [ "$HERE/sym_cand_rule.h" -nt "$o" ] || [ "$HERE/verify_rule.h" -nt "$o" ] || [ "$HERE/five_point.h" -nt "$o" ] || [ "$HERE/../../include/iamx.h" -nt "$o" ]; then
         EXTRA=""
         # the TRF helpers restate numpy expressions: separately rounded multiply and add
         [ "$(basename $f)" = "trf_vec.hip" ] && EXTRA="-ffp-contract=off"

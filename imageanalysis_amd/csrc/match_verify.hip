@@ -13,10 +13,12 @@
 //           the normalisation undone, scaled to unit Frobenius norm, largest entry positive.
 //   score   each wave runs its 8 models, four at a time in registers, over the pair's points in LDS.
 //   choose  lane 0 walks the 32 counts in hypothesis order.
+// The essential model (five-point samples, csrc/five_point.h) has a kernel of its own further down.
 // Built with -ffp-contract=off: the scoring pass and the final mask pass evaluate the same
 // expression and must round it the same way wherever the compiler inlines it.
 #include "iamx_common.h"
 #include "verify_rule.h"
+#include "five_point.h"
 
 #include <math.h>
 
@@ -404,6 +406,209 @@ __global__ __launch_bounds__(256) void verify_pairs_kernel(
     }
 }
 
+// ---- the essential model: five-point samples on calibrated rays (five_point.h), scored as a pixel F.
+// Per round of 256 hypotheses:
+//   solve   every lane runs one sample through five_point::solve into registers / scratch: at most
+//           ten models E each; F = K^-T E K^-1 decides which are valid.
+//   order   a candidate's place is the number of valid candidates before it in (hypothesis, root)
+//           order (the lanes' counts summed in LDS).
+//   pass    CAND_PASS candidates at a time go into the LDS list, in that order;
+//   score   each wave takes every fourth group of four: F from E, then over every match;
+//   choose  lane 0 walks the pass's counts: most inliers, ties to the earliest (hypothesis, root).
+constexpr int ESS_ROUND = 256;
+constexpr int CAND_PASS = 320;
+
+__global__ __launch_bounds__(256) void verify_pairs_essential_kernel(
+    const float4 *__restrict__ pts, const int64_t *__restrict__ m_off, int64_t total,
+    five_point::Camera cam, const double *__restrict__ tol, int hypotheses, uint64_t seed,
+    uint8_t *__restrict__ mask, double *__restrict__ out_model, double *__restrict__ out_essential,
+    int32_t *__restrict__ out_best, int32_t *__restrict__ status)
+{
+    constexpr int K = 5;
+    __shared__ float4 pts_s[TILE];
+    __shared__ double cand_s[CAND_PASS][9];    // E of the pass's candidates
+    __shared__ int candh_s[CAND_PASS];         // their hypotheses
+    __shared__ int cnt_s[CAND_PASS];
+    __shared__ int nvalid_s[ESS_ROUND];
+    __shared__ double best_model_s[9], best_ess_s[9];
+    __shared__ int best_s[2];                  // hypothesis, count
+
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int64_t off = m_off[pair], n64 = m_off[pair + 1] - off;
+    double *om = out_model + (int64_t)pair * 9;
+    double *oe = out_essential ? out_essential + (int64_t)pair * 9 : nullptr;
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+
+    if (off < 0 || n64 < 0 || n64 > 0x7fffffff || off + n64 > total) {
+        // offsets that leave the arena: nothing of the pair is read or written
+        if (tid == 0) {
+            status[pair] = IAMX_VERIFY_NO_MODEL;
+            out_best[2 * pair] = -1;
+            out_best[2 * pair + 1] = 0;
+        }
+        if (tid < 9) { om[tid] = qnan; if (oe) oe[tid] = qnan; }
+        return;
+    }
+    const int n = (int)n64;
+    const float4 *P = pts + off;
+    uint8_t *msk = mask + off;
+
+    if (n < K) {
+        for (int i = tid; i < n; i += 256) msk[i] = 1;
+        if (tid < 9) { om[tid] = qnan; if (oe) oe[tid] = qnan; }
+        if (tid == 0) {
+            status[pair] = IAMX_VERIFY_TOO_FEW;
+            out_best[2 * pair] = -1;
+            out_best[2 * pair + 1] = -1;
+        }
+        return;
+    }
+
+    const double tl = tol[pair], tol2 = tl * tl;
+    if (tid == 0) { best_s[0] = -1; best_s[1] = 0; }
+    const bool one_tile = n <= TILE;
+    if (one_tile)
+        for (int i = tid; i < n; i += 256) pts_s[i] = P[i];
+    __syncthreads();
+
+    const int rounds = (hypotheses + ESS_ROUND - 1) / ESS_ROUND;
+    for (int round = 0; round < rounds; ++round) {
+        // ---- solve: one sample per lane
+        const int h = round * ESS_ROUND + tid;
+        double Eo[FIVE_POINT_MAX_ROOTS][9];
+        int nr = 0;
+        unsigned valid = 0;
+        if (h < hypotheses) {
+            int32_t smp[VERIFY_MAX_SAMPLE];
+            verify_sample(n, K, h, seed, smp);
+            double r[5][4];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const float4 sp = P[smp[j]];
+                five_point::ray(cam, (double)sp.x, (double)sp.y, r[j][0], r[j][1]);
+                five_point::ray(cam, (double)sp.z, (double)sp.w, r[j][2], r[j][3]);
+            }
+            nr = five_point::solve(r, Eo);
+            for (int k = 0; k < nr; ++k) {
+                bool fin = true;
+                for (int j = 0; j < 9; ++j) fin = fin && five_point::finite(Eo[k][j]);
+                double F[9];
+                fin = five_point::pixel_model(cam, Eo[k], F) && fin;
+                valid |= fin ? 1u << k : 0u;
+            }
+        }
+        nvalid_s[tid] = __popc(valid);
+        __syncthreads();
+        // ---- order: candidates before this lane's, and in the round
+        int first = 0, ncand = 0;
+        for (int i = 0; i < ESS_ROUND; ++i) {
+            const int v = nvalid_s[i];
+            first += i < tid ? v : 0;
+            ncand += v;
+        }
+        __syncthreads();
+        for (int base = 0; base < ncand; base += CAND_PASS) {
+            // ---- pass: candidates base .. base + CAND_PASS - 1 into the list
+            int place = first - base;
+            for (int k = 0; k < nr; ++k) {
+                if (!(valid >> k & 1u)) continue;
+                if (place >= 0 && place < CAND_PASS) {
+                    for (int j = 0; j < 9; ++j) cand_s[place][j] = Eo[k][j];
+                    candh_s[place] = h;
+                }
+                ++place;
+            }
+            __syncthreads();
+            const int nc = min(CAND_PASS, ncand - base);
+            // ---- score: four candidates at a time, every fourth group to this wave
+            for (int c0 = wave * 4; c0 < nc; c0 += 16) {
+                double Q[4][9];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int slot = min(c0 + m, nc - 1);
+                    double E[9];
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) E[j] = cand_s[slot][j];
+                    five_point::pixel_model(cam, E, Q[m]);
+                }
+                int cnt[4] = {0, 0, 0, 0};
+                for (int i = lane; i < n; i += 64) {
+                    const float4 p = one_tile ? pts_s[i] : P[i];
+                    const double x1 = p.x, y1 = p.y, x2 = p.z, y2 = p.w;
+#pragma unroll
+                    for (int m = 0; m < 4; ++m)
+                        cnt[m] += verify_inlier<IAMX_VERIFY_FUNDAMENTAL>(Q[m], x1, y1, x2, y2, tol2) ? 1 : 0;
+                }
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+#pragma unroll
+                    for (int k = 32; k >= 1; k >>= 1) cnt[m] += __shfl_xor(cnt[m], k);
+                    if (lane == 0 && c0 + m < nc) cnt_s[c0 + m] = cnt[m];
+                }
+            }
+            __syncthreads();
+            // ---- choose
+            if (tid == 0) {
+                int bc = best_s[1], bi = -1;
+                for (int i = 0; i < nc; ++i)
+                    if (cnt_s[i] > bc) { bc = cnt_s[i]; bi = i; }
+                if (bi >= 0) {
+                    best_s[0] = candh_s[bi];
+                    best_s[1] = bc;
+                    double E[9], F[9];
+                    for (int j = 0; j < 9; ++j) E[j] = cand_s[bi][j];
+                    five_point::pixel_model(cam, E, F);
+                    for (int j = 0; j < 9; ++j) { best_ess_s[j] = E[j]; best_model_s[j] = F[j]; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- the chosen model's mask
+    const int bh = best_s[0], bc = best_s[1];
+    if (bh < 0) {
+        for (int i = tid; i < n; i += 256) msk[i] = 0;
+        if (tid < 9) { om[tid] = qnan; if (oe) oe[tid] = qnan; }
+        if (tid == 0) {
+            status[pair] = IAMX_VERIFY_NO_MODEL;
+            out_best[2 * pair] = -1;
+            out_best[2 * pair + 1] = 0;
+        }
+        return;
+    }
+    double M[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) M[j] = best_model_s[j];
+    for (int i = tid; i < n; i += 256) {
+        const float4 p = P[i];
+        msk[i] = verify_inlier<IAMX_VERIFY_FUNDAMENTAL>(M, p.x, p.y, p.z, p.w, tol2) ? 1 : 0;
+    }
+    if (tid < 9) { om[tid] = best_model_s[tid]; if (oe) oe[tid] = best_ess_s[tid]; }
+    if (tid == 0) {
+        status[pair] = IAMX_VERIFY_OK;
+        out_best[2 * pair] = bh;
+        out_best[2 * pair + 1] = bc;
+    }
+}
+
+// the solver alone: one sample per lane
+__global__ __launch_bounds__(64) void five_point_kernel(const double *__restrict__ rays, int n,
+                                                        double *__restrict__ E, int32_t *__restrict__ count)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    double r[5][4], Eo[FIVE_POINT_MAX_ROOTS][9];
+    for (int j = 0; j < 5; ++j)
+        for (int k = 0; k < 4; ++k) r[j][k] = rays[(int64_t)i * 20 + j * 4 + k];
+    const int nr = five_point::solve(r, Eo);
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int k = 0; k < FIVE_POINT_MAX_ROOTS; ++k)
+        for (int j = 0; j < 9; ++j) E[((int64_t)i * FIVE_POINT_MAX_ROOTS + k) * 9 + j] = k < nr ? Eo[k][j] : qnan;
+    count[i] = nr;
+}
+
 }  // namespace
 
 extern "C" int iamx_verify_pairs(const float *pts, const int64_t *m_off, int n_pairs, int64_t total,
@@ -427,6 +632,40 @@ extern "C" int iamx_verify_pairs(const float *pts, const int64_t *m_off, int n_p
                            0, iamx::as_stream(stream), p4, m_off, total, tol, hypotheses, seed, mask,
                            out_model, out_best, status);
     return iamx::check_launch("iamx_verify_pairs");
+}
+
+extern "C" int iamx_verify_pairs_essential(const float *pts, const int64_t *m_off, int n_pairs,
+                                           int64_t total, const double *K, const double *tol,
+                                           int hypotheses, uint64_t seed, uint8_t *mask,
+                                           double *out_model, double *out_essential, int32_t *out_best,
+                                           int32_t *status, void *stream)
+{
+    IAMX_REQUIRE(n_pairs >= 0 && total >= 0 && hypotheses >= 1, "bad size");
+    IAMX_REQUIRE(m_off && K && tol && out_model && out_best && status, "null pointer");
+    IAMX_REQUIRE(total == 0 || (pts && mask), "null pointer");
+    IAMX_REQUIRE(((uintptr_t)pts & 15) == 0, "pts is not 16-byte aligned");
+    IAMX_REQUIRE(K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0,
+                 "K is not an upper triangular camera matrix with K[8] = 1");
+    IAMX_REQUIRE(five_point::finite(K[0]) && five_point::finite(K[4]) && K[0] != 0.0 && K[4] != 0.0,
+                 "K has a focal length that is zero or not finite");
+    IAMX_REQUIRE(five_point::finite(K[1]) && five_point::finite(K[2]) && five_point::finite(K[5]),
+                 "K has an entry that is not finite");
+    if (n_pairs == 0) return IAMX_OK;
+    const five_point::Camera cam = {K[0], K[1], K[2], K[4], K[5]};
+    hipLaunchKernelGGL(verify_pairs_essential_kernel, dim3((unsigned)n_pairs), dim3(256), 0,
+                       iamx::as_stream(stream), reinterpret_cast<const float4 *>(pts), m_off, total, cam,
+                       tol, hypotheses, seed, mask, out_model, out_essential, out_best, status);
+    return iamx::check_launch("iamx_verify_pairs_essential");
+}
+
+extern "C" int iamx_five_point(const double *rays, int n, double *E, int32_t *count, void *stream)
+{
+    IAMX_REQUIRE(n >= 0, "bad size");
+    IAMX_REQUIRE(rays && E && count, "null pointer");
+    if (n == 0) return IAMX_OK;
+    hipLaunchKernelGGL(five_point_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
+                       iamx::as_stream(stream), rays, n, E, count);
+    return iamx::check_launch("iamx_five_point");
 }
 
 extern "C" int iamx_verify_sample(int64_t n, int k, int64_t hyp, uint64_t seed, int32_t *out)

@@ -612,20 +612,27 @@ def ba_mark_outliers(e, summary, trim_stddev, max_error=None, cap=None):
 # --------------------------------------------------------------------------------------
 # RANSAC verification of pair matches (csrc/match_verify.hip)
 # --------------------------------------------------------------------------------------
-VERIFY_MODELS = {'homography': 0, 'fundamental': 1}
+VERIFY_MODELS = {'homography': 0, 'fundamental': 1, 'essential': 2}
 VERIFY_OK, VERIFY_TOO_FEW, VERIFY_NO_MODEL = 0, 1, 2
 
 
-def verify_pairs(pts, m_off, model, tol, hypotheses=2048, seed=0):
+def verify_pairs(pts, m_off, model, tol, hypotheses=2048, seed=0, K=None, return_essential=False):
     """pts [total, 4] float32 (x1 y1 x2 y2, undistorted pixels), m_off [n_pairs + 1] int64, model
-    'homography' | 'fundamental' (or the ABI's number), tol [n_pairs] float64 pixels (or one number
-    for all pairs).  Returns device tensors (mask uint8 [total], model f64 [n_pairs, 3, 3],
-    best int32 [n_pairs, 2] = hypothesis, inlier count, status int32 [n_pairs]); stream ordered,
-    nothing is synchronised."""
+    'homography' | 'fundamental' | 'essential' (or the ABI's number), tol [n_pairs] float64 pixels (or
+    one number for all pairs).  'essential' needs the camera matrix K [3, 3] (host) and samples five
+    matches on calibrated rays; the other models refuse a K.  Returns device tensors (mask uint8
+    [total], model f64 [n_pairs, 3, 3], best int32 [n_pairs, 2] = hypothesis, inlier count, status
+    int32 [n_pairs]); for 'essential' model is the pixel F = K^-T E K^-1, and return_essential adds E
+    on normalised rays [n_pairs, 3, 3] as a fifth entry.  Stream ordered, nothing is synchronised."""
     dev = require_gpu()
     code = VERIFY_MODELS.get(model, model)
-    if code not in (0, 1):
-        raise ValueError("verify_pairs: model must be 'homography' or 'fundamental', not %r" % (model,))
+    if code not in (0, 1, 2):
+        raise ValueError("verify_pairs: model must be 'homography', 'fundamental' or 'essential', "
+                         "not %r" % (model,))
+    if code == 2 and K is None:
+        raise ValueError("verify_pairs: model 'essential' needs the camera matrix K")
+    if code != 2 and (K is not None or return_essential):
+        raise ValueError("verify_pairs: K and return_essential belong to model 'essential' only")
     pts = _dev(pts, torch.float32).reshape(-1, 4)
     m_off = _dev(m_off, I64).reshape(-1)
     n_pairs, total = m_off.numel() - 1, pts.shape[0]
@@ -640,11 +647,38 @@ def verify_pairs(pts, m_off, model, tol, hypotheses=2048, seed=0):
     out_model = torch.empty((max(n_pairs, 1), 3, 3), dtype=F64, device=dev)
     best = torch.empty((max(n_pairs, 1), 2), dtype=I32, device=dev)
     status = torch.empty(max(n_pairs, 1), dtype=I32, device=dev)
+    if code == 2:
+        Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        ess = torch.empty((max(n_pairs, 1), 3, 3), dtype=F64, device=dev) if return_essential else None
+        check(lib().iamx_verify_pairs_essential(
+            _ptr(pts), _ptr(m_off), n_pairs, total, _lib.c_void_p(Kh.ctypes.data), _ptr(tol),
+            int(hypotheses), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask), _ptr(out_model),
+            _ptr(ess), _ptr(best), _ptr(status), stream_ptr()),
+            'iamx_verify_pairs_essential')
+        out = (mask[:total], out_model[:n_pairs], best[:n_pairs], status[:n_pairs])
+        return out + (ess[:n_pairs],) if return_essential else out
     check(lib().iamx_verify_pairs(_ptr(pts), _ptr(m_off), n_pairs, total, code, _ptr(tol),
                                   int(hypotheses), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(mask),
                                   _ptr(out_model), _ptr(best), _ptr(status), stream_ptr()),
           'iamx_verify_pairs')
     return mask[:total], out_model[:n_pairs], best[:n_pairs], status[:n_pairs]
+
+
+def five_point(rays):
+    """The five-point solver alone (iamx_five_point): rays [n, 5, 4] float64 (x1 y1 x2 y2 on
+    calibrated rays).  Returns device tensors (E f64 [n, 10, 3, 3]: unit Frobenius norm, largest
+    entry positive, ascending in the solver's hidden variable, NaN past the count; count int32 [n])."""
+    dev = require_gpu()
+    rays = _dev(rays, F64)
+    if rays.dim() != 3 or tuple(rays.shape[1:]) != (5, 4):
+        raise ValueError("five_point: rays must be [n, 5, 4]")
+    n = rays.shape[0]
+    E = torch.empty((max(n, 1), 10, 3, 3), dtype=F64, device=dev)
+    count = torch.empty(max(n, 1), dtype=I32, device=dev)
+    if n == 0:                      # an empty tensor has no address to pass
+        return E[:0], count[:0]
+    check(lib().iamx_five_point(_ptr(rays), n, _ptr(E), _ptr(count), stream_ptr()), 'iamx_five_point')
+    return E[:n], count[:n]
 
 
 # --------------------------------------------------------------------------------------

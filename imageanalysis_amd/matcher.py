@@ -2210,15 +2210,15 @@ def saveMatches(image_list, check_if_dirty=False):
 # geometric verification of stored match lists (scripts/lib/matcher.py:90-142)
 # --------------------------------------------------------------------------------------
 VERIFY_BATCH_MATCHES = 1 << 22          # matches per launch of verify_matches (64 MiB of points)
-_ESSENTIAL_REASON = ("transform 'essential' needs the five-point solver, which this package does not "
-                     "have; eight points projected onto the essential manifold are no stand-in on "
-                     "planar ground.  Use 'fundamental' or 'homography'.")
+VERIFY_HYPOTHESES = {'homography': 2048, 'fundamental': 2048, 'essential': 256}
+_ESSENTIAL_REASON = ("transform 'essential': the five-point solver works on calibrated rays and no "
+                     "camera matrix was given.  Pass K, or use 'fundamental' or 'homography'.")
 
 
-def _verify_transform(transform):
-    if transform == 'essential':
+def _verify_transform(transform, K=None):
+    if transform == 'essential' and K is None:
         raise NotImplementedError(_ESSENTIAL_REASON)
-    if transform not in ('homography', 'fundamental', 'none'):
+    if transform not in ('homography', 'fundamental', 'essential', 'none'):
         raise ValueError("transform must be 'homography', 'fundamental', 'essential' or 'none', "
                          "not %r" % (transform,))
     return transform
@@ -2267,12 +2267,15 @@ def _pair_keys(a):
     return (a[:, 0].astype(np.int64) << 32) | (a[:, 1].astype(np.int64) & 0xFFFFFFFF)
 
 
-def filter_by_transform(K, i1, i2, transform, hypotheses=2048, seed=0):
+def filter_by_transform(K, i1, i2, transform, hypotheses=None, seed=0):
     """The reference's filter for one direction of one pair: RANSAC on the undistorted keypoints of
     i1.match_list[i2.name] with tolerance max(1, width ** 0.25) pixels, outliers removed in place.
-    Returns True when nothing was removed.  K is unused by the two models that exist here."""
+    Returns True when nothing was removed.  K is the camera matrix 'essential' needs; the other two
+    models do not use it.  hypotheses: VERIFY_HYPOTHESES[transform] where None."""
     from . import kernels
-    _verify_transform(transform)
+    _verify_transform(transform, K)
+    if hypotheses is None:
+        hypotheses = VERIFY_HYPOTHESES.get(transform, 2048)
     matches = i1.match_list[i2.name]
     n = len(matches)
     if n < min_pairs:
@@ -2287,7 +2290,8 @@ def filter_by_transform(K, i1, i2, transform, hypotheses=2048, seed=0):
         raise ValueError("%s vs %s: a match names a keypoint that does not exist" % (i1.name, i2.name))
     pts = np.concatenate([uv1[pairs[:, 0]], uv2[pairs[:, 1]]], axis=1)
     mask, _model, _best, status = kernels.verify_pairs(pts, np.array([0, n], np.int64), transform,
-                                                       _verify_tol(i1), hypotheses, seed)
+                                                       _verify_tol(i1), hypotheses, seed,
+                                                       K=K if transform == 'essential' else None)
     keep = mask.cpu().numpy().astype(bool)
     st = int(status.cpu()[0])
     if st == kernels.VERIFY_TOO_FEW:
@@ -2304,10 +2308,12 @@ def filter_by_transform(K, i1, i2, transform, hypotheses=2048, seed=0):
 
 def _verify_launch(jobs, transform, hypotheses, seed, arena):
     """masks and statuses of a batch of jobs (a, b, pairs, tol): ONE launch, the points gathered on
-    the device from the keypoint arena.  The seam of verify_matches: tests hand in their own."""
+    the device from the keypoint arena.  The seam of verify_matches: tests hand in their own.  For
+    'essential' the arena carries the camera matrix as a third entry."""
     import torch
     from . import kernels
-    uv, base = arena
+    uv, base = arena[0], arena[1]
+    K = arena[2] if transform == 'essential' else None
     lens = [len(j[2]) for j in jobs]
     m_off = np.zeros(len(jobs) + 1, np.int64)
     np.cumsum(lens, out=m_off[1:])
@@ -2316,7 +2322,7 @@ def _verify_launch(jobs, transform, hypotheses, seed, arena):
     dev = uv.device
     pts = torch.cat([uv[torch.from_numpy(i1).to(dev)], uv[torch.from_numpy(i2).to(dev)]], dim=1)
     tol = np.array([j[3] for j in jobs], np.float64)
-    mask, _model, _best, status = kernels.verify_pairs(pts, m_off, transform, tol, hypotheses, seed)
+    mask, _model, _best, status = kernels.verify_pairs(pts, m_off, transform, tol, hypotheses, seed, K=K)
     mask, status = mask.cpu().numpy(), status.cpu().numpy()
     return [mask[m_off[k]:m_off[k + 1]] for k in range(len(jobs))], status.tolist()
 
@@ -2334,7 +2340,7 @@ def _verify_arena(proj):
     return torch.from_numpy(np.ascontiguousarray(cat)).to(require_gpu()), base
 
 
-def verify_matches(proj, K, transform, hypotheses=2048, seed=0, launch=None):
+def verify_matches(proj, K, transform, hypotheses=None, seed=0, launch=None):
     """The geometric filter over a whole project's stored match lists, after find_matches and
     before 3b: every unordered pair (a before b in proj.image_list) with a non-empty
     a.match_list[b.name] goes through iamx_verify_pairs, in batches of at most VERIFY_BATCH_MATCHES
@@ -2343,8 +2349,12 @@ def verify_matches(proj, K, transform, hypotheses=2048, seed=0, launch=None):
     forward counterpart are dropped and counted).  A list with fewer than min_pairs matches is
     emptied, in either direction, as the reference's filter does.  Running it twice filters twice.
     Single process; nothing is saved here.  `launch(jobs, transform, hypotheses, seed, arena)`
-    replaces the device launch (tests).  Returns the counts."""
-    _verify_transform(transform)
+    replaces the device launch (tests).  'essential' needs the camera matrix K and goes through
+    iamx_verify_pairs_essential; K travels to the launch as arena[2] (a launch of the caller's gets
+    (None, None, K)).  hypotheses: VERIFY_HYPOTHESES[transform] where None.  Returns the counts."""
+    _verify_transform(transform, K)
+    if hypotheses is None:
+        hypotheses = VERIFY_HYPOTHESES.get(transform, 2048)
     counts = dict(pairs=0, matches_in=0, matches_out=0, lists_emptied=0, too_few=0, no_model=0,
                   orphans_dropped=0)
     if transform == 'none':
@@ -2363,10 +2373,12 @@ def verify_matches(proj, K, transform, hypotheses=2048, seed=0, launch=None):
                 _verify_settle(a, b, fwd, np.zeros(len(fwd), bool), counts)
                 continue
             jobs.append((ia, ib, _pairs_of(fwd), _verify_tol(a)))
-    arena = None
+    arena = (None, None, np.asarray(K, np.float64).reshape(3, 3)) if transform == 'essential' else None
     if launch is None:
         launch = _verify_launch
         arena = _verify_arena(proj) if jobs else None
+        if arena is not None and transform == 'essential':
+            arena = arena + (np.asarray(K, np.float64).reshape(3, 3),)
         for ia, ib, pairs, _tol in jobs:
             na, nb = (int(arena[1][k + 1] - arena[1][k]) for k in (ia, ib))
             if pairs.min() < 0 or pairs[:, 0].max() >= na or pairs[:, 1].max() >= nb:

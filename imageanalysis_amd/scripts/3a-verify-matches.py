@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The reference's `--filter homography | fundamental` (scripts/lib/matcher.py:90-142
+"""The reference's `--filter homography | fundamental | essential` (scripts/lib/matcher.py:90-142
 filter_by_transform) as a pass of its own on the MI355X path: every stored pair's matches go through
 a RANSAC fit of the chosen two-view model on the device (matcher.verify_matches), matches that
 disagree with the pair's best model are dropped from both directions, and the .match files of the
@@ -20,8 +20,10 @@ from imageanalysis_amd import matcher, undistort
 
 ap = argparse.ArgumentParser(description='RANSAC verification of stored matches on MI355X.')
 ap.add_argument('project', help='project directory')
-ap.add_argument('--filter', required=True, choices=['homography', 'fundamental'])
-ap.add_argument('--hypotheses', type=int, default=2048, help='minimal samples tried per pair')
+ap.add_argument('--filter', required=True, choices=['homography', 'fundamental', 'essential'])
+ap.add_argument('--hypotheses', type=int, default=None,
+                help='minimal samples tried per pair (default: 2048; 256 for essential, whose five-point '
+                     'samples are all-inlier as often at an inlier share of 0.5)')
 ap.add_argument('--seed', type=int, default=0)
 ap.add_argument('--dry-run', action='store_true', help='print the counts, write nothing')
 args = ap.parse_args()

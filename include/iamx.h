@@ -1332,6 +1332,80 @@ int iamx_verify_pairs(const float *pts,      /* DEV [total][4] x1 y1 x2 y2 (undi
                       void *stream);
 int iamx_verify_sample(int64_t n, int k, int64_t hyp, uint64_t seed, int32_t *out /* HOST [k] */);
 
+/* ------------------------------------------------------------------------------------
+ * The essential model -- cv2.findEssentialMat in the same filter -- as an entry of its own.
+ * iamx_verify_pairs keeps refusing model 2.  Departures from cv2, parity UNPINNED: the error is the
+ * symmetric epipolar distance in pixels under F = K^-T E K^-1 (cv2: Sampson on rays), the number
+ * of hypotheses is fixed, the sample sequence is verify_sample's.
+ *
+ * K is a HOST array [9], row major: [fx skew cu; 0 fy cv; 0 0 1].  K[3], K[6], K[7] must be 0,
+ * K[8] must be 1, fx and fy finite and not zero; a skew is allowed.  These and the pointer,
+ * alignment and size checks of iamx_verify_pairs are made before any launch; n_pairs == 0 returns
+ * IAMX_OK without one.
+ *
+ * One workgroup per pair, everything f64 on the float32 points widened:
+ *   1. rays: y = (v - cv) / fy, x = ((u - cu) - skew y) / fx.  No Hartley normalisation.
+ *   2. hypothesis h < hypotheses draws k = 5 matches by verify_sample.
+ *   3. the 5x9 system, one row per match [ux uy u vx vy v x y 1] ((x, y) image 1, (u, v) image 2),
+ *      and its null space by Gauss-Jordan with FULL pivoting: five times the largest |a| over the
+ *      unused rows and columns (ties: the lowest row, then the lowest column); a pivot of at most
+ *      2^-40 times the largest |entry| of the system means rank < 5 and the hypothesis is passed
+ *      over; otherwise every other row is reduced in all columns.  The four free columns in
+ *      ascending order give the basis X, Y, Z, W: its own free column 1, the other free columns 0,
+ *      each pivot column -a[row][free] / a[row][pivot].
+ *   4. E = xX + yY + zZ + W.  Ten cubic constraints, row 0 det E (first row expansion), rows
+ *      1 + 3i + j the entries of (E E^T - tr(E E^T)/2) E, as a 10x20 matrix over the monomials
+ *        leading   x3 x2y xy2 y3 x2z x2 xyz xy y2z y2
+ *        trailing  xz2 xz x yz2 yz y z3 z2 z 1
+ *      Gauss-Jordan of the leading 10x10 block column by column: the row of largest |a| among rows
+ *      c .. 9 (ties: the lowest) is swapped into place c, divided by its pivot, and taken out of
+ *      every other row.  A pivot of at most 2^-40 times the largest |entry| of the matrix: passed
+ *      over.
+ *   5. row(x2z) - z row(x2), row(xyz) - z row(xy), row(y2z) - z row(y2) are B(z) [x y 1]^T = 0
+ *      with entries of degree 3, 3, 4; p(z) = det B(z) (first row expansion) has degree 10.
+ *   6. real roots of p, no randomness, the same operations for the same input: R = 1 + max |c_i| /
+ *      |c_10| (Cauchy).  A coefficient or R that is not finite, or c_10 = 0: passed over.  For
+ *      k = 1 .. 10 the derivative q = p^(10-k) has degree k; the roots found for p^(11-k), with -R
+ *      in front and R behind, cut [-R, R] into intervals.  An interval [a, b] holds a root of q
+ *      where (q(a) < 0) != (q(b) < 0) (Horner); it is bisected 32 times (48 for p itself, k = 10),
+ *      mid = (lo + hi) / 2 replacing the end whose sign it shares, and the root is the last
+ *      interval's middle.  For p itself two Newton steps z - p(z) / p'(z) follow, each kept only
+ *      where it stays inside [a, b].  Roots come out in ascending z, at most ten.
+ *   7. per root: B(z) numerically; of the cross products of its rows (0,1), (0,2), (1,2) the
+ *      first of largest norm is proportional to [x y 1]; E follows and is scaled to unit Frobenius
+ *      norm with its largest-magnitude entry positive.  F = K^-T E K^-1 in closed form (a = 1/fx,
+ *      d = 1/fy, b = -(skew d) a, c = -(a cu + b cv), e = -(d cv); G = E K^-1, F = K^-T G), scaled
+ *      the same way.  A candidate whose E or F has an entry that is not finite is passed over.
+ *   8. every candidate is scored with the fundamental model's error on the pixel F, tol in
+ *      pixels; the most inliers win, ties to the lowest hypothesis, then the earliest root.  No
+ *      cheirality test, no refit, no adaptive stop.
+ * n < 5: IAMX_VERIFY_TOO_FEW.  No candidate with an inlier (every sample of identical matches is
+ * rank deficient): IAMX_VERIFY_NO_MODEL.  Both write mask, model and best as iamx_verify_pairs
+ * does; out_essential, where given, is NaN wherever out_model is.
+ *
+ * iamx_five_point: steps 3 to 7 alone, one sample per lane, the same device function.  E[s][r] is
+ * the r-th model of sample s on its rays (unit norm, largest entry positive, ascending z);
+ * entries past count[s] are NaN.  count is 0 for a sample that is passed over.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_VERIFY_ESSENTIAL 2
+int iamx_verify_pairs_essential(const float *pts,      /* DEV [total][4] x1 y1 x2 y2 (undistorted px) */
+                                const int64_t *m_off,  /* DEV [n_pairs+1] */
+                                int n_pairs, int64_t total,
+                                const double *K,       /* HOST [9] row major */
+                                const double *tol,     /* DEV [n_pairs] px */
+                                int hypotheses, uint64_t seed,
+                                uint8_t *mask,         /* DEV [total] */
+                                double *out_model,     /* DEV [n_pairs][9]: F = K^-T E K^-1 in pixels */
+                                double *out_essential, /* DEV [n_pairs][9] or NULL: E on normalised rays */
+                                int32_t *out_best,     /* DEV [n_pairs][2] hypothesis index, inlier count */
+                                int32_t *status,       /* DEV [n_pairs] */
+                                void *stream);
+int iamx_five_point(const double *rays, /* DEV [n][5][4] x1 y1 x2 y2, normalised */
+                    int n,
+                    double *E,          /* DEV [n][10][9] */
+                    int32_t *count,     /* DEV [n] */
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

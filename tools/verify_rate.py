@@ -9,10 +9,16 @@
            rate of 157.3 TFLOPS: the public FP64 vector figure of the MI355X.
            Inputs: flat-field (homography) and relief (fundamental) scenes of
            tests/verify_reference.py with a quarter outliers, 64 distinct pairs tiled.
+  --essential
+           the essential model (iamx_verify_pairs_essential, five-point samples) beside the
+           fundamental one on the same relief scenes, 4096 x 2000 and 4096 x 200 matches at 256 and at
+           2048 hypotheses, timed the same way.  The split into solve and scoring is a straight line
+           through the two sizes of n (time = solve + n * per match): the samples, and so the solve,
+           do not depend on what is scored.
   --e2e N  bench.e2e_bench(N)'s rendered survey: seconds of matcher.find_matches, then of
            matcher.verify_matches('homography') and ('fundamental') on copies of its match lists.
 
-    python tools/verify_rate.py [--pairs 4096] [--hypotheses 2048] [--e2e 512] [--out FILE]"""
+    python tools/verify_rate.py [--pairs 4096] [--hypotheses 2048] [--essential] [--e2e 512] [--out FILE]"""
 import argparse
 import copy
 import os
@@ -33,6 +39,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--pairs', type=int, default=4096)
 ap.add_argument('--hypotheses', type=int, default=2048)
 ap.add_argument('--e2e', type=int, default=0)
+ap.add_argument('--essential', action='store_true')
 ap.add_argument('--out', default=None)
 args = ap.parse_args()
 lines = []
@@ -73,6 +80,43 @@ def kernel_rates():
                 % (model, n, ts.mean(), ts.min(), ts.max(), ts.mean() * 1e3 / args.pairs,
                    ops / (ts.mean() * 1e-3) / 1e12, 100 * ops / (ts.mean() * 1e-3) / F64_PEAK,
                    float(mask.float().mean())))
+
+
+def _timed(d_pts, d_off, model, hypotheses, K=None):
+    ts = []
+    for k in range(7):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        mask, _m, _best, status = kernels.verify_pairs(d_pts, d_off, model, vr.TOL, hypotheses, 0, K=K)
+        b.record()
+        b.synchronize()
+        if k >= 2:
+            ts.append(a.elapsed_time(b))
+    assert int((status != 0).sum()) == 0
+    return np.array(ts), float(mask.float().mean())
+
+
+def essential_rates():
+    say('iamx_verify_pairs_essential beside iamx_verify_pairs fundamental, %d pairs, relief scenes with a '
+        'quarter outliers, device events, 2 warm-up + 5 timed launches:' % args.pairs)
+    for hypotheses in (256, 2048):
+        mean = {}
+        for n in (2000, 200):
+            distinct = [vr.scene(n, 0.75, 25.0, 9000 + k)[0] for k in range(4 if n > 500 else 64)]
+            pts = np.concatenate([distinct[k % len(distinct)] for k in range(args.pairs)])
+            d_pts = torch.from_numpy(pts).cuda()
+            d_off = torch.from_numpy(np.arange(args.pairs + 1, dtype=np.int64) * n).cuda()
+            for model, K in (('fundamental', None), ('essential', vr.KMAT)):
+                ts, kept = _timed(d_pts, d_off, model, hypotheses, K)
+                mean[(model, n)] = ts.mean()
+                say('  %-11s %4d hypotheses  n = %4d   %8.2f ms (%.2f .. %.2f)   %7.2f us per pair   '
+                    'inliers kept %.3f' % (model, hypotheses, n, ts.mean(), ts.min(), ts.max(),
+                                           ts.mean() * 1e3 / args.pairs, kept))
+        for model in ('fundamental', 'essential'):
+            per = (mean[(model, 2000)] - mean[(model, 200)]) / 1800.0
+            solve = mean[(model, 200)] - 200 * per
+            say('  %-11s %4d hypotheses  line through n = 200 and 2000: %.2f ms that do not depend on n '
+                '(solve), %.2f ms per 1000 matches (scoring and mask)' % (model, hypotheses, solve, 1000 * per))
 
 
 class _Done(Exception):
@@ -126,7 +170,10 @@ def e2e(n_images):
                c['no_model']))
 
 
-kernel_rates()
+if args.essential:
+    essential_rates()
+else:
+    kernel_rates()
 if args.e2e:
     e2e(args.e2e)
 if args.out:
