@@ -452,6 +452,24 @@ __global__ __launch_bounds__(256) void extrema_multi_kernel(PyrTable T, int o_fi
 // the window is loaded, not per tap -- the round-2 tail kernel spent ~12 instructions per tap on
 // it and took 0.58 ms).
 constexpr int TAIL_PIXELS = 12800;
+// floats of `nxt`, where a tail octave stages the base of its successor at pitch (W / 2) | 1.
+// The octave's own fit, H * (W | 1) <= TAIL_PIXELS, does not bound that: with P = W | 1 the
+// successor's pitch is <= (P + 1) / 2, so (H / 2) * ((W / 2) | 1) <= TAIL_PIXELS / 4 * (1 + 1 / P)
+// -- 750 x 16 stages 375 * 9 = 3375 floats, 2560 x 5 stages 1280 * 3 = 3840.  So the staged base
+// is part of the admission test: iamx_sift_detect picks the tail octaves with tail_admits(), which
+// holds the base against the same TAIL_NEXT that sizes nxt in pyramid_tail_kernel, and a tall
+// narrow octave that fails it is built by the strip kernels instead (the same levels, bit for bit).
+constexpr int TAIL_NEXT = TAIL_PIXELS / 4 + 128;
+
+// may the one-workgroup tail build an H x W octave (has_next: it stages the base of a successor)?
+__host__ __device__ constexpr bool tail_admits(int H, int W, bool has_next)
+{
+    return (int64_t)H * (W | 1) <= TAIL_PIXELS &&
+           (!has_next || (int64_t)(H / 2) * ((W / 2) | 1) <= TAIL_NEXT);
+}
+static_assert(tail_admits(752, 16, false) && !tail_admits(750, 16, true) && tail_admits(736, 16, true),
+              "an octave whose staged base overruns nxt stays out of the tail");
+static_assert(!tail_admits(2560, 5, true) && !tail_admits(1422, 8, true), "worst cases: 3840, 3555 floats");
 
 struct TapSet {
     Taps t[NL + 2];              // layers 1 .. NL+2 (sigma of the incremental blurs)
@@ -525,9 +543,10 @@ __device__ __forceinline__ void tail_level(float *__restrict__ cur, float *__res
 
 __global__ __launch_bounds__(1024) void pyramid_tail_kernel(PyrTable T, int o_first, TapSet TS)
 {
+    // (LDS: 2 x 51 200 + 13 312 B here + 680 B of taps = 116 392 B, unchanged by tail_admits())
     __shared__ float cur[TAIL_PIXELS];
     __shared__ float hor[TAIL_PIXELS];
-    __shared__ float nxt[TAIL_PIXELS / 4 + 128];
+    __shared__ float nxt[TAIL_NEXT];
     __shared__ float sk[NL + 2][MAX_TAPS];
     __shared__ int sr[NL + 2];
     // the taps go from the kernel argument to LDS with compile-time indices (indexing the
@@ -1343,8 +1362,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVE
 //            packed octave (before the first-octave adjustment) DESCENDING
 //   order 0 (pyramid-local, rounds 1-3): octave, layer, y, x, angle ascending, then size /
 //            response / octave descending
-// then every keypoint equal to its predecessor in (x, y, size, angle) is dropped -- the first of
-// such a run (the highest response) stays, as in OpenCV's loop.
+// and of the rows equal in (x, y, size, angle) only the one that OpenCV's order puts first (the
+// highest response, then the highest packed octave) stays, as in OpenCV's loop over the sorted
+// list -- in BOTH orders: order 0 drops the rows that order 1 drops.  In order 1 such rows are
+// neighbours, so a row is dropped when it is equal to its predecessor.  In order 0 they are
+// neighbours only if they also share octave and layer; sort_rank_kernel therefore looks for an
+// equal row that precedes by (response, packed octave, row) in every (octave, layer) segment
+// whose range of sizes holds the row's (none but its own, in a detection).
 // All fields are non-negative floats, so their bit patterns order like the values; a key is six
 // 32-bit words compared lexicographically (descending fields complemented) + the row as a tie
 // break.  Keys are dealt to SORT_BUCKETS buckets by a monotone function of the leading field(s)
@@ -1393,12 +1417,32 @@ __device__ __forceinline__ SortKey make_key(const float *row, int i, const SortP
 
 __global__ __launch_bounds__(256) void sort_count_kernel(const float *__restrict__ kp,
                                                          const int32_t *__restrict__ n_out, int cap,
-                                                         SortParams P, int32_t *__restrict__ bucket_cnt)
+                                                         SortParams P, int32_t *__restrict__ bucket_cnt,
+                                                         unsigned *__restrict__ seg_range)
 {
     const int n = min(*n_out, cap);
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&bucket_cnt[make_key(kp + (int64_t)i * 8, i, P).bucket], 1);
+    SortKey k;
+    if (i < n) {
+        k = make_key(kp + (int64_t)i * 8, i, P);
+        atomicAdd(&bucket_cnt[k.bucket], 1);
+    }
+    if (P.order != 0) return;
+    // order 0: the range of the size word in every (octave, layer) segment, as two maxima over a
+    // zeroed table ([seg][0] of the word, [seg][1] of its complement; an empty segment keeps 0, 0,
+    // which no word lies between) -- first in LDS, then one global atomic per segment a workgroup saw
+    __shared__ unsigned rng[SORT_SEGS * 2];
+    rng[threadIdx.x] = 0;
+    __syncthreads();
+    if (i < n) {
+        const int seg = k.bucket / (SORT_BUCKETS / SORT_SEGS);
+        atomicMax(&rng[seg * 2], k.w[3]);
+        atomicMax(&rng[seg * 2 + 1], ~k.w[3]);
+    }
+    __syncthreads();
+    if (rng[threadIdx.x]) atomicMax(&seg_range[threadIdx.x], rng[threadIdx.x]);
 }
+static_assert(SORT_SEGS * 2 == 256, "sort_count_kernel: one thread per entry of the segment table");
 
 // exclusive scan of the bucket counts (one workgroup); also clears the fill counters
 __global__ __launch_bounds__(1024) void sort_offsets_kernel(const int32_t *__restrict__ bucket_cnt,
@@ -1445,7 +1489,8 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const float *__restri
 // one thread per key: rank inside its bucket = number of smaller keys there; dup = one of them is
 // equal in the four leading words (x, y, size, angle in either order)
 __global__ __launch_bounds__(256) void sort_rank_kernel(const SortKey *__restrict__ keys,
-                                                        const int32_t *__restrict__ bucket_off,
+                                                        const int32_t *__restrict__ bucket_off, int order,
+                                                        const unsigned *__restrict__ seg_range,
                                                         int32_t *__restrict__ rank,
                                                         unsigned *__restrict__ dup_bits,
                                                         int32_t *__restrict__ tile_cnt)
@@ -1468,6 +1513,30 @@ __global__ __launch_bounds__(256) void sort_rank_kernel(const SortKey *__restric
         if (eq) less = o.orig < me.orig;
         cnt += less;
         dup |= less && eq4;
+    }
+    // Order 0 deals the keys to (octave, layer) segments first: a row equal in (x, y, size, angle)
+    // whose packed octave differs in the octave or the layer byte sits in the same y bucket of
+    // ANOTHER segment.  OpenCV's order puts the two side by side and keeps the first (response,
+    // then packed octave descending), and order 0 drops the same rows: look there too -- but only
+    // in the segments whose range of sizes (sort_count_kernel) holds this row's.  In a detection
+    // size fixes octave and layer, the ranges are disjoint and the search costs the 128 range
+    // tests; crafted rows, with any size in any segment, walk their y band of every segment.
+    // (Measured on detection-like rows, whole sort, order 0: 116 us against 103 us without the
+    // search at 20 000 rows, 47 against 33 at 2 000, 883 against 870 at 200 000; 279 us at 20 000
+    // when every non-empty segment was walked.  Order 1 does not come here: 33 us either way.)
+    if (order == 0) {
+        constexpr int PER = SORT_BUCKETS / SORT_SEGS;
+        const int yb = me.bucket % PER;
+        for (int seg = 0; seg < SORT_SEGS && !dup; ++seg) {
+            const int b = seg * PER + yb;
+            if (b == me.bucket || me.w[3] > seg_range[seg * 2] || ~me.w[3] > seg_range[seg * 2 + 1]) continue;
+            const int hi2 = bucket_off[b + 1];
+            for (int j = bucket_off[b]; j < hi2; ++j) {
+                const SortKey o = keys[j];
+                if (o.w[0] != me.w[0] || o.w[1] != me.w[1] || o.w[2] != me.w[2] || o.w[3] != me.w[3]) continue;
+                dup |= o.w[4] != me.w[4] ? o.w[4] < me.w[4] : (o.w[5] != me.w[5] ? o.w[5] < me.w[5] : o.orig < me.orig);
+            }
+        }
     }
     const int r = lo + cnt;
     rank[i] = r;
@@ -1643,6 +1712,20 @@ extern "C" int iamx_sift_detect(const uint8_t *image, int height, int width, int
                  "bad image size / channels / capacity");
     const Layout L = make_layout(height, width, CAP_CAND);
     IAMX_REQUIRE(workspace_bytes >= L.total, "workspace too small (iamx_sift_workspace_bytes)");
+    // Which octaves go where (the issue order below says why): strip kernels on the main stream
+    // below o_side, strip kernels on the side stream down to o_tail, then ONE workgroup for the
+    // rest.  Chosen and checked here, before anything is launched or forked: what
+    // pyramid_tail_kernel indexes its LDS arrays with -- every level fits cur / hor, every staged
+    // base (the next octave at its own pitch) fits nxt.
+    constexpr int SIDE_OCTAVE = 4;
+    const int o_side = L.n_oct < SIDE_OCTAVE ? L.n_oct : SIDE_OCTAVE;
+    int o_tail = L.n_oct;
+    for (int o = L.n_oct - 1; o >= (o_side > 1 ? o_side : 1) && tail_admits(L.h[o], L.w[o], o + 1 < L.n_oct); --o)
+        o_tail = o;
+    for (int o = o_tail; o < L.n_oct; ++o)
+        IAMX_REQUIRE((int64_t)L.h[o] * (L.w[o] | 1) <= TAIL_PIXELS &&
+                         (o == o_tail || (int64_t)L.h[o] * (L.w[o] | 1) <= TAIL_NEXT),
+                     "tail octave does not fit the tail kernel's LDS");
     hipStream_t st = iamx::as_stream(stream);
     char *ws = static_cast<char *>(workspace);
     // base image, part 1: gray -> x2
@@ -1716,8 +1799,6 @@ extern "C" int iamx_sift_detect(const uint8_t *image, int height, int width, int
     // is the launch.  Issue order: levels 1..NL of the big octaves (the chain that leads to the
     // small ones) first, then the small octaves -- all their levels and extrema scans -- on a second
     // stream beside the remaining two levels and the extrema scans of the big octaves.
-    constexpr int SIDE_OCTAVE = 4;
-    const int o_side = L.n_oct < SIDE_OCTAVE ? L.n_oct : SIDE_OCTAVE;
     for (int o = 0; o < o_side; ++o) {
         if (o > 0) downsample(st, o);
         for (int i = 1; i <= NL; ++i)
@@ -1741,10 +1822,7 @@ extern "C" int iamx_sift_detect(const uint8_t *image, int height, int width, int
             blur(st, T.oct[o].g[i - 1], T.oct[o].g[i], L.h[o], L.w[o], taps[i]);
         extrema(st, o);
     }
-    // small octaves: strip kernels down to o_tail, then ONE workgroup for the rest
-    int o_tail = L.n_oct;
-    for (int o = L.n_oct - 1; o >= (o_side > 1 ? o_side : 1) && (int64_t)L.h[o] * (L.w[o] | 1) <= TAIL_PIXELS; --o)
-        o_tail = o;
+    // small octaves: strip kernels down to o_tail, then ONE workgroup for the rest (o_tail: above).
     // The one-workgroup tail (0.25 ms) only needs level NL of the last strip octave: it starts on a
     // THIRD stream as soon as that level exists, beside the octave's two remaining levels and its
     // extrema scan, and the scans of its own octaves are one launch (round 5: the chain tail ->
@@ -1812,7 +1890,7 @@ extern "C" int64_t iamx_sift_sort_workspace_bytes(int cap)
 {
     if (cap < 1) return 0;
     return (int64_t)cap * (int64_t)(sizeof(SortKey) + 4) + ((int64_t)cap / 32 + cap / 256 + 4) * 4 +
-           (3 * SORT_BUCKETS + 4) * 4 + 256;
+           (3 * SORT_BUCKETS + 2 * SORT_SEGS + 4) * 4 + 256;
 }
 
 // detectAndCompute's removeDuplicatedSorted on the lists iamx_sift_detect appended (n_out DEV [1]
@@ -1832,20 +1910,22 @@ extern "C" int iamx_sift_sort(const float *kp, const uint8_t *desc, const int32_
     char *ws = static_cast<char *>(workspace);
     SortKey *keys = reinterpret_cast<SortKey *>(ws);
     int32_t *rank = reinterpret_cast<int32_t *>(ws + (int64_t)cap * sizeof(SortKey));
-    // [dup_bits | tile_cnt | bucket_cnt] are zeroed together
+    // [dup_bits | tile_cnt | seg_range | bucket_cnt] are zeroed together
     unsigned *dup_bits = reinterpret_cast<unsigned *>(rank + cap);
     int32_t *tile_cnt = reinterpret_cast<int32_t *>(dup_bits + cap / 32 + 1);
-    int32_t *bucket_cnt = tile_cnt + cap / 256 + 1;
+    unsigned *seg_range = reinterpret_cast<unsigned *>(tile_cnt + cap / 256 + 1);
+    int32_t *bucket_cnt = reinterpret_cast<int32_t *>(seg_range + 2 * SORT_SEGS);
     int32_t *bucket_off = bucket_cnt + SORT_BUCKETS;
     int32_t *bucket_fill = bucket_off + SORT_BUCKETS + 1;
     const SortParams P{order, (float)width, (float)height};
-    (void)hipMemsetAsync(dup_bits, 0, ((size_t)cap / 32 + 1 + cap / 256 + 1 + SORT_BUCKETS) * 4, st);
+    (void)hipMemsetAsync(dup_bits, 0, ((size_t)cap / 32 + 1 + cap / 256 + 1 + 2 * SORT_SEGS + SORT_BUCKETS) * 4, st);
     const unsigned g = blocks(cap, 256);
-    hipLaunchKernelGGL(sort_count_kernel, dim3(g), dim3(256), 0, st, kp, n_out, cap, P, bucket_cnt);
+    hipLaunchKernelGGL(sort_count_kernel, dim3(g), dim3(256), 0, st, kp, n_out, cap, P, bucket_cnt, seg_range);
     hipLaunchKernelGGL(sort_offsets_kernel, dim3(1), dim3(1024), 0, st, bucket_cnt, bucket_off, bucket_fill);
     hipLaunchKernelGGL(sort_scatter_kernel, dim3(g), dim3(256), 0, st, kp, n_out, cap, P, bucket_off,
                        bucket_fill, keys);
-    hipLaunchKernelGGL(sort_rank_kernel, dim3(g), dim3(256), 0, st, keys, bucket_off, rank, dup_bits, tile_cnt);
+    hipLaunchKernelGGL(sort_rank_kernel, dim3(g), dim3(256), 0, st, keys, bucket_off, order, seg_range,
+                       rank, dup_bits, tile_cnt);
     hipLaunchKernelGGL(sort_compact_kernel, dim3(1), dim3(1024), 0, st, bucket_off, tile_cnt, n_sorted);
     hipLaunchKernelGGL(sort_gather_kernel, dim3(blocks((int64_t)cap * 8, 256)), dim3(256), 0, st, keys,
                        rank, dup_bits, tile_cnt, bucket_off, kp, desc, out_kp, out_desc);

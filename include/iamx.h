@@ -766,7 +766,13 @@ int iamx_surface_grid(const void *records, int num_triangles, const double *valu
  * rest of detectAndCompute: KeyPointsFilter::removeDuplicatedSorted (duplicates dropped, OpenCV's
  * output order).  Behind the float32 pyramid the arithmetic follows OpenCV's sift.simd.hpp scalar
  * code in float32 (adjustLocalExtrema with Matx33f::solve, calcOrientationHist,
- * calcSIFTDescriptor, hal::fastAtan2); oracle/sift_oracle.py states the three departures.
+ * calcSIFTDescriptor, hal::fastAtan2); oracle/sift_oracle.py and DESIGN.md section 2 state the
+ * four departures: (a) - (c) in the arithmetic, (d) the 33-tap limit, which is this:
+ *   sigma      a Gaussian kernel keeps at most 33 taps: its radius is capped at 16 and the kept taps
+ *              are renormalised.  The levels are OpenCV's Gaussians (round(8 s + 1) | 1 taps for a
+ *              blur of s) only while every layer's round(8 sigma_i + 1) | 1 <= 33, i.e. for
+ *              sigma <= 2.10 (the widest layer blur is 1.9312 sigma); above that the upper layers
+ *              of every octave are truncated Gaussians, which cv2 would not produce.
  * ------------------------------------------------------------------------------------ */
 int64_t iamx_sift_workspace_bytes(int height, int width);
 int iamx_sift_detect(const uint8_t *image, int height, int width, int channels,

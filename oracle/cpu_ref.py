@@ -156,7 +156,8 @@ def _ptr_array(arrays):
     return (ctypes.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
 
 
-def sift_keypoints(dogs, gauss, octave, cand, sigma0, nthreads=0):
+def sift_keypoints(dogs, gauss, octave, cand, sigma0, nthreads=0, contrast_threshold=0.04,
+                   edge_threshold=10.0):
     """dogs / gauss: the float32 levels of one octave; cand int32 [n,3] (layer, r, c) ->
     keypoints float64 [m,6] in the candidates' order"""
     dogs = [np.ascontiguousarray(d, np.float32) for d in dogs]
@@ -165,13 +166,14 @@ def sift_keypoints(dogs, gauss, octave, cand, sigma0, nthreads=0):
     h, w = dogs[0].shape
     cap = max(4 * len(cand), 16)
     L = lib()
-    L.oracle_sift_keypoints.restype = ctypes.c_int
+    L.oracle_sift_keypoints_p.restype = ctypes.c_int
     while True:
         kps = np.empty((cap, 6), np.float64)
-        n = L.oracle_sift_keypoints(_ptr_array(dogs), _ptr_array(gauss), ctypes.c_int(h),
-                                    ctypes.c_int(w), ctypes.c_int(octave), _p(cand),
-                                    ctypes.c_int(len(cand)), ctypes.c_double(sigma0), _p(kps),
-                                    ctypes.c_int(cap), ctypes.c_int(nthreads))
+        n = L.oracle_sift_keypoints_p(_ptr_array(dogs), _ptr_array(gauss), ctypes.c_int(h),
+                                      ctypes.c_int(w), ctypes.c_int(octave), _p(cand),
+                                      ctypes.c_int(len(cand)), ctypes.c_double(sigma0),
+                                      ctypes.c_double(contrast_threshold), ctypes.c_double(edge_threshold),
+                                      _p(kps), ctypes.c_int(cap), ctypes.c_int(nthreads))
         if n < 0:
             raise ValueError("oracle_sift_keypoints rc=%d" % n)
         if n <= cap:
@@ -191,18 +193,22 @@ def sift_descriptors(img, par, nthreads=0):
     return desc
 
 
-def sift_detect(gray, cap=None, nthreads=0):
-    """the whole detector + descriptor in C (oracle/sift_ref.c oracle_sift_detect): gray uint8
-    [h,w] -> (kps float64 [n,6], desc uint8 [n,128]), duplicates removed, OpenCV's output order"""
+def sift_detect(gray, cap=None, nthreads=0, sigma=1.6, contrast_threshold=0.04, edge_threshold=10.0,
+                max_radius=None):
+    """the whole detector + descriptor in C (oracle/sift_ref.c oracle_sift_detect_p): gray uint8
+    [h,w] -> (kps float64 [n,6], desc uint8 [n,128]), duplicates removed, OpenCV's output order.
+    max_radius: tap-radius cap of the Gaussian kernels (None: cv2's whole kernels)"""
     gray = np.ascontiguousarray(gray, np.uint8)
     h, w = gray.shape
     cap = int(cap or max(h * w // 8, 4096))
     kps = np.empty((cap, 6), np.float64)
     desc = np.empty((cap, 128), np.uint8)
     L = lib()
-    L.oracle_sift_detect.restype = ctypes.c_int
-    n = L.oracle_sift_detect(_p(gray), ctypes.c_int(h), ctypes.c_int(w), _p(kps), _p(desc),
-                             ctypes.c_int(cap), ctypes.c_int(nthreads))
+    L.oracle_sift_detect_p.restype = ctypes.c_int
+    n = L.oracle_sift_detect_p(_p(gray), ctypes.c_int(h), ctypes.c_int(w), ctypes.c_double(sigma),
+                               ctypes.c_double(contrast_threshold), ctypes.c_double(edge_threshold),
+                               ctypes.c_int(-1 if max_radius is None else int(max_radius)),
+                               _p(kps), _p(desc), ctypes.c_int(cap), ctypes.c_int(nthreads))
     if n < 0:
         raise ValueError("oracle_sift_detect rc=%d" % n)
     return kps[:n].copy(), desc[:n].copy()

@@ -22,10 +22,13 @@ fma(v, k[t], acc) from 0 in ascending tap order -- a filter compiled for FMA har
 the pyramid is separately rounded float32.  From round 4 on everything behind the pyramid follows
 OpenCV's float32 scalar code paths operation by operation (sift.simd.hpp adjustLocalExtrema with
 Matx33f::solve = Cramer's rule, calcOrientationHist, calcSIFTDescriptor, hal::fastAtan2's
-polynomial, KeyPointsFilter::removeDuplicatedSorted and its output order), with three stated
-exceptions (DESIGN.md section 2): the Gaussian weights use exp32() below instead of hal::exp32f's
-table, cosf / sinf / powf are the correctly rounded float32 values, and every histogram bin is
-the exact sum of OpenCV's float32 terms rounded once instead of a running float32 sum.
+polynomial, KeyPointsFilter::removeDuplicatedSorted and its output order), with four stated
+exceptions: (a) the Gaussian weights use exp32() below instead of
+hal::exp32f's table, (b) cosf / sinf / powf are the correctly rounded float32 values, (c) every
+histogram bin is the exact sum of OpenCV's float32 terms rounded once instead of a running float32
+sum, and (d) only where it is asked for with max_radius: a Gaussian kernel cut to that radius and
+renormalised over the kept taps, which is what the device computes with max_radius=16 (its 33
+taps; OpenCV's whole kernels fit them while sigma <= 2.10).
 """
 import math
 
@@ -81,11 +84,15 @@ def resize_linear_2x(img):
     return (top * (F(1) - ty)[:, None] + bot * ty[:, None]).astype(np.float32)
 
 
-def gaussian_kernel(sigma):
+def gaussian_kernel(sigma, max_radius=None):
     """cv2.GaussianBlur(img, Size(), sigma) for CV_32F: ksize = round(sigma*8 + 1) | 1,
-    coefficients exp(-x^2 / 2 sigma^2) normalised to sum 1."""
+    coefficients exp(-x^2 / 2 sigma^2) normalised to sum 1.  max_radius (not cv2's): the taps
+    beyond that radius are dropped and the kept ones normalised to sum 1 -- the truncated
+    Gaussians of a filter with a fixed tap budget (csrc/sift.hip keeps 33 taps: max_radius=16)."""
     ksize = int(round(sigma * 8 + 1)) | 1
     r = ksize // 2
+    if max_radius is not None:
+        r = min(r, int(max_radius))
     x = np.arange(-r, r + 1, dtype=np.float64)
     k = np.exp(-(x * x) / (2.0 * sigma * sigma))
     total = 0.0
@@ -126,10 +133,10 @@ def fma32(a, b, c):
     return r.astype(np.float32)
 
 
-def gaussian_blur_py(img, sigma):
+def gaussian_blur_py(img, sigma, max_radius=None):
     """separable, BORDER_REFLECT_101, fused multiply-add taps in ascending order (numpy twin of
     oracle/sift_ref.c blur_rows)."""
-    k = gaussian_kernel(sigma)
+    k = gaussian_kernel(sigma, max_radius)
     r = len(k) // 2
     h, w = img.shape
     xs = np.arange(w)
@@ -143,28 +150,31 @@ def gaussian_blur_py(img, sigma):
     return out
 
 
-def gaussian_blur(img, sigma):
+def gaussian_blur(img, sigma, max_radius=None):
     from . import cpu_ref
-    return cpu_ref.sift_blur(img, gaussian_kernel(sigma))
+    return cpu_ref.sift_blur(img, gaussian_kernel(sigma, max_radius))
 
 
-def layer_sigmas():
+def layer_sigmas(sigma=SIGMA):
     k = 2.0 ** (1.0 / N_OCTAVE_LAYERS)
-    sig = [SIGMA]
+    sig = [sigma]
     for i in range(1, N_OCTAVE_LAYERS + 3):
-        sp = (k ** (i - 1)) * SIGMA
+        sp = (k ** (i - 1)) * sigma
         st = sp * k
         sig.append(math.sqrt(st * st - sp * sp))
     return sig
 
 
-def build_pyramids(bgr_or_gray):
+def build_pyramids(bgr_or_gray, sigma=SIGMA, max_radius=None):
+    """buildGaussianPyramid / buildDoGPyramid for SIFT_create(sigma=sigma).  max_radius: see
+    gaussian_kernel()."""
+    sigma = float(sigma)
     gray = bgr_to_gray(bgr_or_gray) if bgr_or_gray.ndim == 3 else bgr_or_gray
     base = resize_linear_2x(gray.astype(np.float32))
-    sig_diff = math.sqrt(max(SIGMA * SIGMA - 4.0 * 0.5 * 0.5, 0.01))
-    base = gaussian_blur(base, sig_diff)
+    sig_diff = math.sqrt(max(sigma * sigma - 4.0 * 0.5 * 0.5, 0.01))
+    base = gaussian_blur(base, sig_diff, max_radius)
     n_oct = int(round(math.log(min(base.shape)) / math.log(2.0) - 2)) + 1
-    sig = layer_sigmas()
+    sig = layer_sigmas(sigma)
     gauss, dog = [], []
     for o in range(n_oct):
         lv = []
@@ -175,7 +185,7 @@ def build_pyramids(bgr_or_gray):
                 src = gauss[o - 1][N_OCTAVE_LAYERS]      # INTER_NEAREST to (w//2, h//2)
                 lv.append(np.ascontiguousarray(src[:src.shape[0] // 2 * 2:2, :src.shape[1] // 2 * 2:2]))
             else:
-                lv.append(gaussian_blur(lv[i - 1], sig[i]))
+                lv.append(gaussian_blur(lv[i - 1], sig[i], max_radius))
         gauss.append(lv)
         dog.append([lv[i + 1] - lv[i] for i in range(N_OCTAVE_LAYERS + 2)])
     return gauss, dog
@@ -262,7 +272,8 @@ def _solve3_cramer(a, b):
     return [x0, x1, x2]
 
 
-def _adjust_local_extrema(dogs, layer, r, c):
+def _adjust_local_extrema(dogs, layer, r, c, contrast_threshold=CONTRAST_THRESHOLD,
+                          edge_threshold=EDGE_THRESHOLD):
     """adjustLocalExtrema (sift.simd.hpp): 3-D quadratic refinement, contrast and edge tests, all
     float32.  Returns None or (layer, r, c, xi, xr, xc, contr) with float32 offsets."""
     img_scale = F(1.0 / 255.0)
@@ -304,7 +315,7 @@ def _adjust_local_extrema(dogs, layer, r, c):
           F(F(nxt[r, c] - prv[r, c]) * deriv_scale)]
     t = F(F(F(F(0) + F(dD[0] * xc)) + F(dD[1] * xr)) + F(dD[2] * xi))           # Matx::dot
     contr = F(F(img[r, c] * img_scale) + F(t * F(0.5)))
-    if F(abs(contr) * F(N_OCTAVE_LAYERS)) < F(CONTRAST_THRESHOLD):
+    if F(abs(contr) * F(N_OCTAVE_LAYERS)) < F(contrast_threshold):
         return None
     v2 = F(img[r, c] * F(2))
     dxx = F(F(F(img[r, c + 1] + img[r, c - 1]) - v2) * second_scale)
@@ -312,13 +323,13 @@ def _adjust_local_extrema(dogs, layer, r, c):
     dxy = F(F(F(F(img[r + 1, c + 1] - img[r + 1, c - 1]) - img[r - 1, c + 1]) + img[r - 1, c - 1]) * cross_scale)
     tr = F(dxx + dyy)
     det = F(F(dxx * dyy) - F(dxy * dxy))
-    e = F(EDGE_THRESHOLD)
+    e = F(edge_threshold)
     if det <= 0 or F(F(tr * tr) * e) >= F(F(F(e + F(1)) * F(e + F(1))) * det):
         return None
     return layer, r, c, xi, xr, xc, contr
 
 
-def _keypoint_fields(o, layer, r, c, xi, xr, xc, contr):
+def _keypoint_fields(o, layer, r, c, xi, xr, xc, contr, sigma=SIGMA):
     """the KeyPoint adjustLocalExtrema fills in (float32 fields, octave-0 = doubled image
     coordinates): x, y, size, |contrast|, packed octave"""
     scale = F(1 << o)
@@ -326,7 +337,7 @@ def _keypoint_fields(o, layer, r, c, xi, xr, xc, contr):
     py = F(F(F(r) + xr) * scale)
     octave = o + (layer << 8) + (cv_round((float(xi) + 0.5) * 255) << 16)
     e = F(F(F(layer) + xi) / F(N_OCTAVE_LAYERS))
-    size = F(F(F(F(SIGMA) * F(2.0 ** float(e))) * scale) * F(2))              # powf(2.f, e)
+    size = F(F(F(F(sigma) * F(2.0 ** float(e))) * scale) * F(2))              # powf(2.f, e)
     return px, py, size, F(abs(contr)), octave
 
 
@@ -392,14 +403,18 @@ def _orientation_peaks(hist):
     return out
 
 
-def detect(bgr_or_gray, use_c=True):
+def detect(bgr_or_gray, use_c=True, sigma=SIGMA, contrast_threshold=CONTRAST_THRESHOLD,
+           edge_threshold=EDGE_THRESHOLD, max_radius=None):
     """findScaleSpaceExtrema + the first-octave rescale of detectAndCompute -> (keypoints [N,6]
     float64 holding float32 values: x, y, size, angle, response, octave(packed int) in the
     order candidates are visited (octave, layer, row major, peak) -- NOT yet de-duplicated or
     sorted, see remove_duplicated_sorted() --, Gaussian pyramid).
-    use_c: refinement + orientation through oracle/sift_ref.c (OpenMP), else the numpy twin."""
-    gauss, dog = build_pyramids(bgr_or_gray)
-    threshold = math.floor(0.5 * CONTRAST_THRESHOLD / N_OCTAVE_LAYERS * 255)
+    use_c: refinement + orientation through oracle/sift_ref.c (OpenMP), else the numpy twin.
+    sigma, contrast_threshold, edge_threshold: the arguments of cv2.SIFT_create of the same names
+    (its defaults); max_radius: see gaussian_kernel()."""
+    sigma = float(sigma)
+    gauss, dog = build_pyramids(bgr_or_gray, sigma=sigma, max_radius=max_radius)
+    threshold = math.floor(0.5 * contrast_threshold / N_OCTAVE_LAYERS * 255)
     kps = []
     for o, dogs in enumerate(dog):
         h, w = dogs[0].shape
@@ -425,11 +440,11 @@ def detect(bgr_or_gray, use_c=True):
                 cands.append(np.stack([np.full(len(rr), layer), rr + IMG_BORDER, cc + IMG_BORDER], 1))
                 continue
             for r, c in zip(rr + IMG_BORDER, cc + IMG_BORDER):
-                res = _adjust_local_extrema(dogs, layer, int(r), int(c))
+                res = _adjust_local_extrema(dogs, layer, int(r), int(c), contrast_threshold, edge_threshold)
                 if res is None:
                     continue
                 l2, r2, c2, xi, xr, xc, contr = res
-                px, py, size, resp, octave = _keypoint_fields(o, l2, r2, c2, xi, xr, xc, contr)
+                px, py, size, resp, octave = _keypoint_fields(o, l2, r2, c2, xi, xr, xc, contr, sigma)
                 scl_octv = F(F(size * F(0.5)) / F(1 << o))
                 hist = _orientation_hist(gauss[o][l2], r2, c2, cv_round(F(F(ORI_RADIUS) * scl_octv)),
                                          F(F(ORI_SIG_FCTR) * scl_octv))
@@ -437,7 +452,9 @@ def detect(bgr_or_gray, use_c=True):
                     kps.append([px, py, size, angle, resp, octave])
         if use_c and cands:
             from . import cpu_ref
-            kps.extend(cpu_ref.sift_keypoints(dogs, gauss[o], o, np.concatenate(cands), SIGMA).tolist())
+            kps.extend(cpu_ref.sift_keypoints(dogs, gauss[o], o, np.concatenate(cands), sigma,
+                                              contrast_threshold=contrast_threshold,
+                                              edge_threshold=edge_threshold).tolist())
     kps = np.array(kps, np.float64).reshape(-1, 6)
     # first octave is -1: rescale to the input image (detectAndCompute; x 0.5 is exact in float32)
     if len(kps):
@@ -576,14 +593,17 @@ def descriptor_params(kps):
     return par, level
 
 
-def detect_and_compute(bgr_or_gray, use_c=True, order='opencv', return_removed=False):
+def detect_and_compute(bgr_or_gray, use_c=True, order='opencv', return_removed=False, sigma=SIGMA,
+                       contrast_threshold=CONTRAST_THRESHOLD, edge_threshold=EDGE_THRESHOLD,
+                       max_radius=None):
     """cv2.SIFT_create().detectAndCompute(img, None) -> keypoints [N,6] (x, y, size, angle,
     response, packed octave; float32 values) and descriptors [N,128] u8, duplicates removed
     (KeyPointsFilter::removeDuplicatedSorted) and in OpenCV's output order (order='opencv') or in
     the pyramid-local (octave, layer, y, x, angle) order (order='canonical').
     use_c: the per-keypoint loops through oracle/sift_ref.c (OpenMP), else their numpy twins
-    (small images only)."""
-    kps, gauss = detect(bgr_or_gray, use_c=use_c)
+    (small images only).  sigma, contrast_threshold, edge_threshold, max_radius: see detect()."""
+    kps, gauss = detect(bgr_or_gray, use_c=use_c, sigma=sigma, contrast_threshold=contrast_threshold,
+                        edge_threshold=edge_threshold, max_radius=max_radius)
     kps, _idx, removed = remove_duplicated_sorted(kps)
     des = np.zeros((len(kps), 128), np.uint8)
     par, level = descriptor_params(kps)
@@ -601,12 +621,14 @@ def detect_and_compute(bgr_or_gray, use_c=True, order='opencv', return_removed=F
     return (kps, des, removed) if return_removed else (kps, des)
 
 
-def detect_and_compute_c(bgr_or_gray, order='opencv'):
+def detect_and_compute_c(bgr_or_gray, order='opencv', sigma=SIGMA, contrast_threshold=CONTRAST_THRESHOLD,
+                         edge_threshold=EDGE_THRESHOLD, max_radius=None):
     """detect_and_compute() with nothing but oracle/sift_ref.c underneath (OpenMP): the form
     bench.py times as the CPU baseline of the SIFT section"""
     from . import cpu_ref
     gray = bgr_to_gray(bgr_or_gray) if bgr_or_gray.ndim == 3 else bgr_or_gray
-    kps, des = cpu_ref.sift_detect(gray)
+    kps, des = cpu_ref.sift_detect(gray, sigma=sigma, contrast_threshold=contrast_threshold,
+                                   edge_threshold=edge_threshold, max_radius=max_radius)
     if order == 'canonical' and len(kps):
         sel = canonical_order(kps, des)
         kps, des = kps[sel], des[sel]

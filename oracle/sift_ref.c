@@ -153,7 +153,7 @@ typedef struct {
 
 /* sift_oracle._adjust_local_extrema = adjustLocalExtrema of sift.simd.hpp (float32 throughout) */
 static int adjust_local_extrema(const float *const *dogs, int h, int w, int layer, int r, int c,
-                                refined_t *out)
+                                float contrast_threshold, float edge_threshold, refined_t *out)
 {
     const float img_scale = 1.f / 255.f;
     const float deriv_scale = img_scale * 0.5f, second_scale = img_scale, cross_scale = img_scale * 0.25f;
@@ -195,13 +195,13 @@ static int adjust_local_extrema(const float *const *dogs, int h, int w, int laye
         float t = 0.f;                                   /* Matx::dot */
         t += dD[0] * xc; t += dD[1] * xr; t += dD[2] * xi;
         const float contr = AT(img, r, c) * img_scale + t * 0.5f;
-        if (fabsf(contr) * (float)NL < 0.04f) return 0;
+        if (fabsf(contr) * (float)NL < contrast_threshold) return 0;
         const float v2 = AT(img, r, c) * 2.f;
         const float dxx = (AT(img, r, c + 1) + AT(img, r, c - 1) - v2) * second_scale;
         const float dyy = (AT(img, r + 1, c) + AT(img, r - 1, c) - v2) * second_scale;
         const float dxy = (AT(img, r + 1, c + 1) - AT(img, r + 1, c - 1) - AT(img, r - 1, c + 1) + AT(img, r - 1, c - 1)) * cross_scale;
         const float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
-        const float e = 10.f;
+        const float e = edge_threshold;
         if (det <= 0 || tr * tr * e >= (e + 1) * (e + 1) * det) return 0;
         out->layer = layer; out->r = r; out->c = c;
         out->xi = xi; out->xr = xr; out->xc = xc; out->contr = contr;
@@ -267,8 +267,9 @@ static int orientation_peaks(const float *img, int h, int w, int r, int c, int r
  * angle, |contrast| (float32 values), packed octave in the coordinates of the DOUBLED image
  * (detect() halves them afterwards).  Returns the number of keypoints (may exceed cap: only cap
  * are stored). */
-int oracle_sift_keypoints(const float *const *dogs, const float *const *gauss, int h, int w, int o,
-                          const int32_t *cand, int n, double sigma0, double *kps, int cap, int nthreads)
+int oracle_sift_keypoints_p(const float *const *dogs, const float *const *gauss, int h, int w, int o,
+                            const int32_t *cand, int n, double sigma0, double contrast_threshold,
+                            double edge_threshold, double *kps, int cap, int nthreads)
 {
     if (!dogs || !gauss || !cand || !kps) return -1;
 #ifdef _OPENMP
@@ -285,7 +286,9 @@ int oracle_sift_keypoints(const float *const *dogs, const float *const *gauss, i
 #pragma omp parallel for schedule(dynamic, 64)
     for (int k = 0; k < n; ++k) {
         refined_t R;
-        if (!adjust_local_extrema(dogs, h, w, cand[3 * k], cand[3 * k + 1], cand[3 * k + 2], &R)) continue;
+        if (!adjust_local_extrema(dogs, h, w, cand[3 * k], cand[3 * k + 1], cand[3 * k + 2],
+                                  (float)contrast_threshold, (float)edge_threshold, &R))
+            continue;
         const float scale = (float)(1 << o);
         const float e = ((float)R.layer + R.xi) / (float)NL;
         const float size = sigma * (float)exp2((double)e) * scale * 2.f;     /* powf(2.f, e) */
@@ -315,6 +318,13 @@ int oracle_sift_keypoints(const float *const *dogs, const float *const *gauss, i
     }
     free(cnt); free(loc); free(more);
     return total;
+}
+
+/* the defaults of cv2.SIFT_create(): contrastThreshold 0.04, edgeThreshold 10 */
+int oracle_sift_keypoints(const float *const *dogs, const float *const *gauss, int h, int w, int o,
+                          const int32_t *cand, int n, double sigma0, double *kps, int cap, int nthreads)
+{
+    return oracle_sift_keypoints_p(dogs, gauss, h, w, o, cand, n, sigma0, 0.04, 10.0, kps, cap, nthreads);
 }
 
 /* sift_oracle.descriptor = calcSIFTDescriptor (float32 throughout; bins = exact sums rounded once) */
@@ -450,12 +460,15 @@ int oracle_sift_remove_duplicated_sorted(double *kps, int n)
  * baseline of bench.py's SIFT section; tests/test_oracle.py checks it against the numpy oracle.
  * Output: duplicates removed and in OpenCV's order (KeyPointsFilter::removeDuplicatedSorted).
  * ------------------------------------------------------------------------------------------- */
-static void gaussian_taps(double sigma, float *k, int *r_out)
+/* max_radius >= 0: the taps beyond it are dropped and the kept ones renormalised (sift_oracle.
+ * gaussian_kernel(sigma, max_radius)); < 0: cv2's kernel */
+static void gaussian_taps(double sigma, int max_radius, float *k, int *r_out)
 {
     int ksize = (int)lrint(sigma * 8 + 1) | 1;
     int r = ksize / 2;
     double kd[129], sum = 0;
     if (r > 64) r = 64;
+    if (max_radius >= 0 && r > max_radius) r = max_radius;
     for (int i = -r; i <= r; ++i) {
         kd[i + r] = exp(-(double)(i * i) / (2.0 * sigma * sigma));
         sum += kd[i + r];
@@ -496,16 +509,16 @@ static void resize2x(const uint8_t *gray, int h, int w, float *dst)
     }
 }
 
-int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *desc, int cap,
-                       int nthreads)
+int oracle_sift_detect_p(const uint8_t *gray, int h, int w, double sigma0, double contrast_threshold,
+                         double edge_threshold, int max_radius, double *kps, uint8_t *desc, int cap,
+                         int nthreads)
 {
-    if (!gray || !kps || !desc || h < 2 || w < 2) return -1;
+    if (!gray || !kps || !desc || h < 2 || w < 2 || !(sigma0 > 0)) return -1;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #else
     (void)nthreads;
 #endif
-    const double sigma0 = 1.6;
     int H = 2 * h, W = 2 * w;
     int n_oct = (int)lrint(log((double)(H < W ? H : W)) / log(2.0) - 2) + 1;
     if (n_oct < 1) n_oct = 1;
@@ -533,7 +546,7 @@ int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *
         if (o == 0) {
             float *up = (float *)malloc(sizeof(float) * npx);
             resize2x(gray, h, w, up);
-            gaussian_taps(sqrt(fmax(sigma0 * sigma0 - 1.0, 0.01)), taps, &r);
+            gaussian_taps(sqrt(fmax(sigma0 * sigma0 - 1.0, 0.01)), max_radius, taps, &r);
             blur_rows(up, H, W, taps, r, tmp, g[0]);
             free(up);
         } else {
@@ -544,14 +557,14 @@ int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *
                 for (int x = 0; x < W; ++x) g[0][(size_t)y * W + x] = src[(size_t)(2 * y) * sw + 2 * x];
         }
         for (int i = 1; i < NL + 3; ++i) {
-            gaussian_taps(sig[i], taps, &r);
+            gaussian_taps(sig[i], max_radius, taps, &r);
             blur_rows(g[i - 1], H, W, taps, r, tmp, g[i]);
 #pragma omp parallel for schedule(static)
             for (size_t q = 0; q < npx; ++q) dg[i - 1][q] = g[i][q] - g[i - 1][q];
         }
         /* extrema: candidates per (layer, row) counted, then written in order */
         if (H > 2 * IMG_BORDER && W > 2 * IMG_BORDER) {
-            const float threshold = floorf(0.5f * 0.04f / NL * 255.f);
+            const float threshold = (float)floor(0.5 * contrast_threshold / NL * 255);
             const int rows = H - 2 * IMG_BORDER;
             int *cnt = (int *)calloc((size_t)NL * rows + 1, sizeof(int));
             for (int pass = 0; pass < 2; ++pass) {
@@ -591,8 +604,9 @@ int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *
                 if (pass == 1) {
                     const int n_c = cnt[NL * rows];
                     const int room = cap - total > 0 ? cap - total : 0;
-                    const int got = oracle_sift_keypoints((const float *const *)dg, (const float *const *)g, H, W,
-                                                          o, cand, n_c, sigma0, kps + (size_t)total * 6, room, 0);
+                    const int got = oracle_sift_keypoints_p((const float *const *)dg, (const float *const *)g, H, W,
+                                                            o, cand, n_c, sigma0, contrast_threshold,
+                                                            edge_threshold, kps + (size_t)total * 6, room, 0);
                     if (got > 0) total += got < room ? got : room;
                     free(cand);
                 }
@@ -626,4 +640,11 @@ int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *
     for (int q = 0; q < n_oct * (NL + 2); ++q) free(dogs[q]);
     free(gauss); free(dogs); free(oh); free(ow); free(tmp);
     return total;
+}
+
+/* cv2.SIFT_create() with its defaults (sigma 1.6, contrastThreshold 0.04, edgeThreshold 10, whole kernels) */
+int oracle_sift_detect(const uint8_t *gray, int h, int w, double *kps, uint8_t *desc, int cap,
+                       int nthreads)
+{
+    return oracle_sift_detect_p(gray, h, w, 1.6, 0.04, 10.0, -1, kps, desc, cap, nthreads);
 }
