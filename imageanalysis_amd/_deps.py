@@ -61,9 +61,10 @@ def smart():
 
 
 def srtm():
-    """lib.srtm (SRTM tile download + interpolation, scripts/lib/srtm.py) when the reference
-    environment is there, else None.  Out of scope here (network + tile cache); the smart mirror
-    delegates update_srtm_elevations() to it exactly like the reference does."""
+    """lib.srtm (scripts/lib/srtm.py) when the reference environment is there, so that the terrain
+    process.py initialised is the one read; else imageanalysis_amd.srtm, its mirror (tiles from the
+    cache directory only, look-ups and ray hits on the device).  Not in REPLACED: no shim takes
+    lib/srtm.py's place."""
     if 'srtm' not in _resolved:
         mod = None
         if HAVE_PROPS:
@@ -71,5 +72,7 @@ def srtm():
                 mod = importlib.import_module('lib.srtm')
             except Exception:
                 mod = None
+        if mod is None:
+            mod = importlib.import_module('imageanalysis_amd.srtm')
         _resolved['srtm'] = mod
     return _resolved['srtm']

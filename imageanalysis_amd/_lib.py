@@ -127,6 +127,12 @@ SIGNATURES = {
                                     c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'iamx_surface_grid': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4
                           + [c_int, c_void_p, c_int, c_int, c_int, c_double, c_int] + [c_void_p] * 5),
+    'iamx_terrain_heights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p]),
+    'iamx_terrain_rays': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_int] + [c_void_p] * 4),
+    'iamx_terrain_rays_vec': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_int] + [c_void_p] * 4),
     'iamx_jpeg_info': (c_int, [c_void_p, c_int64, c_void_p]),
     'iamx_jpeg_decode_coefficients': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'iamx_jpeg_workspace_bytes': (c_int64, [c_void_p]),

@@ -1578,6 +1578,82 @@ def surface_grid(surface, M, ned, avg_ground, uv, no_extrapolate=False, ground_m
 
 
 # --------------------------------------------------------------------------------------
+# terrain under the survey (csrc/terrain.hip)
+# --------------------------------------------------------------------------------------
+TERRAIN_SKY, TERRAIN_CAPPED, TERRAIN_LEFT_GRID = 1, 2, 4
+TERRAIN_MAX_AXIS = 32768
+TERRAIN_FILL = -32768.0
+
+
+class Terrain(object):
+    """The axes and the grid of a RegularGridInterpolator((axis_n, axis_e), grid) on the device."""
+
+    def __init__(self, axis_n, axis_e, grid):
+        axis_n = np.ascontiguousarray(axis_n, np.float64).reshape(-1)
+        axis_e = np.ascontiguousarray(axis_e, np.float64).reshape(-1)
+        grid = np.ascontiguousarray(grid, np.float64)
+        self.rows, self.cols = int(axis_n.shape[0]), int(axis_e.shape[0])
+        if grid.shape != (self.rows, self.cols):
+            raise ValueError("a grid of %r over axes of %d and %d nodes" % (grid.shape, self.rows, self.cols))
+        for a in (axis_n, axis_e):
+            if not 2 <= a.shape[0] <= TERRAIN_MAX_AXIS or not np.all(np.diff(a) > 0):
+                raise ValueError("a terrain axis is strictly ascending with 2 to %d nodes" % TERRAIN_MAX_AXIS)
+        self.axis_n, self.axis_e, self.grid = _dev(axis_n, F64), _dev(axis_e, F64), _dev(grid, F64)
+        torch.cuda.current_stream().synchronize()          # (the uploads' staging copies have been read)
+
+    def _args(self):
+        return _ptr(self.axis_n), self.rows, _ptr(self.axis_e), self.cols, _ptr(self.grid)
+
+
+def terrain_heights(terrain, points):
+    """RegularGridInterpolator(..., bounds_error=False, fill_value=-32768)(points) on the device:
+    points [N, 2] (n, e), numpy or device -> z float64 [N] device (NaN for a NaN coordinate,
+    TERRAIN_FILL outside the axes)."""
+    dev = require_gpu()
+    q = _dev(points, F64).reshape(-1, 2)
+    n = int(q.shape[0])
+    z = torch.empty(n, dtype=F64, device=dev)
+    check(lib().iamx_terrain_heights(*terrain._args(), _ptr(q), n, _ptr(z), stream_ptr()), 'iamx_terrain_heights')
+    if not isinstance(points, torch.Tensor):
+        torch.cuda.current_stream().synchronize()          # (the upload's staging copy has been read)
+    return z
+
+
+def terrain_rays(terrain, M, ned, uv=None, v=None):
+    """lib/srtm.py's interpolate_vector for a batch of images, one thread per ray.  ned [I, 3] and
+    either M [I, 3, 3] with the shared pixel grid uv [n, 2] (rays = unit(M . [u, v, 1]), the arguments
+    of surface_grid) or ready vectors v [I, n, 3] with M None.  -> pts float64 [I, n, 3] NED, iters
+    uint8 [I, n], flags uint8 [I, n] (TERRAIN_SKY | TERRAIN_CAPPED | TERRAIN_LEFT_GRID)."""
+    dev = require_gpu()
+    if (M is None) == (v is None) or (M is None) != (uv is None):
+        raise ValueError("M with uv, or v")
+    nd = _dev(ned, F64).reshape(-1, 3)
+    I = int(nd.shape[0])
+    if v is None:
+        Md = _dev(M, F64).reshape(-1, 9)
+        uvd = _dev(uv, F64).reshape(-1, 2)
+        n = int(uvd.shape[0])
+        if Md.shape[0] != I:
+            raise ValueError("M and ned must have one entry per image")
+    else:
+        vd = _dev(v, F64).reshape(I, -1, 3) if I else _dev(v, F64).reshape(0, 1, 3)
+        n = int(vd.shape[1])
+    if n < 1:
+        raise ValueError("no rays")
+    pts = torch.empty((I, n, 3), dtype=F64, device=dev)
+    iters = torch.empty((I, n), dtype=U8, device=dev)
+    flags = torch.empty((I, n), dtype=U8, device=dev)
+    if v is None:
+        check(lib().iamx_terrain_rays(*terrain._args(), _ptr(Md), _ptr(nd), I, _ptr(uvd), n, _ptr(pts),
+                                      _ptr(iters), _ptr(flags), stream_ptr()), 'iamx_terrain_rays')
+    else:
+        check(lib().iamx_terrain_rays_vec(*terrain._args(), _ptr(vd), _ptr(nd), I, n, _ptr(pts),
+                                          _ptr(iters), _ptr(flags), stream_ptr()), 'iamx_terrain_rays_vec')
+    torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
+    return pts, iters, flags
+
+
+# --------------------------------------------------------------------------------------
 # the explorer's colour tables (csrc/image_colour.hip)
 # --------------------------------------------------------------------------------------
 def _frame3(img):

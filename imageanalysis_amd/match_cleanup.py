@@ -565,27 +565,34 @@ def link_matches(proj, matches_direct):
 # --------------------------------------------------------------------------------------
 def _base_elevations(proj):
     """per image: /smart/<name>/tri_surface_m if present, else the SRTM ground under the camera
-    (lib.srtm, only inside the reference environment); never above 1 m below the camera."""
+    (_deps.srtm(): lib.srtm inside the reference environment, else its mirror, which looks all those
+    cameras up in one launch); never above 1 m below the camera."""
     smart = _deps.smart()
     if smart is not None:
         smart.load(proj.analysis_dir)
         smart_node = smart.smart_node
     else:
         smart_node = _deps.getNode("/smart", True)
-    srtm = None
     base = np.zeros(len(proj.image_list))
-    for i, image in enumerate(proj.image_list):
-        image_node = smart_node.getChild(image.name, True)
-        ned, _ypr, _quat = image.get_camera_pose()
-        if image_node.hasChild("tri_surface_m"):
-            b = image_node.getFloat("tri_surface_m")
+    neds = [image.get_camera_pose()[0] for image in proj.image_list]
+    nodes = [smart_node.getChild(image.name, True) for image in proj.image_list]
+    need = [i for i, node in enumerate(nodes) if not node.hasChild("tri_surface_m")]
+    ground = {}
+    if need:
+        srtm = _deps.srtm()
+        if srtm.ned_interp is None:
+            raise RuntimeError("no /smart/%s/tri_surface_m estimate and the terrain was never initialised "
+                               "(srtm.initialize) to look the ground elevation up" % proj.image_list[need[0]].name)
+        if hasattr(srtm, 'heights'):
+            ground = dict(zip(need, srtm.heights([[neds[i][0], neds[i][1]] for i in need]).tolist()))
         else:
-            if srtm is None:
-                srtm = _deps.srtm()
-                if srtm is None:
-                    raise RuntimeError("no /smart/%s/tri_surface_m estimate and no lib.srtm to "
-                                       "look the ground elevation up" % image.name)
-            b = srtm.ned_interp([ned[0], ned[1]])[0]
+            ground = {i: srtm.ned_interp([neds[i][0], neds[i][1]])[0] for i in need}
+    for i, image in enumerate(proj.image_list):
+        ned = neds[i]
+        if i in ground:
+            b = ground[i]
+        else:
+            b = nodes[i].getFloat("tri_surface_m")
         if -ned[2] - 1 < b:
             b = -ned[2] - 1
         image.base_elev = b

@@ -328,13 +328,17 @@ def map_grids(proj, group, raw_points, raw_values, sw=None, ref=None):
     stage['poses'] = clock() - t
 
     if srtm_mode:
-        # SRTM ground interpolator: lib.srtm, as smart.update_srtm_elevations reaches it
+        # SRTM ground interpolator, as smart.update_srtm_elevations reaches it: lib.srtm's terrain is
+        # adopted inside the reference environment, else the mirror builds its own; then every ray of
+        # every image in one launch (csrc/terrain.hip)
+        from . import srtm as terrain
         srtm = _deps.srtm()
-        if srtm is None:
-            raise RuntimeError("use_srtm_surface needs the reference's lib.srtm (not importable here)")
         srtm.initialize(ref, 6000, 6000, 30)
-        pts = np.array([srtm.interpolate_vectors(ned[i].tolist(), unit_rays(M[i], grid))
-                        for i in range(len(images))], np.float64).reshape(len(images), len(grid), 3)
+        if srtm is not terrain:
+            terrain.adopt(srtm.ned_interp)
+        t = clock()
+        pts = terrain.intersect(M, ned, np.array(grid, np.float64).reshape(-1, 2))
+        stage['kernel'] += clock() - t
     else:
         pts = surface_grids(tri, raw_values, M, ned, avg_ground, grid, no_extrapolate=sw['no_extrapolate'],
                             ground_m=sw['force_ground_elevation_m'] if ground else None,

@@ -11,7 +11,11 @@ import os
 
 from props import getNode
 
-from lib import camera, project, smart, srtm
+from lib import camera, project, smart
+try:
+    from lib import srtm
+except ImportError:                     # (pylab / navpy missing: the mirror, tiles from the cache only)
+    from imageanalysis_amd import srtm
 from lib.logger import log
 
 from imageanalysis_amd import matcher

@@ -46,7 +46,10 @@ for group in group_list:
 print()
 
 if args.method == 'srtm':
-    from lib import srtm
+    try:
+        from lib import srtm
+    except ImportError:                 # (pylab / navpy missing: the mirror, tiles from the cache only)
+        from imageanalysis_amd import srtm
     ref_node = getNode('/config/ned_reference', True)
     ref = [ref_node.getFloat('lat_deg'), ref_node.getFloat('lon_deg'), ref_node.getFloat('alt_m')]
     logger().log("NED reference location:", ref)

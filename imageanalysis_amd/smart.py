@@ -25,7 +25,7 @@ deterministic robust fit (least squares, then re-fits on the matches within 200,
 px), so yaw estimates agree with the reference's to the extent the two fits do (both see
 GMS-filtered, cross-checked matches).  Inside the reference environment this module works on the
 reference's own /smart tree (props.getNode) and smart.json goes through props_json, so the rest
-of process.py shares its state; lib.srtm (tile download + interpolation, out of scope here) is
+of process.py shares its state; lib.srtm (or its mirror imageanalysis_amd.srtm outside that tree) is
 used where the reference uses it."""
 import json
 import os
@@ -838,18 +838,22 @@ def get_surface_estimate(i1, i2):
 # ---- what process.py asks of the module around find_matches (smart.py:319-331) ----------------
 def update_srtm_elevations(proj, ned_interp=None):
     """smart.py:319-324 (process.py:220): /smart/<image>/srtm_surface_m = the SRTM ground under
-    every camera, to 0.1 m.  The lookup is lib.srtm's (tile download + interpolation, out of
-    scope here), which process.py:218 initialises itself; `ned_interp` replaces it for callers
-    without the reference tree."""
+    every camera, to 0.1 m.  The terrain is _deps.srtm()'s, which process.py:218 initialises itself:
+    lib.srtm's inside the reference tree, else the mirror's, where all cameras are looked up in one
+    launch; `ned_interp` replaces it."""
+    neds = [image.get_camera_pose()[0] for image in proj.image_list]
     if ned_interp is None:
         srtm = _deps.srtm()
-        if srtm is None:
-            raise RuntimeError("update_srtm_elevations: lib.srtm is not importable (it is the "
-                               "reference's SRTM tile reader); pass ned_interp=")
-        ned_interp = srtm.ned_interp
-    for image in proj.image_list:
-        ned, _ypr, _quat = image.get_camera_pose()
-        surface = np.asarray(ned_interp([ned[0], ned[1]]), float).ravel()[0]
+        if srtm.ned_interp is None:
+            raise RuntimeError("update_srtm_elevations: the terrain was never initialised "
+                               "(srtm.initialize(ref, 6000, 6000, 30), process.py:218)")
+        if hasattr(srtm, 'heights'):
+            surfaces = srtm.heights([[ned[0], ned[1]] for ned in neds]) if neds else []
+        else:
+            ned_interp = srtm.ned_interp
+    if ned_interp is not None:
+        surfaces = [np.asarray(ned_interp([ned[0], ned[1]]), float).ravel()[0] for ned in neds]
+    for image, surface in zip(proj.image_list, surfaces):
         image_node = smart_node.getChild(image.name, True)
         image_node.setFloat("srtm_surface_m", float("%.1f" % surface))
 

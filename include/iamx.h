@@ -753,6 +753,45 @@ int iamx_surface_grid(const void *records, int num_triangles, const double *valu
                       void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Terrain (csrc/terrain.hip) -- the NED elevation grid of scripts/lib/srtm.py:179-254 and its
+ * readers: ned_interp (scipy.interpolate.RegularGridInterpolator, linear, bounds_error=False,
+ * fill_value=-32768) and interpolate_vector (:277-314).  All pointers are DEV, all arithmetic f64.
+ *
+ * The terrain: axis_n [rows], axis_e [cols] strictly ascending (np.linspace: not exactly
+ *   uniform; the interval is found from a uniform guess corrected against the axis), grid
+ *   [rows][cols].  2 <= rows, cols <= IAMX_TERRAIN_MAX_AXIS.
+ *
+ * iamx_terrain_heights: pts [N][2] (n, e) -> z [N].  A NaN coordinate -> NaN; outside
+ *   [axis[0], axis[-1]] on either axis -> -32768; else with a[i] <= x < a[i+1] (last interval
+ *   closed), t = (x - a[i]) / (a[i+1] - a[i]):
+ *   g00 (1-tn)(1-te) + g01 (1-tn) te + g10 tn (1-te) + g11 tn te, multiplied and summed left to right.
+ *
+ * iamx_terrain_rays: one thread per (image, ray).  M [I][9], ned [I][3], uv [n][2]; ray =
+ *   unit(M [u, v, 1]) (render_panda3d.unit_rays).  iamx_terrain_rays_vec takes ready vectors
+ *   v [I][n][3] instead.  Then interpolate_vector as written: v[2] <= 0 -> the camera position
+ *   (IAMX_TERRAIN_SKY); first look-up under the camera, 0.0 where it is NaN or not above -32768;
+ *   while error > 0.01 and count < 25: d = -(ned[2] + ground), p = ned + v (d / v[2]) with
+ *   p[2] = ned[2] + d, look-up at p keeps the previous ground where it is NaN or not above
+ *   -32768, error = |p[2] + ground|.  IAMX_TERRAIN_CAPPED: 25 rounds and the error still above
+ *   0.01; IAMX_TERRAIN_LEFT_GRID: a look-up of the ray was outside the grid.
+ *   pts [I][n][3] f64 NED, iters [I][n] u8, flags [I][n] u8.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_TERRAIN_MAX_AXIS 32768
+#define IAMX_TERRAIN_SKY 1
+#define IAMX_TERRAIN_CAPPED 2
+#define IAMX_TERRAIN_LEFT_GRID 4
+int iamx_terrain_heights(const double *axis_n, int rows, const double *axis_e, int cols,
+                         const double *grid, const double *pts, int64_t num_points, double *z,
+                         void *stream);
+int iamx_terrain_rays(const double *axis_n, int rows, const double *axis_e, int cols,
+                      const double *grid, const double *M, const double *ned, int num_images,
+                      const double *uv, int num_rays, double *pts, uint8_t *iters, uint8_t *flags,
+                      void *stream);
+int iamx_terrain_rays_vec(const double *axis_n, int rows, const double *axis_e, int cols,
+                          const double *grid, const double *v, const double *ned, int num_images,
+                          int num_rays, double *pts, uint8_t *iters, uint8_t *flags, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * K1: SIFT detect + describe -- replaces cv2.SIFT_create().detectAndCompute(scaled, None)
  *   scripts/lib/image.py:235-237,324 (OpenCV defaults: 3 layers/octave, sigma 1.6, image
  *   doubled, contrastThreshold 0.04, edgeThreshold 10, no feature cap).
