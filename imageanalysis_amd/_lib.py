@@ -226,6 +226,10 @@ SIGNATURES = {
     'iamx_verify_pairs_essential': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int,
                                             ctypes.c_uint64] + [c_void_p] * 6),
     'iamx_five_point': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'iamx_ratio_bins': (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p, c_double, c_int64]
+                        + [c_void_p] * 7),
+    'iamx_ratio_select': (c_int, [c_void_p] * 3 + [c_int, c_int, c_double, c_int] + [c_void_p] * 6
+                          + [c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64] + [c_void_p] * 4),
 }
 
 

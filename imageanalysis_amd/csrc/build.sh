@@ -8,7 +8,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 OUT="$HERE/../libiamx.so"
 OBJDIR="$HERE/obj"
-SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/ba_robust.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip $HERE/ortho_raster.hip $HERE/match_verify.hip $HERE/terrain.hip"
+SRCS="$HERE/common.hip $HERE/match_knn2.hip $HERE/match_knn2v2.hip $HERE/match_knn2sym.hip $HERE/match_post.hip $HERE/host_cleanup.hip $HERE/triangulate.hip $HERE/ba_kernels.hip $HERE/ba_linalg.hip $HERE/ba_schur.hip $HERE/ba_robust.hip $HERE/trf_vec.hip $HERE/comm.hip $HERE/sift.hip $HERE/image_prep.hip $HERE/image_area.hip $HERE/image_colour.hip $HERE/jpeg.hip $HERE/jpeg_entropy.hip $HERE/cache_codec.hip $HERE/surface_grid.hip $HERE/chain_geom.hip $HERE/ortho_raster.hip $HERE/match_verify.hip $HERE/terrain.hip $HERE/match_ratio.hip"
 mkdir -p "$OBJDIR"
 OBJS=""
 for f in $SRCS; do
@@ -35,6 +35,8 @@ for f in $SRCS; do
         [ "$(basename $f)" = "match_verify.hip" ] && EXTRA="-ffp-contract=off"
         # the terrain look-up and the ray iteration restate scipy's / lib/srtm.py's double expressions, operation by operation
         [ "$(basename $f)" = "terrain.hip" ] && EXTRA="-ffp-contract=off"
+        # the ratio bins restate Python's double division and comparisons, operation by operation
+        [ "$(basename $f)" = "match_ratio.hip" ] && EXTRA="-ffp-contract=off"
         # the one-wave-per-SIMD sweep (form 2) needs its MFMA
         # accumulators in VGPRs (the allocator's default for > 256 registers is the AGPR half,
         # at a v_accvgpr_read per element the VALU touches)

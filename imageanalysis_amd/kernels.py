@@ -682,6 +682,136 @@ def five_point(rays):
 
 
 # --------------------------------------------------------------------------------------
+# the 'bestratio' strategy (csrc/match_ratio.hip): ratio bins -> RANSAC homography per bin -> select
+# --------------------------------------------------------------------------------------
+RATIO_CUTOFFS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85)       # matcher.py:622
+RATIO_MIN_UNIQUE = 20                                              # matcher.py:603
+RATIO_BATCH_BYTES = 4 << 30
+
+
+class RatioResult(object):
+    """what ratio_pairs() returns, device tensors over its n pairs: rows int32 [total, 2] (query
+    row, train row) packed back to back, off int64 [n + 1], cnt int32 [n], chosen int32 [n] (-1:
+    no bin taken), stats int32 [n, n_bins, 3] = members, fit, unique (-1 where a bin is not looked
+    at), flag int32 [2] (rows with a zero second distance, pairs refused).  slots int32 [n, stride,
+    2]: the same lists in fixed slots (iamx_similarity_pairs' layout) when the call was one launch,
+    else None."""
+    __slots__ = ('rows', 'off', 'cnt', 'chosen', 'stats', 'flag', 'slots', 'stride')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _ratio_tab_size(stride):
+    t = 64
+    while t < 2 * stride:
+        t *= 2
+    return t
+
+
+def ratio_bytes(nq, n_bins=len(RATIO_CUTOFFS)):
+    """device bytes one launch of ratio_pairs() over query images of `nq` rows (an array) takes:
+    the top-2 rows (16 B), the materialised bins (n_bins x 25 B), the packed result (8 B) per query
+    row, and per pair the select stage's slices at the launch's stride (work lists 24 B, result
+    slot 8 B per row of the largest query image, two key tables of tab_size x 4 B)"""
+    nq = np.asarray(nq, np.int64).reshape(-1)
+    if not len(nq):
+        return 0
+    stride = max(int(nq.max()), 1)
+    return int(nq.sum()) * (24 + 25 * n_bins) + len(nq) * (32 * stride + 8 * _ratio_tab_size(stride) + 64 * n_bins)
+
+
+def _ratio_launch(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed, cut, flag):
+    """one launch chain over pairs whose images all have at least 2 rows"""
+    dev = require_gpu()
+    L = lib()
+    nb, P = len(cut), len(pairs)
+    idx, d2, out_off = knn2_pairs(store, pairs)
+    total = int(out_off[-1])
+    nq = np.diff(out_off)
+    stride = max(int(nq.max()), 1)
+    tab = _ratio_tab_size(stride)
+    cap = nb * total
+    d_pairs = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev)
+    row_off = torch.from_numpy(out_off).to(dev)
+    z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
+    bin_cnt, seg_cnt = z32(P, nb), z32(P, nb)
+    seg_off = torch.zeros(P * nb + 1, dtype=I64, device=dev)
+    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
+    check(L.iamx_ratio_bins(_ptr(idx), _ptr(d2), _ptr(row_off), _ptr(d_pairs), _ptr(kp_off), _ptr(xy),
+                            P, nb, _lib.c_void_p(cut.ctypes.data), float(min_pairs), cap,
+                            _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts), _ptr(rows),
+                            _ptr(flag), stream_ptr()), 'iamx_ratio_bins')
+    # bin b's consensus is iamx_verify_pairs on that bin's points as one segment
+    mask, _model, _best, vstatus = verify_pairs(pts[:cap], seg_off, 'homography',
+                                                float(tol), hypotheses=hypotheses, seed=seed)
+    work = torch.empty(P * (6 * stride + 2 * tab), dtype=I32, device=dev)
+    slots = torch.empty((P, stride, 2), dtype=I32, device=dev)
+    cnt, chosen, stats = z32(P), z32(P), z32(P, nb, 3)
+    off = torch.zeros(P + 1, dtype=I64, device=dev)
+    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
+    check(L.iamx_ratio_select(_ptr(d_pairs), _ptr(kp_off), _ptr(key2), P, nb, float(min_pairs),
+                              RATIO_MIN_UNIQUE, _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(rows),
+                              _ptr(mask), _ptr(vstatus), cap, stride, tab, _ptr(work), _ptr(slots),
+                              _ptr(cnt), _ptr(off), _ptr(out_rows), total, _ptr(chosen), _ptr(stats),
+                              _ptr(flag), stream_ptr()), 'iamx_ratio_select')
+    return RatioResult(rows=out_rows, off=off, cnt=cnt, chosen=chosen, stats=stats, flag=flag,
+                       slots=slots, stride=stride)
+
+
+def ratio_pairs(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed,
+                cutoffs=RATIO_CUTOFFS, batch_bytes=RATIO_BATCH_BYTES):
+    """scripts/lib/matcher.py:595-694 ratio_pair_matches() for a batch of ordered (query image, train
+    image) pairs of `store`: exact k=2 neighbours (knn2_pairs), Lowe-ratio bins, a RANSAC homography
+    per bin at `tol` pixels (verify_pairs' rule with `hypotheses` and `seed`), the bin with the most
+    unique inliers, the min_pairs gates.  kp_off / xy / key2: the keypoint arena of the store's
+    slots (DeviceMatcher.keypoints()).  A pair with an image of at most 1 row ends with nothing
+    (raw_matches' guards).  The work is enqueued on the current stream in launches of at most
+    batch_bytes of device memory each (ratio_bytes); -> RatioResult."""
+    dev = require_gpu()
+    cut = np.ascontiguousarray(cutoffs, np.float64).reshape(-1)
+    nb = len(cut)
+    if not 1 <= nb <= 8:
+        raise ValueError("ratio_pairs: 1 to 8 cutoffs")
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    P = len(pairs)
+    counts = np.asarray(store.counts, np.int64)
+    nq = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
+    ok = (nq >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
+    live = np.nonzero(ok)[0]
+    # launches of at most batch_bytes (a launch's stride is its largest query image)
+    chunks, a = [], 0
+    while a < len(live):
+        b = a + 1
+        while b < len(live) and ratio_bytes(nq[live[a:b + 1]], nb) <= batch_bytes:
+            b += 1
+        chunks.append(live[a:b])
+        a = b
+    flag = torch.zeros(2, dtype=I32, device=dev)            # (the launches only ever raise it)
+    parts = [_ratio_launch(store, pairs[c], kp_off, xy, key2, tol, min_pairs, hypotheses, seed, cut, flag)
+             for c in chunks]
+    if len(parts) == 1 and len(live) == P:
+        return parts[0]
+    # the launches' results side by side (copies and one scan, no arithmetic of their own)
+    cnt = torch.zeros(P, dtype=I32, device=dev)
+    chosen = torch.full((P,), -1, dtype=I32, device=dev)
+    stats = torch.full((P, nb, 3), -1, dtype=I32, device=dev)
+    stats[:, :, 0] = 0
+    rows = []
+    for c, r in zip(chunks, parts):
+        where = torch.from_numpy(c).to(dev)
+        cnt[where], chosen[where], stats[where] = r.cnt, r.chosen, r.stats
+        rows.append(r.rows[:int(r.off[-1])])
+    off = exclusive_scan(cnt) if P else torch.zeros(1, dtype=I64, device=dev)
+    rows = torch.cat(rows) if rows else torch.empty((0, 2), dtype=I32, device=dev)
+    one = len(parts) == 1
+    return RatioResult(rows=rows, off=off, cnt=cnt, chosen=chosen, stats=stats, flag=flag,
+                       slots=None, stride=parts[0].stride if one else None)
+
+
+# --------------------------------------------------------------------------------------
 # a reusable, allocation-free batch of ordered pairs: knn2 -> metric -> scan -> compaction
 # --------------------------------------------------------------------------------------
 class PairWorkspace(object):

@@ -5,6 +5,7 @@ Same module-level entry points, arguments and on-disk results:
     find_matches(proj, K, strategy, transform, sort, review)   :852-1031
     saveMatches(image_list, check_if_dirty=False)         :1033-1040
     raw_matches / basic_pair_matches / bidirectional_pair_matches   :203-347
+    ratio_pair_matches(i1, i2, review, est_rotation)      :595-694
     filter_duplicates / filter_cross_check                :157-200
 so scripts/process.py:290-292 runs unchanged.
 
@@ -16,8 +17,15 @@ device.  The python below keeps the reference's ordering rules (stable metric so
 2000, GMS, first-come de-duplication, cross check) so the match lists are identical to the
 reference run on an exact matcher.
 
-Only the 'traditional' strategy (the default of process.py / 3a-matching.py) and SIFT
-descriptors (integer valued 0..255) are on this path.
+Two strategies are on this path, for SIFT descriptors (integer valued 0..255):
+  'traditional'  (the default of process.py / 3a-matching.py) as above;
+  'bestratio'    one direction: the k=2 neighbours in eight nested Lowe-ratio bins, a RANSAC
+                 homography per bin at half a percent of the image diagonal, the bin with the most
+                 unique inliers (csrc/match_ratio.hip).  The Python-level rules -- guards, ratio,
+                 bins, the strict `>` from 20, filter_duplicates, the min_pairs gates -- are pinned
+                 to the reference's own function; the consensus is this package's rule
+                 (iamx_verify_pairs, RATIO_HYPOTHESES hypotheses, seed 0), parity with cv2 UNPINNED.
+'smart' and 'bruteforce' (k = 3 neighbours, a pose prior) still end in quit().
 """
 import contextlib
 import ctypes
@@ -507,6 +515,150 @@ def bidirectional_pair_matches(i1, i2, review=False):
     else:
         idx_pairs2 = []
     return filter_cross_check(idx_pairs1, idx_pairs2)
+
+
+# --------------------------------------------------------------------------------------
+# the 'bestratio' strategy -- matcher.py:595-694
+# --------------------------------------------------------------------------------------
+RATIO_CUTOFFS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85)       # matcher.py:622
+RATIO_MIN_UNIQUE = 20                                              # matcher.py:603
+RATIO_BATCH_BYTES = 8 << 30     # device memory of one round's bins / consensus / select stage
+ratio_last = None               # the last ratio_pair_matches() call's per-bin figures (the reference prints them)
+
+
+def _ratio_tol():
+    """matcher.py:606-611: half a percent of the image diagonal, at least 5 px"""
+    w, h = _camera_size()
+    diag = int(sqrt(h * h + w * w))
+    tol = int(round(diag * 0.005))
+    return 5 if tol < 5 else tol
+
+
+def _ratio_flags(flag):
+    if int(flag[0]):
+        raise ZeroDivisionError("float division by zero")       # matcher.py:619
+    if int(flag[1]):
+        raise RuntimeError("libiamx: the ratio stage refused %d pairs (an image of more than 2^24 "
+                           "rows, or buffers of the wrong size)" % int(flag[1]))
+
+
+def ratio_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None, seed=0):
+    """matcher.py:595-694 for one ordered pair -> (idx_pairs, rev_pairs).  review / est_rotation are
+    accepted and unused (the reference's review path opens windows).  The RANSAC homography of every
+    bin is this package's rule (iamx_verify_pairs with `hypotheses`, default RATIO_HYPOTHESES, and
+    `seed`), not cv2's."""
+    global ratio_last
+    ratio_last = None
+    if i1.des_list is None or i2.des_list is None:
+        return [], []
+    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
+        return [], []
+    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+        return [], []
+    if the_matcher is None:
+        configure()
+    import torch
+    from . import kernels
+    dev = _lib.require_gpu()
+    xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
+    store = kernels.DescriptorStore.from_arrays([np.ascontiguousarray(i1.des_list),
+                                                 np.ascontiguousarray(i2.des_list)])
+    xy = np.ascontiguousarray(np.concatenate([xy1, xy2]), np.float32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    r = kernels.ratio_pairs(store, [[0, 1]], up(np.array([0, len(xy1)], np.int64)), up(xy),
+                            up(np.concatenate([kp_key2(xy1), kp_key2(xy2)])), _ratio_tol(), min_pairs,
+                            RATIO_HYPOTHESES if hypotheses is None else hypotheses, seed,
+                            cutoffs=RATIO_CUTOFFS)
+    _ratio_flags(r.flag.cpu().numpy())
+    stats, chosen = r.stats.cpu().numpy()[0], int(r.chosen.cpu().numpy()[0])
+    ratio_last = dict(stats=stats, chosen=chosen)
+    _qlog("  raw matches:", len(xy1))
+    for b, (n, fit, unique) in enumerate(stats.tolist()):
+        _qlog("bin:", b, "cutoff:", RATIO_CUTOFFS[b], "len:", n)
+        if fit >= 0:
+            _qlog(" fit:", fit, "unique:", unique)
+    pairs = r.rows[:int(r.off[-1])].cpu().numpy()
+    if not len(pairs):
+        return [], []
+    _qlog("  found matches =", len(pairs))
+    return pairs.tolist(), pairs[:, ::-1].tolist()
+
+
+def _ratio_pairs_per_batch(rows):
+    """ordered pairs per round of the 'bestratio' strategy: as many as RATIO_BATCH_BYTES hold at
+    `rows` descriptors per image (kernels.ratio_bytes), at most PAIRS_PER_BATCH"""
+    from . import kernels
+    per_pair = max(kernels.ratio_bytes([max(int(rows), 1)], len(RATIO_CUTOFFS)), 1)
+    return int(max(1, min(PAIRS_PER_BATCH, RATIO_BATCH_BYTES // per_pair)))
+
+
+def _launch_ratio_batch(view, rows_i, rows_j, surface):
+    """a round of find_matches(strategy='bestratio'): ENQUEUES, on the current stream, the k=2
+    search of the FORWARD pairs only, the ratio stage (kernels.ratio_pairs) and, with `surface`,
+    the similarity fits; the handle goes to _finish_ratio_arrays().  A pair with an image of at most
+    one row never reaches the device (raw_matches' guards)."""
+    import torch
+    from . import kernels
+    from .kernels import _ptr, check, lib, stream_ptr
+    dm = the_matcher
+    n = len(view)
+    live = np.nonzero((np.asarray(rows_i) > 1) & (np.asarray(rows_j) > 1))[0]
+    h = dict(ratio=True, batch=view, n=n, live=live, surface=surface, r=None)
+    if len(live):
+        slot_of = np.zeros(len(view.image_list), np.int32)
+        for u in np.unique(np.concatenate([view.pi[live], view.pj[live]])).tolist():
+            slot_of[u] = dm.slot_of(view.image_list[u])
+        if dm._pending or dm._kp_dev is None or dm._kp_dev[0] != len(dm._counts):
+            # (the arenas are about to be rebuilt: an earlier traditional round's side stream may read them)
+            torch.cuda.current_stream().wait_stream(_side_stream())
+        store = dm.store()
+        kp_off, xy, key2 = dm.keypoints()
+        slots = np.ascontiguousarray(np.stack([slot_of[view.pi[live]], slot_of[view.pj[live]]], 1), np.int32)
+        # (one launch chain: the round was sized by _ratio_pairs_per_batch)
+        r = h['r'] = kernels.ratio_pairs(store, slots, kp_off, xy, key2, _ratio_tol(), min_pairs,
+                                         RATIO_HYPOTHESES, 0, cutoffs=RATIO_CUTOFFS, batch_bytes=1 << 62)
+        if surface:
+            dev = xy.device
+            d_pairs = torch.from_numpy(slots).to(dev)
+            h['aff'] = torch.empty((len(live), 2, 6), dtype=torch.float64, device=dev)
+            h['aff_ok'] = torch.empty((len(live), 2), dtype=torch.int32, device=dev)
+            check(lib().iamx_similarity_pairs(_ptr(d_pairs), _ptr(kp_off), _ptr(xy), _ptr(r.cnt),
+                                              _ptr(r.slots), len(live), r.stride, _ptr(h['aff']),
+                                              _ptr(h['aff_ok']), stream_ptr()), 'iamx_similarity_pairs')
+            h['tables'] = (d_pairs, kp_off, xy, key2)
+    h['done'] = torch.cuda.Event()
+    h['done'].record()
+    return h
+
+
+def _finish_ratio_arrays(h):
+    """-> _RoundResult of a round of the 'bestratio' strategy.  n_fwd: the members of the widest bin
+    (what the reference's log calls the filtered matches), n_rev 0: there is no reverse search; the
+    reverse list is the forward one mirrored, which is _RoundResult's invariant."""
+    h['done'].synchronize()
+    n, live, r, view = h['n'], h['live'], h['r'], h['batch']
+    R = _RoundResult(n)
+    cnt = np.zeros(n, np.int64)
+    R.n_fwd, R.n_rev = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    src = np.zeros((0, 2), np.int32)
+    if r is not None:
+        _ratio_flags(r.flag.cpu().numpy())
+        cnt[live] = r.cnt.cpu().numpy()
+        R.n_fwd[live] = r.stats.cpu().numpy()[:, -1, 0]
+        src = np.ascontiguousarray(r.rows[:int(cnt.sum())].cpu().numpy())
+    R.cc, R.quiet = cnt, cnt == 0
+    hit = np.nonzero(cnt > 0)[0]
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    R.hit_rows, R.lo, R.hi = hit.astype(np.int64), off[hit], off[hit] + cnt[hit]
+    if len(hit):
+        R.fwd_all, R.rev_all = src, np.ascontiguousarray(src[:, ::-1])
+    R.fit = bool(h['surface'])
+    if R.fit:
+        where = np.searchsorted(live, hit)                   # (a pair with matches is a live one)
+        aff = h['aff'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2, 6))
+        aff_ok = h['aff_ok'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2), np.int32)
+        _round_fits(R, view, aff, aff_ok)
+    return R
 
 
 # --------------------------------------------------------------------------------------
@@ -1146,7 +1298,6 @@ def _finish_batch_arrays(h):
         # (a stand-in of _launch_batch / _finish_batch that already returns per-pair tuples:
         #  the CPU tests of the multi-rank logic)
         return _round_from_tuples(h)
-    from . import smart as _smart
     hs, n = h['host'], h['n']
     R = _RoundResult(n)
     keep_host = False
@@ -1180,24 +1331,8 @@ def _finish_batch_arrays(h):
                 #  triangulated heights beside them: the landing buffers stay out of the pool
                 #  until R.done())
                 R.src = dict(kind='pinned', pairs=hs['pk_pairs'], z=hs['pk_z'], total=int(off[n]))
-        aff = hs['aff'].numpy()[dev_rows] if R.fit else None
-        aff_ok = hs['aff_ok'].numpy()[dev_rows] if R.fit else None
-        if R.fit and len(R.hit_rows):
-            ned, air_yaw = _smart.frozen_ned(view.image_list, with_yaw=True)
-            a_idx, b_idx = view.pi[R.hit_rows], view.pj[R.hit_rows]
-            R.dist = np.linalg.norm(ned[b_idx] - ned[a_idx], axis=1)
-            R.same = a_idx == b_idx
-            # the yaw error of both directions of every pair from the similarity fits
-            # (smart.yaw_error_from_affine, vectorised over the round)
-            R.yv_f = np.stack(_smart.yaw_errors_from_affines(ned[a_idx], air_yaw[a_idx], ned[b_idx],
-                                                             aff[:, 0]), 1)
-            R.yv_r = np.stack(_smart.yaw_errors_from_affines(ned[b_idx], air_yaw[b_idx], ned[a_idx],
-                                                             aff[:, 1]), 1)
-            R.aff_ok = aff_ok.astype(bool)
-        elif R.fit:
-            R.dist, R.same = np.zeros(0), np.zeros(0, bool)
-            R.yv_f = R.yv_r = np.zeros((0, 4))
-            R.aff_ok = np.zeros((0, 2), bool)
+        if R.fit:
+            _round_fits(R, view, hs['aff'].numpy()[dev_rows], hs['aff_ok'].numpy()[dev_rows])
         keep_host = R.src is not None
     finally:
         _recycle(h, keep_host)
@@ -1206,6 +1341,27 @@ def _finish_batch_arrays(h):
     if _round_trace is not None:        # (tools/find_matches_rate.py --trace)
         _round_trace.append(('finish', _t1 - _t0, time.perf_counter() - _t1, len(R.hit_rows)))
     return R
+
+
+def _round_fits(R, view, aff, aff_ok):
+    """the fit fields of a round from the similarity fits [h, 2, 6] / [h, 2] of its pairs with matches"""
+    from . import smart as _smart
+    if len(R.hit_rows):
+        ned, air_yaw = _smart.frozen_ned(view.image_list, with_yaw=True)
+        a_idx, b_idx = view.pi[R.hit_rows], view.pj[R.hit_rows]
+        R.dist = np.linalg.norm(ned[b_idx] - ned[a_idx], axis=1)
+        R.same = a_idx == b_idx
+        # the yaw error of both directions of every pair from the similarity fits
+        # (smart.yaw_error_from_affine, vectorised over the round)
+        R.yv_f = np.stack(_smart.yaw_errors_from_affines(ned[a_idx], air_yaw[a_idx], ned[b_idx],
+                                                         aff[:, 0]), 1)
+        R.yv_r = np.stack(_smart.yaw_errors_from_affines(ned[b_idx], air_yaw[b_idx], ned[a_idx],
+                                                         aff[:, 1]), 1)
+        R.aff_ok = aff_ok.astype(bool)
+    else:
+        R.dist, R.same = np.zeros(0), np.zeros(0, bool)
+        R.yv_f = R.yv_r = np.zeros((0, 4))
+        R.aff_ok = np.zeros((0, 2), bool)
 
 
 _round_trace = None
@@ -1326,10 +1482,14 @@ def find_matches(proj, K, strategy="smart", transform="homography", sort=False, 
                 _deps.smart().freeze_poses(False)
 
 
+STRATEGIES = ('traditional', 'bestratio')
+
+
 def _find_matches(proj, K, strategy, transform, sort, review):
-    if strategy != "traditional":
+    if strategy not in STRATEGIES:
         _log("Match strategy", strategy, "is not on the MI355X path; only 'traditional'",
-             "(bidirectional k=2 NN + metric + GMS + cross check) is.")
+             "(bidirectional k=2 NN + metric + GMS + cross check) and 'bestratio' (one direction,",
+             "Lowe-ratio bins + a RANSAC homography per bin) are.")
         quit()
     if the_matcher is None:
         configure()
@@ -1340,7 +1500,7 @@ def _find_matches(proj, K, strategy, transform, sort, review):
         #  feedback changes is the camera ATTITUDE --, and reading one back from the property
         #  tree costs more than a pair's share of the kernels: smart.frozen_ned)
         smart.freeze_poses(True)
-    run = _MatchRun(proj, sort)
+    run = _MatchRun(proj, sort, strategy)
     run.schedule()
     run.prepare()
     run.rounds()
@@ -1531,9 +1691,9 @@ class _MatchRun(object):
     """
     BOOK_CHUNK = 64     # pairs with matches booked per step (~2 ms): see drain()
 
-    def __init__(self, proj, sort):
+    def __init__(self, proj, sort, strategy='traditional'):
         from . import dist as _dist
-        self.proj, self.sort = proj, sort
+        self.proj, self.sort, self.strategy = proj, sort, strategy
         self.image_list = proj.image_list
         self.names = [im.name for im in self.image_list]
         self.rank, self.ws = _dist.world()
@@ -1690,7 +1850,8 @@ class _MatchRun(object):
                     first = image_list[int(wi[rank])]
                     _ensure_features(first)
                     known = [_rows_of(first)]
-                ppb = _pairs_per_batch(1.25 * max(known))
+                ppb = _pairs_per_batch(1.25 * max(known)) if self.strategy == 'traditional' else \
+                    _ratio_pairs_per_batch(max(known))
         except (Exception, SystemExit) as exc:
             if ws == 1:
                 raise
@@ -1702,7 +1863,8 @@ class _MatchRun(object):
         # a survey of many full rounds: the pools its rounds rotate through are filled (and the
         # page-locked buffers touched) on a helper thread while the bookkeeping below runs
         self.warm = None
-        if ws == 1 and self.device and self.failure is None and known and self.n_rounds >= PREWARM_ROUNDS:
+        if ws == 1 and self.device and self.failure is None and known and self.n_rounds >= PREWARM_ROUNDS \
+                and self.strategy == 'traditional':       # (the pools are those of the symmetric sweep's rounds)
             import threading
             import torch as _torch
 
@@ -1785,16 +1947,21 @@ class _MatchRun(object):
                 _ensure_features(im)
             rows[k] = _rows_of(im)
             rows_known[k] = True
-            if rows[k] <= 1:
+            if rows[k] <= 1 and self.strategy == 'traditional':
                 # raw_matches() returns [] and basic_pair_matches divides by len([]) (:232)
                 raise ZeroDivisionError("float division by zero")
-        handle = _launch_batch(view, self.match_ratio, surface='fit' if self.surface else False)
+        if self.strategy == 'bestratio':
+            # (ratio_pair_matches returns [], [] under raw_matches' guards: such a pair ends with nothing)
+            handle = _launch_ratio_batch(view, rows[view.pi], rows[view.pj], bool(self.surface))
+        else:
+            handle = _launch_batch(view, self.match_ratio, surface='fit' if self.surface else False)
         return view, sl, handle
 
     def finish_round(self, launched):
         """-> _Part: the round's pairs of this rank and their results as arrays"""
         view, sl, handle = launched
-        R = _finish_batch_arrays(handle)
+        R = _finish_ratio_arrays(handle) if isinstance(handle, dict) and handle.get('ratio') else \
+            _finish_batch_arrays(handle)
         return _Part(sl, view.pi, view.pj, self.wd[sl], self.rows[view.pi], self.rows[view.pj], R)
 
     def exchange(self, part):
@@ -2211,6 +2378,7 @@ def saveMatches(image_list, check_if_dirty=False):
 # --------------------------------------------------------------------------------------
 VERIFY_BATCH_MATCHES = 1 << 22          # matches per launch of verify_matches (64 MiB of points)
 VERIFY_HYPOTHESES = {'homography': 2048, 'fundamental': 2048, 'essential': 256}
+RATIO_HYPOTHESES = VERIFY_HYPOTHESES['homography']      # the consensus of every bin of 'bestratio'
 _ESSENTIAL_REASON = ("transform 'essential': the five-point solver works on calibrated rays and no "
                      "camera matrix was given.  Pass K, or use 'fundamental' or 'homography'.")
 

@@ -25,6 +25,9 @@ ap.add_argument('project', help='project directory')
 ap.add_argument('--scale', type=float, default=0.4, help='image scale for feature detection')
 ap.add_argument('--detector', default='SIFT', choices=['SIFT'])
 ap.add_argument('--match-ratio', default=0.75, type=float)
+ap.add_argument('--match-strategy', default='traditional', choices=['traditional', 'bestratio'],
+                help="'traditional': both directions, metric + GMS + cross check; 'bestratio': one "
+                     "direction, Lowe-ratio bins with a RANSAC homography per bin")
 ap.add_argument('--min-pairs', default=25, type=int)
 ap.add_argument('--min-dist', default=0, type=float)
 ap.add_argument('--max-dist', default=75, type=float)
@@ -68,7 +71,7 @@ proj.save_images_info()
 
 K = camera.get_K()
 matcher.configure()
-matcher.find_matches(proj, K, strategy='traditional', transform=args.filter, sort=True,
+matcher.find_matches(proj, K, strategy=args.match_strategy, transform=args.filter, sort=True,
                      review=False)
 
 n = sum(image.num_features for image in proj.image_list)

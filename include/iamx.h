@@ -1451,6 +1451,57 @@ int iamx_five_point(const double *rays, /* DEV [n][5][4] x1 y1 x2 y2, normalised
                     int32_t *count,     /* DEV [n] */
                     void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * The 'bestratio' strategy -- scripts/lib/matcher.py:595-694 ratio_pair_matches(): ONE direction
+ * of every pair, Lowe-ratio bins, a RANSAC homography per bin, the bin with the most unique inliers.
+ * Three launches: iamx_ratio_bins, iamx_verify_pairs(model = homography) over the n_pairs * n_bins
+ * segments it leaves, iamx_ratio_select.  The Python-level rules are the reference's; the consensus
+ * is iamx_verify_pairs' rule (parity with cv2 UNPINNED).
+ *
+ * iamx_ratio_bins, one workgroup per ordered pair over its top-2 rows (iamx_knn2_l2_pairs):
+ *   idx / d2  DEV [total rows][2]; row_off DEV [n_pairs + 1] int64 first row of every pair;
+ *   pairs DEV [n_pairs][2] image slots (query, train); kp_off / xy as for iamx_match_postfilter;
+ *   cutoffs HOST [n_bins] doubles, ascending, 1 <= n_bins <= 8.
+ *   ratio = (double)d0 / (double)d1 with d* = float32(sqrt(d2*)); bin b holds the rows with
+ *   ratio <= cutoffs[b] in query-row order; a row with d1 == 0 is in no bin and adds 1 to flag[0]
+ *   (python divides by it: the caller raises ZeroDivisionError).
+ *   bin_cnt DEV [n_pairs][n_bins] members of every bin.  seg_cnt DEV [n_pairs][n_bins]: the same
+ *   where the bin is looked at -- at least min_pairs members (matcher.py:634) and at least 4 (a
+ *   homography's sample), and not as many as the last bin that was looked at (nested bins: the
+ *   same set, the same consensus, which cannot win under `>`) -- else 0.  seg_off DEV
+ *   [n_pairs * n_bins + 1] int64: exclusive scan of seg_cnt = the m_off of iamx_verify_pairs.
+ *   pts DEV [cap][4] x1 y1 x2 y2 = kp.pt of both ends (16-byte aligned), rows DEV [cap][2]
+ *   (query row, train row); cap >= n_bins * total rows.  flag DEV [2] is only ever raised:
+ *   [0] rows with d1 == 0, [1] pairs refused (more than 2^24 rows, or a size the caller got wrong).
+ *
+ * iamx_ratio_select, one workgroup per pair, over mask / status of iamx_verify_pairs:
+ *   per bin in order: the inliers in order (none where status != IAMX_VERIFY_OK), their number
+ *   `fit`, and `unique` = what filter_duplicates (matcher.py:157-182: first come wins on key2 of
+ *   either end, a dropped entry reserves no key) leaves of them; the bin is taken where unique is
+ *   strictly more than the best so far (min_unique = 20 at the start).  The result is the taken
+ *   bin's de-duplicated list if its fit and its unique are both >= min_pairs, else empty.
+ *   stats DEV [n_pairs][n_bins][3] = members, fit, unique (-1, -1 where the bin is not looked at; a
+ *   bin that repeats the one before carries that one's figures); chosen DEV [n_pairs] (-1: none);
+ *   out_slots DEV [n_pairs][stride][2] and out_cnt DEV [n_pairs]: the lists in fixed slots (what
+ *   iamx_similarity_pairs reads with clip = stride); out_off DEV [n_pairs + 1] int64 and out_rows
+ *   DEV [out_cap][2]: the same lists packed back to back (out_cap >= total rows).
+ *   There is no clip here: stride >= the rows of the largest query image of the launch, tab_size a
+ *   power of two >= max(64, 2 * stride), work DEV [n_pairs][6 * stride + 2 * tab_size] int32.
+ * Null pointers, negative counts and n_bins outside 1..8: IAMX_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------ */
+int iamx_ratio_bins(const int32_t *idx, const int32_t *d2, const int64_t *row_off,
+                    const int32_t *pairs, const int64_t *kp_off, const float *xy, int n_pairs,
+                    int n_bins, const double *cutoffs, double min_pairs, int64_t cap,
+                    int32_t *bin_cnt, int32_t *seg_cnt, int64_t *seg_off, float *pts, int32_t *rows,
+                    int32_t *flag, void *stream);
+int iamx_ratio_select(const int32_t *pairs, const int64_t *kp_off, const int32_t *key2, int n_pairs,
+                      int n_bins, double min_pairs, int min_unique, const int32_t *bin_cnt,
+                      const int32_t *seg_cnt, const int64_t *seg_off, const int32_t *rows,
+                      const uint8_t *mask, const int32_t *vstatus, int64_t cap, int stride,
+                      int tab_size, int32_t *work, int32_t *out_slots, int32_t *out_cnt,
+                      int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *chosen,
+                      int32_t *stats, int32_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
