@@ -8,233 +8,72 @@ the one libiamx.so binds to -- one runtime per process, device pointers intercha
 import contextlib
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('IAMX_LIB') or os.path.join(_HERE, 'libiamx.so')   # IAMX_LIB: A/B builds
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'iamx.h')   # where csrc/iamx_common.h includes it from
 _lib = None
 
-c_void_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_int64 = ctypes.c_int64
-c_double = ctypes.c_double
-
-# name -> (restype, argtypes); mirrors include/iamx.h one to one
-SIGNATURES = {
-    'iamx_version': (c_int, []),
-    'iamx_last_error': (ctypes.c_char_p, []),
-    'iamx_arch': (ctypes.c_char_p, []),
-    'iamx_desc_padded_rows': (c_int64, [c_int64]),
-    'iamx_desc_pack_u8': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_desc_pack_f32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_desc_unpack_u8': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'iamx_knn2_wg_per_pair': (c_int, [c_int]),
-    'iamx_knn2_l2_pairs': (c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'iamx_knn2_l2_u8': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                c_void_p, c_void_p, c_void_p]),
-    'iamx_match_metric': (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p]),
-    'iamx_match_compact': (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 4),
-    'iamx_desc2_rows_cap': (c_int64, [c_int64]),
-    'iamx_desc2_pack_u8': (c_int, [c_void_p, c_int64] + [c_void_p] * 7),
-    'iamx_desc2_pack_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 7),
-    'iamx_desc2_pack_batch_u8': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int]
-                                 + [c_void_p] * 7),
-    'iamx_knn2v2_pairs': (c_int, [c_void_p] * 11 + [c_int, c_int, c_int, c_int] + [c_void_p] * 3),
-    'iamx_knn2v2_resolve': (c_int, [c_void_p] * 13 + [c_int, c_void_p, c_void_p]),
-    'iamx_knn2v2_finish': (c_int, [c_void_p] * 10 + [c_double] + [c_void_p] * 5 + [c_int]
-                           + [c_void_p] * 3),
-    'iamx_desc3_rows_cap': (c_int64, [c_int64]),
-    'iamx_knn2sym_rows_per_wg': (c_int, [c_int]),
-    'iamx_knn2sym_kernel_id': (ctypes.c_char_p, [c_int]),
-    'iamx_desc3_pack_u8': (c_int, [c_void_p, c_int64] + [c_void_p] * 7),
-    'iamx_desc3_pack_f32': (c_int, [c_void_p, c_int64] + [c_void_p] * 7),
-    'iamx_desc3_pack_batch_u8': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int]
-                                 + [c_void_p] * 7),
-    'iamx_knn2sym_narrow_bytes': (c_int64, [c_int64, c_int]),
-    'iamx_knn2sym_sweep': (c_int, [c_void_p] * 9 + [c_int, c_int, c_int] + [c_void_p] * 4),
-    'iamx_knn2sym_sweep_items': (c_int, [c_void_p] * 9 + [c_int, c_int] + [c_void_p] * 4),
-    'iamx_knn2sym_candidates': (c_int, [c_void_p] * 12 + [c_int, c_double] + [c_void_p] * 8
-                                + [c_int64, c_int, c_int, c_void_p]),
-    'iamx_knn2sym_exact': (c_int, [c_void_p] * 4 + [c_int64] + [c_void_p] * 8 + [c_int, c_double]
-                           + [c_void_p] * 13 + [c_int64, c_int, c_void_p]),
-    'iamx_match_postfilter_clip': (c_int, []),
-    'iamx_match_pack_results': (c_int, [c_void_p] * 4 + [c_int, c_int, c_int64] + [c_void_p] * 4),
-    'iamx_match_postfilter': (c_int, [c_void_p] * 9 + [c_int, c_double, c_double, c_double, c_double]
-                              + [c_void_p] * 6),
-    'iamx_thp_pays': (c_int, []),
-    'iamx_link_matches': (c_int64, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                    c_void_p, c_void_p]),
-    'iamx_chain_members_uv': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
-    'iamx_kp_key2': (c_int, [c_void_p, c_int64, c_void_p]),
-    'iamx_kp_dup_remap': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
-    'iamx_match_lists_scan': (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
-    'iamx_link_pair_blocks': (c_int64, [c_void_p] * 3 + [c_int64] + [c_void_p] * 4),
-    'iamx_chains_longest_first': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
-    'iamx_first_occurrence': (c_int, [c_void_p, c_int64, c_void_p]),
-    'iamx_ledger_index': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    'iamx_pairs_fwd_rev': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int]),
-    'iamx_touch_pages': (c_int, [c_void_p, c_int64, c_int]),
-    'iamx_segment_mean_std': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int]),
-    'iamx_hbm_copy16': (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
-    'iamx_yaw_feedback_new': (c_void_p, [c_int, c_void_p]),
-    'iamx_yaw_feedback_free': (None, [c_void_p]),
-    'iamx_yaw_feedback_seed': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_yaw_feedback_feed': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_yaw_feedback_state': (c_int, [c_void_p, c_void_p, c_void_p]),
-    'iamx_group_level': (c_int64, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
-                                   c_int, c_int, c_void_p]),
-    'iamx_triangulate_ground': (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 3 + [c_int64]
-                                + [c_void_p] * 3),
-    'iamx_triangulate_pairs': (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
-    'iamx_triangulate_pairs_xyz': (c_int, [c_void_p] * 7 + [c_int, c_int, c_void_p, c_void_p]),
-    'iamx_triangulate_packed': (c_int, [c_void_p] * 7 + [c_int, c_int64, c_void_p, c_void_p]),
-    'iamx_similarity_pairs': (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'iamx_exclusive_scan_i32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    'iamx_ba_residual': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                 c_int64, c_void_p, c_void_p, c_void_p]),
-    'iamx_ba_residual_prepared': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                          c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_ba_residual_jac': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p]),
-    'iamx_ba_reproj_stats': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
-                                     c_int64] + [c_void_p] * 7),
-    'iamx_ba_mark_outliers': (c_int, [c_void_p, c_int64, c_double, c_int, c_double, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_int64, c_void_p]),
-    'iamx_image_prep_workspace_bytes': (c_int64, [c_int, c_int]),
-    'iamx_image_resized_dims': (c_int, [c_int, c_int, c_double, c_void_p, c_void_p]),
-    'iamx_image_equalize_resize': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, c_double,
-                                           c_void_p, c_int64, c_void_p, c_void_p]),
-    'iamx_image_prep_stage': (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
-    'iamx_image_area_dims': (c_int, [c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
-    'iamx_image_resize_area': (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p,
-                                       c_void_p]),
-    'iamx_colour_histogram': (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    'iamx_colour_accumulate_max_frames': (c_int, []),
-    'iamx_colour_accumulate': (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
-    'iamx_colour_mean': (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    'iamx_colour_moments_workspace_doubles': (c_int, []),
-    'iamx_colour_moments': (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p,
-                                    c_void_p, c_void_p]),
-    'iamx_colour_fit_mask': (c_int, [c_int, c_int, c_double, c_double, c_void_p, ctypes.c_uint64,
-                                     c_void_p, c_void_p]),
-    'iamx_colour_mask_finish': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    'iamx_colour_lut': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_surface_pack': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    'iamx_surface_interp': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
-                                    c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_surface_grid': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 4
-                          + [c_int, c_void_p, c_int, c_int, c_int, c_double, c_int] + [c_void_p] * 5),
-    'iamx_terrain_heights': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p,
-                                     c_void_p]),
-    'iamx_terrain_rays': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                  c_void_p, c_int] + [c_void_p] * 4),
-    'iamx_terrain_rays_vec': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
-                                      c_int] + [c_void_p] * 4),
-    'iamx_jpeg_info': (c_int, [c_void_p, c_int64, c_void_p]),
-    'iamx_jpeg_decode_coefficients': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    'iamx_jpeg_workspace_bytes': (c_int64, [c_void_p]),
-    'iamx_jpeg_reconstruct': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    'iamx_jpeg_entropy_header_bytes': (c_int64, []),
-    'iamx_jpeg_entropy_prepare': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64]),
-    'iamx_jpeg_entropy_workspace_bytes': (c_int64, [c_void_p]),
-    'iamx_jpeg_entropy_decode': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                         c_void_p, c_int64, c_void_p, c_void_p]),
-    'iamx_gzip_f32_from_u8_bound': (c_int64, [c_int64, c_int64]),
-    'iamx_gzip_f32_from_u8': (c_int64, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64]),
-    'iamx_gzip_members_bound': (c_int64, [c_int64, c_int64]),
-    'iamx_gzip_members': (c_int64, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p, c_int64]),
-    'iamx_gzip_records_bound': (c_int64, [c_int64, c_int64]),
-    'iamx_gzip_records': (c_int64, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64]),
-    'iamx_u8_to_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int]),
-    'iamx_f32_to_u8_many': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
-    'iamx_u8_gather_many': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int]),
-    'iamx_feat_records': (c_int, [c_void_p] * 7 + [c_int64, c_void_p]),
-    'iamx_pickle_pair_lists': (c_int64, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
-    'iamx_sift_workspace_bytes': (c_int64, [c_int, c_int]),
-    'iamx_sift_detect': (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float,
-                                 ctypes.c_float, c_void_p, c_int64, c_void_p, c_void_p, c_int,
-                                 c_void_p, c_void_p]),
-    'iamx_sift_pyramid_level': (c_int, [c_int] * 5 + [c_void_p] * 4),
-    'iamx_sift_sort_workspace_bytes': (c_int64, [c_int]),
-    'iamx_sift_sort': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                               c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_ba_jv': (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    'iamx_ba_jtv': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_void_p, c_int, c_void_p,
-                            c_void_p, c_void_p]),
-    'iamx_ba_lsmr_state_size': (c_int, []),
-    'iamx_ba_lsmr_partials_size': (c_int64, [c_int, c_int]),
-    'iamx_ba_lsmr_prepare': (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 3),
-    'iamx_ba_lsmr_iterate': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int] + [c_void_p] * 12
-                             + [c_int, c_void_p]),
-    'iamx_ba_lsmr_phase': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, c_int]
-                           + [c_void_p] * 12 + [c_int, c_int, c_void_p]),
-    'iamx_ba_accumulate': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int] + [c_void_p] * 5),
-    'iamx_ba_block_diag': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
-    'iamx_ba_schur_state_size': (c_int, []),
-    'iamx_ba_schur_prepare': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int] + [c_void_p] * 10),
-    'iamx_ba_schur_factor': (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_double, c_double, c_int]
-                             + [c_void_p] * 8),
-    'iamx_ba_schur_iterate': (c_int, [c_void_p] * 8 + [c_int64, c_int, c_int] + [c_void_p] * 15
-                              + [c_int, c_int, c_int, c_void_p]),
-    'iamx_ba_schur_finish': (c_int, [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_int]
-                             + [c_void_p] * 8),
-    'iamx_ba_robust_cost': (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_void_p]),
-    'iamx_ba_robust_scale': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_double, c_void_p]),
-    'iamx_comm_unique_id': (c_int, [c_void_p]),
-    'iamx_comm_init': (c_int, [c_int, c_int, c_void_p, c_void_p]),
-    'iamx_comm_destroy': (c_int, [c_void_p]),
-    'iamx_comm_allgather': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
-    'iamx_comm_allreduce_f64': (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
-    'iamx_vec_axpby': (c_int, [c_int64, c_double, c_void_p, c_double, c_void_p, c_void_p]),
-    'iamx_vec_mul2': (c_int, [c_int64] + [c_void_p] * 6),
-    'iamx_vec_dot': (c_int, [c_int64] + [c_void_p] * 5),
-    'iamx_vec_lsmr_update': (c_int, [c_int64] + [c_void_p] * 4 + [c_double] * 3 + [c_void_p]),
-    'iamx_vec_lincomb': (c_int, [c_int64, c_double, c_void_p, c_double, c_void_p, c_double, c_void_p,
-                                 c_void_p, c_void_p]),
-    'iamx_vec_mul': (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_vec_gather': (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_vec_sqrt_shift': (c_int, [c_int64, c_void_p, c_double, c_void_p, c_void_p]),
-    'iamx_vec_scratch_doubles': (c_int, []),
-    'iamx_vec_dots': (c_int, [c_int64, c_int] + [c_void_p] * 6),
-    'iamx_vec_absmax_prod': (c_int, [c_int64] + [c_void_p] * 5),
-    'iamx_trf_cl_scaling': (c_int, [c_int64] + [c_void_p] * 7),
-    'iamx_trf_scale': (c_int, [c_int64] + [c_void_p] * 9),
-    'iamx_trf_jac_scale': (c_int, [c_int64, c_void_p, c_void_p, c_int, c_void_p]),
-    'iamx_trf_step_to_bound': (c_int, [c_int64] + [c_void_p] * 7),
-    'iamx_trf_reflect': (c_int, [c_int64] + [c_void_p] * 4 + [c_double] + [c_void_p] * 4),
-    'iamx_trf_count_outside': (c_int, [c_int64] + [c_void_p] * 7),
-    'iamx_trf_strictly_feasible': (c_int, [c_int64] + [c_void_p] * 6),
-    'iamx_trf_active': (c_int, [c_int64] + [c_void_p] * 3 + [c_double] + [c_void_p] * 2),
-    'iamx_trf_feasible_start': (c_int, [c_int64] + [c_void_p] * 3 + [c_double] + [c_void_p] * 2),
-    'iamx_trf_scaled_start': (c_int, [c_int64] + [c_void_p] * 6),
-    'iamx_undistort_points': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    'iamx_chain_triangulate': (c_int, [c_void_p] * 4 + [c_int64, c_int] + [c_void_p] * 3 + [c_int]
-                               + [c_void_p] * 5),
-    'iamx_chain_pair_angles': (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p, c_void_p, c_int,
-                                       c_double] + [c_void_p] * 4),
-    'iamx_ortho_max_steps': (c_int, []),
-    'iamx_ortho_clear': (c_int, [c_int, c_int, c_int] + [c_void_p] * 5),
-    'iamx_ortho_raster_image': (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]
-                                + [c_int] * 7 + [c_void_p] * 5),
-    'iamx_ortho_resolve': (c_int, [c_int, c_int] + [c_void_p] * 4),
-    'iamx_verify_pairs': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int,
-                                  ctypes.c_uint64] + [c_void_p] * 5),
-    'iamx_verify_sample': (c_int, [c_int64, c_int, c_int64, ctypes.c_uint64, c_void_p]),
-    'iamx_verify_pairs_essential': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int,
-                                            ctypes.c_uint64] + [c_void_p] * 6),
-    'iamx_five_point': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    'iamx_ratio_bins': (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p, c_double, c_int64]
-                        + [c_void_p] * 7),
-    'iamx_ratio_select': (c_int, [c_void_p] * 3 + [c_int, c_int, c_double, c_int] + [c_void_p] * 6
-                          + [c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64] + [c_void_p] * 4),
-}
+c_void_p = ctypes.c_void_p      # callers wrap their device pointers in it
 
 
 class IamxError(RuntimeError):
     pass
+
+
+# the whole binding: a parameter with '*' or '[' is a pointer, every other type is one of these
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'int64_t': ctypes.c_int64,
+            'uint64_t': ctypes.c_uint64, 'double': ctypes.c_double, 'float': ctypes.c_float}
+_RETURNS = dict(_SCALARS, **{'const char *': ctypes.c_char_p, 'void *': ctypes.c_void_p, 'void': None})
+
+
+def _argtype(param, proto):
+    if '(' in param or ')' in param:
+        raise IamxError("iamx.h: %s: parameter '%s' (a function pointer?) has no ctypes rule" % (proto, param))
+    if '*' in param or '[' in param:
+        return ctypes.c_void_p
+    words = [w for w in param.split() if w != 'const']
+    if len(words) not in (1, 2) or words[0] not in _SCALARS:       # type, or type and name
+        raise IamxError("iamx.h: %s: parameter '%s' has no ctypes rule" % (proto, param))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every `<return type> iamx_<name>(<parameters>);` of a C header.
+    Strict: a type outside the rules above, an iamx_ name in front of a '(' that is no such prototype
+    and a name declared twice raise IamxError -- nothing is guessed or skipped."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+    text = re.sub(r'extern\s*"C"\s*\{|^[ \t]*\}[ \t]*$', '', text, flags=re.M)
+    table = {}
+    for stmt in text.split(';'):
+        stmt = ' '.join(stmt.split())
+        m = re.fullmatch(r'([\w\s*]+?)\s*\b(iamx_\w+)\s*\((.*)\)', stmt)
+        if not m:
+            if re.search(r'\biamx_\w+\s*\(', stmt):
+                raise IamxError("iamx.h: '%s' names an entry point but is not a prototype" % stmt)
+            continue
+        ret, name, params = re.sub(r'\s*\*\s*', ' *', m.group(1)).strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise IamxError("iamx.h: %s: return type '%s' has no ctypes rule" % (name, ret))
+        if name in table:
+            raise IamxError("iamx.h: %s is declared twice" % name)
+        params = [] if params == 'void' else [p.strip() for p in params.split(',')]
+        table[name] = (_RETURNS[ret], [_argtype(p, name) for p in params])
+    return table
+
+
+def _signatures():
+    if not os.path.isfile(HEADER_PATH):
+        raise IamxError("%s not found: the ctypes bindings are derived from the C header" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes): include/iamx.h, parsed once at import; the header is the only statement of the ABI
+SIGNATURES = _signatures()
 
 
 def lib():

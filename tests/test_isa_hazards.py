@@ -10,16 +10,9 @@ on the ISA the installed hipcc actually emits (cross-compiled to gfx950 assembly
   that opens every asm block and by the order of the instructions inside it.
 
 A compiler upgrade that schedules differently fails here instead of producing wrong matches."""
-import os
 import re
-import subprocess
-import tempfile
 
-import pytest
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'imageanalysis_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+from isa_common import device_assembly
 
 VREG = re.compile(r'\bv(\d+)\b|\bv\[(\d+):(\d+)\]')
 
@@ -64,13 +57,7 @@ def _functions(path):
 
 
 def _assembly(src):
-    if not os.path.exists(HIPCC):
-        pytest.skip('no hipcc')
-    out = os.path.join(tempfile.mkdtemp(prefix='iamx_isa_'), 'k.s')
-    subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-S', '--cuda-device-only',
-                           '-I' + os.path.join(REPO, 'include'), '-I' + CSRC, os.path.join(CSRC, src),
-                           '-o', out], stderr=subprocess.DEVNULL)
-    return _functions(out)
+    return _functions(device_assembly(src))
 
 
 def test_asm_med3_never_is_the_first_reader_of_an_mfma_result():

@@ -15,16 +15,12 @@ overflow  sum over gaps of max(0, 8 + 4 (vector + s_nop) + 4 per v_permlane16_sw
 * no global_load_lds shares a gap with another one.
 
 The loop is a cycle: the gap behind its last MFMA continues in front of its first one."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'imageanalysis_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+from isa_common import device_assembly
+
 KERNELS = {
     'one_pair': '_ZN12_GLOBAL__N_114knn2sym_kernelILi8ELi4ELi0ELi5ELi2ELi0ELb1ELi128ELi1EEEvNS_7SymArgsE',
     'items': '_ZN12_GLOBAL__N_114knn2sym_kernelILi8ELi4ELi1ELi5ELi2ELi0ELb1ELi128ELi1EEEvNS_7SymArgsE',
@@ -33,13 +29,7 @@ KERNELS = {
 
 @pytest.fixture(scope='module')
 def assembly():
-    if not os.path.exists(HIPCC):
-        pytest.skip('no hipcc')
-    out = os.path.join(tempfile.mkdtemp(prefix='iamx_gaps_'), 'k.s')
-    subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-mllvm', '-amdgpu-mfma-vgpr-form',
-                           '-S', '--cuda-device-only', '-I' + os.path.join(REPO, 'include'), '-I' + CSRC,
-                           os.path.join(CSRC, 'match_knn2sym.hip'), '-o', out], stderr=subprocess.DEVNULL)
-    return open(out).read().split('\n')
+    return open(device_assembly('match_knn2sym.hip')).read().split('\n')
 
 
 def _kernel(lines, name):

@@ -9,27 +9,18 @@ with the limits tests/test_sweep_schedule.py sets for the one-pair kernel:
 * the chunk loop has no waterfall loop (a buffer resource or address in vector registers: its
   s_and_saveexec / exec loop would cut the barrier step's gap in two);
 * VGPRs + AGPRs stay within the 512 of one wave per SIMD, with no scratch."""
-import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'imageanalysis_amd', 'csrc')
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+from isa_common import device_assembly
+
 ITEMS2 = '_ZN12_GLOBAL__N_114knn2sym_kernelILi8ELi4ELi1ELi5ELi2ELi0ELb1ELi128ELi1EEEvNS_7SymArgsE'
 
 
 @pytest.fixture(scope='module')
 def items2():
-    if not os.path.exists(HIPCC):
-        pytest.skip('no hipcc')
-    out = os.path.join(tempfile.mkdtemp(prefix='iamx_items_sched_'), 'k.s')
-    subprocess.check_call([HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-mllvm', '-amdgpu-mfma-vgpr-form',
-                           '-S', '--cuda-device-only', '-I' + os.path.join(REPO, 'include'), '-I' + CSRC,
-                           os.path.join(CSRC, 'match_knn2sym.hip'), '-o', out], stderr=subprocess.DEVNULL)
+    out = device_assembly('match_knn2sym.hip')
     lines, cur = [], False
     for line in open(out):
         if line.startswith(ITEMS2 + ':'):
