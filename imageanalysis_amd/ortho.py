@@ -3,12 +3,13 @@ window (every image's surface grid drawn top-down, no depth test, ordered by dis
 centre) written as one georeferenced image, on a machine without a display.
 
     raster_frame(grids, gsd)                       origin, size, snapped vertices (host)
-    compose(grids, uvs, frames, width, height, gsd, mode)     the rasteriser on ready arrays
+    compose(grids, uvs, frames, width, height, gsd, mode, bands=)   the rasteriser on ready arrays
     render(proj, group_list, group_index, gsd, ...)           grids, frames and filters of a project
     save(mosaic, analysis_dir, tile, fmt)          tiles, world files, ortho.json
 
-The rasteriser is csrc/ortho_raster.hip; tests/ortho_restatement.py restates the rules below in
-numpy, operation by operation, and the device result is held to it byte for byte.
+The rasteriser is csrc/ortho_raster.hip; tests/ortho_restatement.py (mode multiband:
+tests/ortho_multiband_restatement.py) restates the rules below in numpy, operation by operation,
+and the device result is held to it byte for byte.
 
 THE RULES
 
@@ -58,10 +59,44 @@ Composition, images in group order:
   feather   d = min(u, width - u, v, height - v) at the interpolated source coordinate,
             w = max(d / (0.5 min(width, height)), 2^-20), colour = sum w sample / sum w in
             float64, accumulated in group order, bgr = floor(colour + 0.5); count as above.
+  multiband Burt-Adelson blending along best's seams (tests/ortho_multiband_restatement.py restates
+            it).  Everything above is reused as it is; what follows is float32, every product and
+            sum rounded on its own, the one division done in float64 and rounded once (that is the
+            correctly rounded float32 quotient, whatever a device does with denormals).
+    bands   B, 1 .. 16 (default 5; anything else is a ValueError before any device call).  Level
+            sizes H_0 = H, H_(l+1) = (H_l + 1) // 2, W likewise; the levels used are
+            L = min(B, 1 + ceil(log2(max(H, W)))): a 1 x 1 mosaic has one.
+    owner   before any frame is needed, mode best's index and count for the whole group (geometry
+            only): byte for byte what mode best produces.
+    layer   of image k, over the mosaic: C_k(p) = the sample above, all three channels, cast to
+            float32, wherever image k COVERS p (not only where it wins), 0 elsewhere and outside the
+            mosaic; A_k(p) = 1 where index(p) == k, else 0.
+    reduce  R, separable, ALONG x FIRST (every row), THEN ALONG y: taps g = (1, 4, 6, 4, 1) / 16 at
+            the source positions 2j - 2 .. 2j + 2, outside the level 0, the five terms summed from
+            the left:  (((g0 x[2j-2] + g1 x[2j-1]) + g2 x[2j]) + g1 x[2j+1]) + g0 x[2j+2].
+    expand  E, to the finer level's size, along x first, then along y; outside is 0:
+            even 2m:     ((X[m-1] + 6 X[m]) + X[m+1]) 0.125        odd 2m+1:   (X[m] + X[m+1]) 0.5
+    pyramids per image:  GC^0 = C_k, GC^(l+1) = R(GC^l);  GA^0 = A_k, GA^(l+1) = R(GA^l);
+            LP^l = GC^l - E(GC^(l+1)) for l < L - 1, LP^(L-1) = GC^(L-1).
+    accumulate, images in group order, stream ordered, no atomics:
+            N^l = N^l + GA^l LP^l per channel,  D^l = D^l + GA^l.
+    resolve Q^l = N^l / D^l where D^l > 0, else 0;  M^(L-1) = Q^(L-1),  M^l = Q^l + E(M^(l+1));
+            bgr = floor(min(max(M^0, 0), 255) + 0.5) where count > 0, else 0.
+            The Mosaic carries bgr, index, count, mode 'multiband' and bands = L.
+    extents the device works, per image, on the region of each level where GA^l or GC^l can be
+            non-zero: the pixel box at level 0, and lo .. hi of level l becomes
+            ceil((lo - 2) / 2) .. floor((hi + 2) / 2), cut to the level, at level l + 1
+            (level_regions()).  Outside it GA^l is 0 and N^l, D^l would receive +-0: no bit changes.
+            The restatement computes every level over the whole mosaic; equality checks the extents.
 Uncovered pixels are 0.
 
 Memory: best holds 8 + 4 + 2 + 3 = 17 bytes per pixel, feather 32 + 2 + 3 = 37; one image is one
-launch that reads and writes only the pixels it covers, plus the frame.
+launch that reads and writes only the pixels it covers, plus the frame.  multiband
+(multiband_bytes()): 16 bytes per accumulator pixel of every level (at most 16 * 4 / 3 per mosaic
+pixel), index 4, count 2, bgr 3; on top the larger of the ownership metric (8 per mosaic pixel,
+freed before the first frame) and the layer pyramid of the image with the largest pixel box (16 per
+pixel of its regions).  The collapse works in place.  An image costs a layer launch, L - 1 reduces
+and L accumulates over its regions; the collapse runs once over every level.
 """
 import ctypes
 import json
@@ -74,10 +109,14 @@ import numpy as np
 from . import _deps
 from ._deps import getNode
 
-MODES = {'best': 0, 'feather': 1}
+# a mode's number in iamx_ortho_clear / iamx_ortho_raster_image; multiband has none: it has entry
+# points of its own (iamx_ortho_mb_*) and is never forwarded to those two
+MODES = {'best': 0, 'feather': 1, 'multiband': None}
 MAX_SIDE = 1 << 20
 SNAP = 256
-BYTES_PER_PIXEL = {'best': 8 + 4 + 2 + 3, 'feather': 32 + 2 + 3}
+# multiband: the pyramid accumulators' upper bound 16 * 4 / 3, index, count, bgr (multiband_bytes() is exact)
+BYTES_PER_PIXEL = {'best': 8 + 4 + 2 + 3, 'feather': 32 + 2 + 3, 'multiband': 22 + 4 + 2 + 3}
+MAX_BANDS = 16
 PREFILTER_BELOW = 0.75         # the frame is shrunk when native / gsd is below this
 WORLD_EXT = {'jpg': 'jgw', 'jpeg': 'jgw', 'png': 'pgw', 'tif': 'tfw', 'tiff': 'tfw', 'bmp': 'bpw'}
 
@@ -101,10 +140,12 @@ class RasterFrame(object):
 
 class Mosaic(object):
     """device bgr uint8 [H,W,3], index int32 [H,W] (None in mode feather), count uint16 [H,W];
-    x0, y1, gsd; mode; names (the group's images, `index` counts into them)"""
-    __slots__ = ('bgr', 'index', 'count', 'x0', 'y1', 'gsd', 'mode', 'names')
+    x0, y1, gsd; mode; names (the group's images, `index` counts into them); bands (multiband: the
+    levels used, L; else None)"""
+    __slots__ = ('bgr', 'index', 'count', 'x0', 'y1', 'gsd', 'mode', 'names', 'bands')
 
     def __init__(self, **kw):
+        self.bands = None
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -187,6 +228,46 @@ def pixel_box(X, Y, verts, W, H):
     return max(c0, 0), max(r0, 0), min(c1, W - 1), min(r1, H - 1)
 
 
+def band_levels(H, W, bands=5):
+    """multiband: [(H_l, W_l)] of the L = min(bands, 1 + ceil(log2(max(H, W)))) levels used"""
+    bands = int(bands)
+    if not 1 <= bands <= MAX_BANDS:
+        raise ValueError("bands must be 1 .. %d (got %d)" % (MAX_BANDS, bands))
+    L = min(bands, 1 + (max(int(H), int(W)) - 1).bit_length())
+    sizes = [(int(H), int(W))]
+    while len(sizes) < L:
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return sizes
+
+
+def level_regions(box, sizes):
+    """multiband: per level the inclusive region (y0, x0, y1, x1) where an image's layer can be
+    non-zero, from its pixel box (c0, r0, c1, r1) of level 0.  Reduced pixel j reads 2j - 2 .. 2j + 2,
+    so lo .. hi becomes ceil((lo - 2) / 2) .. floor((hi + 2) / 2), cut to the level."""
+    c0, r0, c1, r1 = box
+    out = [(r0, c0, r1, c1)]
+    for h, w in sizes[1:]:
+        y0, x0, y1, x1 = out[-1]
+        out.append((max((y0 - 1) // 2, 0), max((x0 - 1) // 2, 0), min((y1 + 2) // 2, h - 1), min((x1 + 2) // 2, w - 1)))
+    return out
+
+
+def _area(region):
+    return (region[2] - region[0] + 1) * (region[3] - region[1] + 1)
+
+
+def multiband_bytes(sizes, boxes):
+    """multiband's device memory: (what stays: 16 B per accumulator pixel of every level, index 4,
+    count 2, bgr 3 per mosaic pixel; the ownership metric, 8 per mosaic pixel, freed before the first
+    frame; the largest image's layer pyramid, 16 B per pixel of its regions).  The peak is the first
+    plus the larger of the other two."""
+    H, W = sizes[0]
+    stay = 16 * sum(h * w for h, w in sizes) + (4 + 2 + 3) * H * W
+    temp = 16 * max([sum(_area(r) for r in level_regions(b, sizes)) for b in boxes if b[2] >= b[0] and b[3] >= b[1]]
+                    or [0])
+    return stay, 8 * H * W, temp
+
+
 def native_gsd(grid, cells, frame_w, frame_h):
     """sqrt(footprint area of the used cells / (frame_w frame_h)): the metres one frame pixel spans"""
     g = np.asarray(grid, np.float64)
@@ -220,12 +301,14 @@ class _Composer(object):
     """the accumulators of one mosaic and the group's tables on the device; add(k, frame) rasterises
     image k (call it in group order), finish() -> Mosaic"""
 
-    def __init__(self, grids, uvs, width, height, gsd, mode, names=None):
+    def __init__(self, grids, uvs, width, height, gsd, mode, names=None, bands=5):
         import torch
         from . import kernels
         from ._lib import check, lib, require_gpu, stream_ptr
         if mode not in MODES:
-            raise ValueError("mode must be 'best' or 'feather'")
+            raise ValueError("mode must be 'best', 'feather' or 'multiband'")
+        if mode == 'multiband':
+            band_levels(1, 1, bands)                       # (a ValueError before any device call)
         g, S = _grids(grids)
         L = lib()
         if S > int(L.iamx_ortho_max_steps()):
@@ -236,6 +319,11 @@ class _Composer(object):
         self.cells, self.verts = used_cells(g)
         dev = self.dev = require_gpu()
         need = rf.W * rf.H * BYTES_PER_PIXEL[mode]
+        if mode == 'multiband':
+            self.sizes = band_levels(rf.H, rf.W, bands)
+            self.boxes = [pixel_box(rf.X[k], rf.Y[k], self.verts[k], rf.W, rf.H) for k in range(len(g))]
+            stay, metric, temp = multiband_bytes(self.sizes, self.boxes)
+            need = stay + max(metric, temp)
         free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
         if need > free:
             raise MemoryError("a %d x %d pixel mosaic (mode %s) needs %.2f GB of accumulators, %.2f GB of device "
@@ -252,20 +340,141 @@ class _Composer(object):
         self.used = kernels._dev(rf.used, kernels.U8)
         torch.cuda.current_stream().synchronize()          # (the uploads' staging copies have been read)
         n = (rf.H, rf.W)
+        self._p = kernels._ptr
+        self._call = (L, check, stream_ptr)
+        self.done = 0
+        if mode == 'multiband':
+            self._init_multiband(torch, temp)
+            return
         self.acc = torch.empty(n if mode == 'best' else n + (4,), dtype=torch.float64, device=dev)
         self.index = torch.empty(n, dtype=torch.int32, device=dev) if mode == 'best' else None
         self.count = torch.empty(n, dtype=torch.uint16, device=dev)
         self.bgr = torch.empty(n + (3,), dtype=torch.uint8, device=dev)
-        self._p = kernels._ptr
-        self._call = (L, check, stream_ptr)
         check(L.iamx_ortho_clear(MODES[mode], rf.H, rf.W, self._p(self.acc), self._p(self.index),
                                  self._p(self.count), self._p(self.bgr), stream_ptr()), 'iamx_ortho_clear')
-        self.done = 0
+
+    # ---- mode multiband ----
+    def _params(self, k):
+        terms = image_terms(self.g[k], self.verts[k])
+        if terms is None:
+            return None
+        rf = self.rf
+        return (ctypes.c_double * 8)(self.width, self.height, rf.x0, rf.y1, rf.gsd, *terms)
+
+    def _init_multiband(self, torch, temp_bytes):
+        """the ownership pass (mode best's index and count, from the geometry alone), then the
+        accumulators of every level, zeroed, and the layer pyramid's buffer"""
+        L, check, stream_ptr = self._call
+        rf, p, dev = self.rf, self._p, self.dev
+        n = (rf.H, rf.W)
+        self.index = torch.empty(n, dtype=torch.int32, device=dev)
+        self.count = torch.empty(n, dtype=torch.uint16, device=dev)
+        self.bgr = torch.empty(n + (3,), dtype=torch.uint8, device=dev)
+        metric = torch.empty(n, dtype=torch.float64, device=dev)
+        check(L.iamx_ortho_clear(MODES['best'], rf.H, rf.W, p(metric), p(self.index), p(self.count), p(self.bgr),
+                                 stream_ptr()), 'iamx_ortho_clear')
+        for k in range(len(self.g)):
+            params = self._params(k)
+            if params is None:
+                continue
+            xy = self.xy[k]
+            check(L.iamx_ortho_mb_owner(rf.S, p(xy[0]), p(xy[1]), p(self.used[k]), params, k, *self.boxes[k],
+                                        rf.H, rf.W, p(metric), p(self.index), p(self.count), stream_ptr()),
+                  'iamx_ortho_mb_owner')
+        del metric                                         # (stream ordered: the allocator hands it on in order)
+        self.bands = len(self.sizes)
+        self.offsets = np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])]).astype(np.int64)
+        self.acc = torch.zeros((int(self.offsets[-1]), 4), dtype=torch.float32, device=dev)
+        self.temp = torch.empty((max(temp_bytes // 16, 1), 4), dtype=torch.float32, device=dev)
+        self.finished = False
+
+    def _level(self, l):
+        return self.acc[int(self.offsets[l]):int(self.offsets[l + 1])]
+
+    def accumulators(self):
+        """multiband, before finish(): per level (N float32 [H_l][W_l][3], D float32 [H_l][W_l]), views"""
+        if self.mode != 'multiband' or self.finished:
+            raise RuntimeError("accumulators(): mode multiband only, and before finish() (the collapse works in place)")
+        out = []
+        for l, (h, w) in enumerate(self.sizes):
+            a = self._level(l).view(h, w, 4)
+            out.append((a[:, :, :3], a[:, :, 3]))
+        return out
+
+    def _mb_plan(self, k):
+        """image k's launch arguments: (params, pixel box, per-level regions, per-level layer buffers);
+        None when it has no used cell or covers no pixel centre"""
+        params = self._params(k)
+        box = self.boxes[k]
+        if params is None or box[2] < box[0] or box[3] < box[1]:
+            return None
+        regions = level_regions(box, self.sizes)
+        at = np.concatenate([[0], np.cumsum([_area(r) for r in regions])])
+        return params, box, regions, [self.temp[int(at[l]):int(at[l + 1])] for l in range(len(regions))]
+
+    def _mb_layer(self, k, frame, plan):
+        """kernel (a): C_k and A_k over the image's pixel box"""
+        L, check, stream_ptr = self._call
+        rf, p = self.rf, self._p
+        params, box, _regions, layers = plan
+        xy = self.xy[k]
+        check(L.iamx_ortho_mb_layer(rf.S, p(xy[0]), p(xy[1]), p(self.uv[0 if self.shared_uv else k]), p(self.used[k]),
+                                    p(frame), int(frame.shape[0]), int(frame.shape[1]), params, int(k), *box,
+                                    rf.H, rf.W, p(self.index), p(layers[0]), stream_ptr()), 'iamx_ortho_mb_layer')
+
+    def _mb_pyramid(self, plan):
+        """kernels (b) and (c): the layer's Gaussian pyramid, then every level into the accumulators"""
+        L, check, stream_ptr = self._call
+        p = self._p
+        _params, _box, regions, layers = plan
+        st = stream_ptr()
+        top = len(regions) - 1
+        for l in range(top):
+            h, w = self.sizes[l]
+            check(L.iamx_ortho_mb_reduce(h, w, p(layers[l]), *regions[l], p(layers[l + 1]), *regions[l + 1], st),
+                  'iamx_ortho_mb_reduce')
+        for l in range(top + 1):
+            h, w = self.sizes[l]
+            coarse, cr = (p(layers[l + 1]), regions[l + 1]) if l < top else (None, (0, 0, 0, 0))
+            check(L.iamx_ortho_mb_accumulate(h, w, p(layers[l]), *regions[l], coarse, *cr, p(self._level(l)), st),
+                  'iamx_ortho_mb_accumulate')
+
+    def _add_multiband(self, k, frame):
+        plan = self._mb_plan(k)
+        if plan is not None:
+            self._mb_layer(k, frame, plan)
+            self._mb_pyramid(plan)
+
+    def _mb_collapse(self):
+        """kernel (d), from the top level down; level 0 ends in bgr"""
+        L, check, stream_ptr = self._call
+        p = self._p
+        top = len(self.sizes) - 1
+        for l in range(top, -1, -1):
+            h, w = self.sizes[l]
+            up = p(self._level(l + 1)) if l < top else None
+            count, bgr = (p(self.count), p(self.bgr)) if l == 0 else (None, None)
+            check(L.iamx_ortho_mb_collapse(h, w, p(self._level(l)), up, count, bgr, stream_ptr()),
+                  'iamx_ortho_mb_collapse')
+
+    def _finish_multiband(self):
+        rf = self.rf
+        if self.finished:
+            raise RuntimeError("finish() was called before: the collapse works in place")
+        self.finished = True
+        self._mb_collapse()
+        self.temp = None
+        return Mosaic(bgr=self.bgr, index=self.index, count=self.count, x0=rf.x0, y1=rf.y1, gsd=rf.gsd,
+                      mode=self.mode, names=self.names, bands=self.bands)
 
     def add(self, k, frame):
         L, check, stream_ptr = self._call
         rf, p = self.rf, self._p
         frame = _check_frame(frame)
+        if self.mode == 'multiband':
+            self._add_multiband(k, frame)
+            self.done += 1
+            return
         terms = image_terms(self.g[k], self.verts[k])
         if terms is None:
             self.done += 1
@@ -283,6 +492,8 @@ class _Composer(object):
     def finish(self):
         L, check, stream_ptr = self._call
         rf, p = self.rf, self._p
+        if self.mode == 'multiband':
+            return self._finish_multiband()
         if self.mode == 'feather':
             check(L.iamx_ortho_resolve(rf.H, rf.W, p(self.acc), p(self.count), p(self.bgr), stream_ptr()),
                   'iamx_ortho_resolve')
@@ -290,11 +501,11 @@ class _Composer(object):
                       mode=self.mode, names=self.names)
 
 
-def compose(grids, uvs, frames, width, height, gsd, mode='best', names=None):
+def compose(grids, uvs, frames, width, height, gsd, mode='best', names=None, bands=5):
     """The rasteriser on ready arrays: grids [N][(S+1)^2][3] ENU, uvs [(S+1)^2][2] (one for the group)
     or [N][(S+1)^2][2], frames: N device uint8 [h,w,3] tensors, width x height: the camera's image
-    size.  -> Mosaic"""
-    comp = _Composer(grids, uvs, width, height, gsd, mode, names)
+    size; bands: mode multiband's pyramid levels, 1 .. 16.  -> Mosaic"""
+    comp = _Composer(grids, uvs, width, height, gsd, mode, names, bands)
     frames = list(frames)
     if len(frames) != len(comp.g):
         raise ValueError("%d frames for %d grids" % (len(frames), len(comp.g)))
@@ -354,18 +565,19 @@ def group_grids(proj, group_list, group_index, matches=None):
 
 
 def render(proj, group_list, group_index, gsd, mode='best', prefilter=True, histogram=False, vignette=False,
-           frames=None, matches=None):
+           frames=None, matches=None, bands=5):
     """The orthomosaic of one group.  The frames are decoded by histogram.frame_pass (in group
     order, on this thread's stream); frames=: ready device tensors, one per image of the group,
     instead.  histogram / vignette: the explorer's colour tables (histogram.load() must have found
-    the project's file; models/vignette-mask.jpg must exist).  -> Mosaic"""
+    the project's file; models/vignette-mask.jpg must exist).  bands: mode multiband's pyramid levels.
+    -> Mosaic"""
     from . import histogram as _histogram
     t0 = time.perf_counter()
     camera = _deps.camera()
     images, grids, uv = group_grids(proj, group_list, group_index, matches)
     width, height = camera.get_image_params()
     names = [im.name for im in images]
-    comp = _Composer(grids, uv, width, height, gsd, mode, names)
+    comp = _Composer(grids, uv, width, height, gsd, mode, names, bands)
     mask = _vignette_mask(proj.analysis_dir) if vignette else None
     state = {'k': 0, 'shrunk': 0}
 
@@ -402,7 +614,7 @@ def world_file_text(gsd, west, north):
 def save(mosaic, analysis_dir, tile=4096, fmt='jpg'):
     """<analysis_dir>/ortho/tile_<row>_<col>.<fmt> through Pillow (jpg: panda3d.encode_jpeg's
     settings), a world file per tile (local ENU metres, the pixel-centre convention) and ortho.json:
-    /config/ned_reference, gsd, bounds, mode, per-tile bounds, the image names.  -> the json's dict"""
+    /config/ned_reference, gsd, bounds, mode (multiband: and bands), per-tile bounds, the image names.  -> the json's dict"""
     from PIL import Image as PILImage
     from . import panda3d
     tile = int(tile)
@@ -441,5 +653,7 @@ def save(mosaic, analysis_dir, tile=4096, fmt='jpg'):
             'width': W, 'height': H, 'tile': tile, 'format': fmt,
             'bounds': {'west': x0, 'east': x0 + W * gsd, 'north': y1, 'south': y1 - H * gsd},
             'tiles': tiles, 'images': list(mosaic.names) if mosaic.names is not None else []}
+    if mosaic.mode == 'multiband':
+        info['bands'] = int(mosaic.bands)
     panda3d._write_atomic(os.path.join(out_dir, 'ortho.json'), json.dumps(info, indent=1).encode())
     return info

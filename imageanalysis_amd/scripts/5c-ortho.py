@@ -18,7 +18,9 @@ ap.add_argument('--group', type=int, default=0, help='group index')
 ap.add_argument('--gsd', type=float, default=0.1, help='metres per pixel')
 ap.add_argument('--mode', choices=sorted(ortho.MODES), default='best',
                 help="best: the explorer's ordering, one image per pixel; feather: blended by distance from the "
-                     "frame's border")
+                     "frame's border; multiband: best's seams blended band by band (Laplacian pyramids), wide for "
+                     "coarse detail and narrow for fine")
+ap.add_argument('--bands', type=int, default=5, help='multiband: pyramid levels, 1 .. 16 (fewer are used on a small mosaic)')
 ap.add_argument('--tile', type=int, default=4096, help='tile side in pixels')
 ap.add_argument('--format', default='jpg', help='tile file format (jpg, png, tif)')
 ap.add_argument('--histogram', action='store_true',
@@ -38,7 +40,7 @@ if args.histogram and not histogram.load(proj.analysis_dir):
                      % proj.analysis_dir)
 
 mosaic = ortho.render(proj, group_list, args.group, args.gsd, mode=args.mode, prefilter=not args.no_prefilter,
-                      histogram=args.histogram, vignette=args.vignette)
+                      histogram=args.histogram, vignette=args.vignette, bands=args.bands)
 h, w = mosaic.shape
 print('Mosaic: %d x %d pixels at %.3f m, %d images, %.1f frames/s' % (w, h, args.gsd, ortho.render_stats['images'],
                                                                      ortho.render_stats['frames_per_s']))

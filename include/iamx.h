@@ -1324,6 +1324,42 @@ int iamx_ortho_raster_image(int mode, int S, const int32_t *X, const int32_t *Y,
 int iamx_ortho_resolve(int H, int W, const double *acc, const uint16_t *count, uint8_t *bgr,
                        void *stream);
 
+/* Mode multiband (Laplacian pyramids, float32; the rules: imageanalysis_amd/ortho.py, restated by
+ * tests/ortho_multiband_restatement.py).  It has entry points of its own: the mode numbers of the
+ * calls above stay 0 and 1.  Level l of an H x W mosaic is h x w with h_0 = H, h_{l+1} =
+ * (h_l + 1) / 2.  A pixel of a level is four floats, 16-byte aligned: a LAYER holds (C_b, C_g, C_r,
+ * A) of one image and lives in a buffer of its REGION only, an inclusive box (y0, x0, y1, x1) of
+ * the level, row-major; outside its region a layer is 0.  An ACCUMULATOR holds (N_b, N_g, N_r, D)
+ * over the whole level.  All pointers DEV unless noted; every check is made on the host first.
+ *
+ * owner:       mode best's count, metric and index from the geometry alone (no frame, no bgr): what
+ *   iamx_ortho_raster_image(0, ...) leaves in acc, index and count, after iamx_ortho_clear(0, ...).
+ * layer:       level 0 of image `image_index` over its pixel box (c0, r0, c1, r1), which is the
+ *   layer's region: C = the sample (float64 cast to float32) where the image covers the pixel,
+ *   A = 1 where index == image_index, 0 elsewhere.  Arguments as iamx_ortho_raster_image's.
+ * reduce:      dst = R(src) over the region (dy0 .. dx1) of the level below the h x w one, src given
+ *   over (sy0 .. sx1): taps (1, 4, 6, 4, 1) / 16 at 2j - 2 .. 2j + 2, along x first, then along y.
+ * accumulate:  over the region (fy0 .. fx1) of the h x w level: LP = C(fine) - E(C(coarse)), or
+ *   LP = C(fine) when coarse is null (the top level); N += A LP, D += A into acc [h][w][4].
+ * collapse:    one level, whole: M = N / D (0 where D == 0) + E(M of the level below, `up`
+ *   [(h+1)/2][(w+1)/2][4], null at the top level).  bgr null: M replaces N in acc.  bgr given
+ *   (level 0): bgr = floor(min(max(M, 0), 255) + 0.5) where count > 0, else 0; acc is left alone.
+ */
+int iamx_ortho_mb_owner(int S, const int32_t *X, const int32_t *Y, const uint8_t *used,
+                        const double *params, int image_index, int c0, int r0, int c1, int r1, int H,
+                        int W, double *metric, int32_t *index, uint16_t *count, void *stream);
+int iamx_ortho_mb_layer(int S, const int32_t *X, const int32_t *Y, const double *uv,
+                        const uint8_t *used, const uint8_t *frame, int h_s, int w_s,
+                        const double *params, int image_index, int c0, int r0, int c1, int r1, int H,
+                        int W, const int32_t *index, float *layer, void *stream);
+int iamx_ortho_mb_reduce(int h, int w, const float *src, int sy0, int sx0, int sy1, int sx1,
+                         float *dst, int dy0, int dx0, int dy1, int dx1, void *stream);
+int iamx_ortho_mb_accumulate(int h, int w, const float *fine, int fy0, int fx0, int fy1, int fx1,
+                             const float *coarse, int cy0, int cx0, int cy1, int cx1, float *acc,
+                             void *stream);
+int iamx_ortho_mb_collapse(int h, int w, float *acc, const float *up, const uint16_t *count,
+                           uint8_t *bgr, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * RANSAC verification of pair matches -- scripts/lib/matcher.py:90-142 filter_by_transform()
  * (cv2.findHomography / cv2.findFundamentalMat with cv2.RANSAC).  Parity with cv2 is UNPINNED:
