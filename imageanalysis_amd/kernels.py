@@ -479,6 +479,51 @@ def knn2_pairs(store, pairs):
     return idx[:total], d2[:total], out_off
 
 
+def knn3_pairs(store, pairs):
+    """Exact 3-NN for a batch of ordered (query image, train image) pairs (csrc/match_knn3.hip): what
+    the 'smart' strategy's per-row walk reads.
+
+    Returns (idx, d2, out_off) as knn2_pairs does, with idx/d2 int32 device tensors [sum n_q, 3]
+    ascending by (squared distance, train row); a train image of exactly 2 rows leaves the third
+    neighbour as idx = -1, d2 = 0x7FFFFFFF."""
+    dev = require_gpu()
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    counts = np.asarray(store.counts, np.int64)
+    P = len(pairs)
+    if P and (pairs.min() < 0 or pairs.max() >= len(counts)):
+        raise ValueError("pair list names an image the store does not hold")
+    nq = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
+    if P and counts[pairs[:, 1]].min() < 2:
+        raise ValueError("train image with fewer than 2 descriptors "
+                         "(the reference returns no matches there, lib/matcher.py:205-210)")
+    out_off = np.zeros(P + 1, np.int64)
+    np.cumsum(nq, out=out_off[1:])
+    wg = np.zeros(P + 1, np.int64)
+    np.cumsum((nq + 255) // 256, out=wg[1:])
+    if wg[-1] >= 2 ** 31:
+        raise ValueError("batch too large: split the pair list")
+    total = int(out_off[-1])
+    idx = torch.empty((max(total, 1), 3), dtype=I32, device=dev)
+    d2 = torch.empty((max(total, 1), 3), dtype=I32, device=dev)
+    if P == 0 or total == 0:
+        return idx[:0], d2[:0], out_off
+    d_pairs = torch.from_numpy(pairs).to(dev)
+    d_wg = torch.from_numpy(wg.astype(np.int32)).to(dev)
+    d_out = torch.from_numpy(out_off[:-1].copy()).to(dev)
+    check(lib().iamx_knn3_l2_pairs(_ptr(store.desc), _ptr(store.norm_q), _ptr(store.norm_t),
+                                   _ptr(store.img_off), _ptr(store.img_n), _ptr(d_pairs),
+                                   _ptr(d_wg), _ptr(d_out), P, int(wg[-1]), _ptr(idx), _ptr(d2),
+                                   stream_ptr()), 'iamx_knn3_l2_pairs')
+    torch.cuda.current_stream().synchronize()      # launch tables are temporaries
+    return idx[:total], d2[:total], out_off
+
+
+def knn3(des_q, des_t):
+    """Single pair convenience (packs both sides): returns device (idx[nq,3], d2[nq,3])."""
+    idx, d2, _off = knn3_pairs(DescriptorStore.from_arrays([des_q, des_t]), [(0, 1)])
+    return idx, d2
+
+
 def knn2(des_q, des_t):
     """Single pair convenience (packs both sides): returns device (idx[nq,2], d2[nq,2])."""
     dev = require_gpu()
@@ -809,6 +854,156 @@ def ratio_pairs(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed
     one = len(parts) == 1
     return RatioResult(rows=rows, off=off, cnt=cnt, chosen=chosen, stats=stats, flag=flag,
                        slots=None, stride=parts[0].stride if one else None)
+
+
+# --------------------------------------------------------------------------------------
+# the 'smart' strategy (csrc/match_knn3.hip, csrc/match_smart.hip): per pass, candidate choice and
+# distance bins -> RANSAC homography per bin -> select + least-squares refit
+# --------------------------------------------------------------------------------------
+SMART_CUTOFFS = (32, 64, 128, 256, 512, 1024, 2048)                # matcher.py:516
+SMART_MIN_UNIQUE = 20                                              # matcher.py:468
+FIT_OK, FIT_TOO_FEW, FIT_DEGENERATE = 0, 1, 2
+
+
+def homography_fit(pts, seg_off, mask=None):
+    """Least-squares homographies x2 ~ H x1 (iamx_homography_fit: cv2's kernel without its LM
+    polish) of segments of correspondences: pts [total, 4] float32 (x1 y1 x2 y2), seg_off [n + 1]
+    int64, mask [total] uint8 or None (only points with a non-zero byte count).  Returns device
+    tensors (H f64 [n, 3, 3] with h22 = 1, NaN where status != FIT_OK; status int32 [n]).  Stream
+    ordered, nothing is synchronised."""
+    dev = require_gpu()
+    pts = _dev(pts, torch.float32).reshape(-1, 4)
+    seg_off = _dev(seg_off, I64).reshape(-1)
+    n, total = seg_off.numel() - 1, pts.shape[0]
+    if n < 0:
+        raise ValueError("homography_fit: seg_off needs n + 1 entries")
+    if mask is not None:
+        mask = _dev(mask, U8).reshape(-1)
+        if mask.numel() != total:
+            raise ValueError("homography_fit: one mask byte per point")
+    H = torch.empty((max(n, 1), 3, 3), dtype=F64, device=dev)
+    status = torch.empty(max(n, 1), dtype=I32, device=dev)
+    if n == 0:
+        return H[:0], status[:0]
+    if total == 0:                              # an empty tensor has no address to pass
+        pts = torch.zeros((1, 4), dtype=torch.float32, device=dev)
+    check(lib().iamx_homography_fit(_ptr(pts), _ptr(seg_off), _ptr(mask), n, total, _ptr(H), _ptr(status),
+                                    stream_ptr()), 'iamx_homography_fit')
+    return H[:n], status[:n]
+
+
+class SmartResult(object):
+    """what smart_pairs() returns over its n pairs: rows int32 [total, 2] (query row, train row)
+    packed back to back, off int64 [n + 1], cnt int32 [n] (device tensors: the lists after the
+    min_pairs gates and filter_duplicates); H f64 [n, 3, 3] the last prediction of every pair (device);
+    passes int [n] (host) the passes every pair went through, the last one without a gain included;
+    stats: one int32 [n, 7, 3] host array per pass = members, fit, unique per bin (-1, -1 where a bin
+    is not looked at; a pair that did not take part in the pass: -2 throughout); taken: one int32 [n]
+    host array per pass, 1 + the last bin that raised the pair's best (0: none); best int32 [n, 2]
+    (host) = unique, fitted of the final lists before the gates; flag int32 [2] (host): rows with a
+    zero nearest distance, pairs refused."""
+    __slots__ = ('rows', 'off', 'cnt', 'H', 'passes', 'stats', 'taken', 'best', 'flag')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def smart_pairs(store, pairs, kp_off, xy, size, key2, H0, tol, min_pairs, match_ratio, hypotheses=2048,
+                seed=0, knn=None, max_passes=None):
+    """scripts/lib/matcher.py:465-593 -- smart_pair_matches() from its k = 3 search on -- for a batch
+    of ordered (query image, train image) pairs of `store`.  kp_off / xy / key2: the keypoint arena
+    of the store's slots (DeviceMatcher.keypoints()), size: kp.size beside xy (DeviceMatcher.sizes());
+    H0 [n, 3, 3] float64: every pair's predicted homography (matcher.smart_prior).  Per pass, for the
+    pairs whose best rose in the pass before (all in the first): iamx_smart_stats -> verify_pairs'
+    consensus at `tol` pixels with `hypotheses` and `seed` over the 7 bins -> iamx_smart_select; one
+    word per pair is read back.  knn: (idx, d2, out_off) of knn3_pairs(store, pairs) when the caller
+    ran the search ahead.  A pair with an image of at most 1 row ends with nothing (raw_matches'
+    guards).  max_passes: stop early (tests).  -> SmartResult."""
+    dev = require_gpu()
+    L = lib()
+    NB = len(SMART_CUTOFFS)
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    P = len(pairs)
+    counts = np.asarray(store.counts, np.int64)
+    H0 = np.ascontiguousarray(np.asarray(H0, np.float64).reshape(-1, 9))
+    if len(H0) != P:
+        raise ValueError("smart_pairs: one predicted homography per pair")
+    nq_all = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
+    ok = (nq_all >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
+    if knn is not None and not ok.all():
+        raise ValueError("smart_pairs: a search handed in covers pairs of images with at least 2 rows only")
+    live = np.nonzero(ok)[0]
+    n = len(live)
+    passes = np.zeros(P, np.int64)
+    res = SmartResult(passes=passes, stats=[], taken=[], flag=np.zeros(2, np.int32),
+                      best=np.tile(np.array([SMART_MIN_UNIQUE, 0], np.int32), (P, 1)))
+    H = torch.from_numpy(H0.copy()).to(dev)
+    cnt_all = torch.zeros(P, dtype=I32, device=dev)
+    if n == 0:
+        res.rows, res.off, res.cnt, res.H = (torch.empty((0, 2), dtype=I32, device=dev),
+                                             torch.zeros(P + 1, dtype=I64, device=dev), cnt_all, H.view(P, 3, 3))
+        return res
+    idx, d2, out_off = knn if knn is not None else knn3_pairs(store, pairs[live])
+    total = int(out_off[-1])
+    nq = np.diff(out_off)
+    stride = max(int(nq.max()), 1)
+    tab = _ratio_tab_size(stride)
+    cap = NB * total
+    z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
+    d_pairs = torch.from_numpy(np.ascontiguousarray(pairs[live])).to(dev)
+    row_off = torch.from_numpy(np.ascontiguousarray(out_off, np.int64)).to(dev)
+    Hl = H[torch.from_numpy(live).to(dev)].contiguous() if n != P else H
+    bin_cnt, seg_cnt = z32(n, NB), z32(n, NB)
+    seg_off = torch.zeros(n * NB + 1, dtype=I64, device=dev)
+    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
+    flag = z32(2)
+    work = torch.empty(n * (6 * stride + 2 * tab), dtype=I32, device=dev)
+    slots = torch.empty((n, stride, 2), dtype=I32, device=dev)
+    best = torch.from_numpy(np.tile(np.array([SMART_MIN_UNIQUE, 0], np.int32), (n, 1))).to(dev)
+    improved, cnt, fit_status = z32(n), z32(n), z32(n)
+    stats = z32(n, NB, 3)
+    off = torch.zeros(n + 1, dtype=I64, device=dev)
+    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
+    active = torch.ones(n, dtype=I32, device=dev)
+    act_h = np.ones(n, bool)
+    while act_h.any() and (max_passes is None or len(res.stats) < max_passes):
+        check(L.iamx_smart_stats(_ptr(idx), _ptr(d2), _ptr(row_off), _ptr(d_pairs), _ptr(kp_off), _ptr(xy),
+                                 _ptr(size), _ptr(Hl), _ptr(active), n, float(match_ratio), float(min_pairs),
+                                 cap, _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts), _ptr(rows),
+                                 _ptr(flag), stream_ptr()), 'iamx_smart_stats')
+        mask, model, _best, vstatus = verify_pairs(pts[:cap], seg_off, 'homography', float(tol),
+                                                   hypotheses=hypotheses, seed=seed)
+        check(L.iamx_smart_select(_ptr(d_pairs), _ptr(kp_off), _ptr(key2), _ptr(active), n, float(min_pairs),
+                                  _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts), _ptr(rows),
+                                  _ptr(mask), _ptr(vstatus), _ptr(model), cap, stride, tab, _ptr(work),
+                                  _ptr(best), _ptr(improved), _ptr(slots), _ptr(cnt), _ptr(off),
+                                  _ptr(out_rows), total, _ptr(stats), _ptr(Hl), _ptr(fit_status), _ptr(flag),
+                                  stream_ptr()), 'iamx_smart_select')
+        taken = improved.cpu().numpy()                      # (the one read of the pass: it synchronises)
+        passes[live[act_h]] += 1
+        st_h = np.full((P, NB, 3), -2, np.int32)
+        st_h[live[act_h]] = stats.cpu().numpy()[act_h]
+        tk_h = np.zeros(P, np.int32)
+        tk_h[live] = taken
+        res.stats.append(st_h)
+        res.taken.append(tk_h)
+        res.flag = flag.cpu().numpy()
+        if res.flag.any():
+            break                                           # (the caller raises: python stops at that row)
+        act_h = taken > 0
+        active.copy_(torch.from_numpy(act_h.astype(np.int32)))
+    res.best[live] = best.cpu().numpy()
+    if n == P:
+        res.rows, res.off, res.cnt, res.H = out_rows, off, cnt, Hl.view(P, 3, 3)
+        return res
+    where = torch.from_numpy(live).to(dev)
+    cnt_all[where] = cnt
+    H[where] = Hl
+    res.rows, res.cnt, res.H = out_rows, cnt_all, H.view(P, 3, 3)
+    res.off = exclusive_scan(cnt_all)
+    return res
 
 
 # --------------------------------------------------------------------------------------

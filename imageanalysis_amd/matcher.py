@@ -25,7 +25,13 @@ Two strategies are on this path, for SIFT descriptors (integer valued 0..255):
                  bins, the strict `>` from 20, filter_duplicates, the min_pairs gates -- are pinned
                  to the reference's own function; the consensus is this package's rule
                  (iamx_verify_pairs, RATIO_HYPOTHESES hypotheses, seed 0), parity with cv2 UNPINNED.
-'smart' and 'bruteforce' (k = 3 neighbours, a pose prior) still end in quit().
+The 'smart' strategy (matcher.py:358-593) has entries of its own, smart_prior / smart_pair_matches /
+smart_matches: a homography predicted from the camera poses, the yaw-error estimates and the ground
+estimate picks among every feature's THREE nearest neighbours (csrc/match_knn3.hip), a RANSAC
+homography per distance bin and a least-squares refit tighten it pass by pass (csrc/match_smart.hip).
+Its pair loop is serial -- every pair's prediction depends on the pairs before it -- so it does not go
+through the batched rounds; find_matches(strategy='smart') itself still ends in quit() and is routed
+to smart_matches in a later change, and 'bruteforce' stays out.
 """
 import contextlib
 import ctypes
@@ -138,6 +144,8 @@ class DeviceMatcher(object):
         self._kp = {}             # slot -> (xy float32 [n,2], key2 int32 [n,2]) host copies
         self._kp_dev = None       # (n_slots, kp_off, xy, key2) device arena of the post filter
         self._adopted = {}        # image name -> n_rows: features that arrived from another rank
+        self._size = {}           # slot -> kp.size float32 [n] host copy (None: the slot came without sizes)
+        self._size_dev = None     # (n_slots, size float32 [total]) device arena beside keypoints()
 
     # cv2-style single pair call (returns numpy (idx[nq,2], dist[nq,2] float32))
     def knnMatch(self, des1, des2, k=2):
@@ -169,7 +177,46 @@ class DeviceMatcher(object):
             xy = _kp_xy(image)
             pre = (xy, kp_key2(xy))
         self._kp[slot] = pre
+        self._size[slot] = image              # (read when sizes() is first asked for: most strategies never do)
         return slot
+
+    def sizes(self):
+        """device arena of kp.size for every slot, float32 [total] at keypoints()' offsets: what the
+        'smart' strategy's size test reads.  Like keypoints() it grows geometrically and only the NEW
+        slots go up (the pair loop registers images as it meets them).  The sizes of a slot are read
+        from its image's kp_list when the arena first reaches it; a slot whose image no longer holds
+        them, or that came without keypoint objects (adopt()), has none: ValueError, nothing changed."""
+        import torch
+        n = len(self._counts)
+        cur = self._size_dev
+        if cur is None or cur[0] != n:
+            n0, rows0 = (cur[0], cur[2]) if cur is not None else (0, 0)
+            parts, missing = [], 0
+            for s in range(n0, n):
+                im, want = self._size.get(s), len(self._kp[s][0])
+                kl = im.kp_list if im is not None else None
+                if kl is not None and len(kl) == want:
+                    parts.append(_kp_size(im))
+                elif want:
+                    missing += 1
+            if missing:
+                raise ValueError("no keypoint sizes for %d image slots (features flushed, or adopted from "
+                                 "another rank)" % missing)
+            new = np.ascontiguousarray(np.concatenate(parts + [np.zeros(0, np.float32)]), np.float32)
+            rows = rows0 + len(new)
+            if cur is None or cur[1].shape[0] < rows:
+                cap = max(rows, 2 * (cur[1].shape[0] if cur is not None else 0), 1 << 16)
+                d_size = torch.empty(cap, dtype=torch.float32, device=_lib.require_gpu())
+                if cur is not None:
+                    d_size[:rows0].copy_(cur[1][:rows0])
+            else:
+                d_size = cur[1]
+            if len(new):
+                d_size[rows0:rows].copy_(torch.from_numpy(new))
+            for s in range(n0, n):
+                self._size.pop(s, None)           # (the image is no longer needed here)
+            self._size_dev = (n, d_size, rows)
+        return self._size_dev[1]
 
     def slot_known(self, image):
         """the image's slot without looking at its features when it is registered already (the
@@ -662,9 +709,231 @@ def _finish_ratio_arrays(h):
 
 
 # --------------------------------------------------------------------------------------
+# the 'smart' strategy -- matcher.py:358-593 and its pair loop :923-1031
+# --------------------------------------------------------------------------------------
+SMART_CUTOFFS = (32, 64, 128, 256, 512, 1024, 2048)                # matcher.py:516
+SMART_MIN_UNIQUE = 20                                              # matcher.py:468
+SMART_GRID_STEPS = 8                                               # matcher.py:366
+smart_last = None               # the last smart_pair_matches() call: dict(stats, taken per pass, passes, H0, H)
+# the two places where the strategy reaches the device, replaceable together by tests without one:
+smart_pair_hook = None          # the device part of smart_pair_matches (see _smart_device_pair)
+smart_prior_fit = None          # the least-squares fit at the end of smart_prior (see _device_prior_fit)
+
+
+def gen_grid(w, h, steps):
+    """matcher.py:349-356 as an array [(steps + 1)^2, 2]"""
+    u, v = np.linspace(0, w, steps + 1), np.linspace(0, h, steps + 1)
+    return np.array([[a, b] for b in v for a in u], np.float64)
+
+
+def _kp_size(image):
+    """[N] float32 array of kp.size"""
+    kl = image.kp_list
+    if isinstance(kl, KeyPointList):
+        return np.ascontiguousarray(kl.size, np.float32)
+    return np.array([kp.size for kp in kl], np.float32).reshape(-1)
+
+
+def _smart_tol():
+    """matcher.py:513-514: half a percent of the image diagonal truncated (no round() here, unlike
+    'bestratio'), at least 5 px"""
+    w, h = _camera_size()
+    tol = int(int(sqrt(h * h + w * w)) * 0.005)
+    return 5 if tol < 5 else tol
+
+
+def _rot_x(deg):
+    """transformations.rotation_matrix(deg * d2r, [1, 0, 0])[:3, :3], term by term"""
+    from math import cos, sin, pi
+    a = deg * (pi / 180.0)
+    c, s = cos(a), sin(a)
+    return np.array([[c + (1.0 - c), 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
+
+
+def smart_prior(i1, i2, est_rotation=False):
+    """matcher.py:360-454 in numpy float64 -> (H0 [3, 3], ground_m, reproj [81, 2]): the 9 x 9 pixel
+    grid of image 2 is cast onto the ground estimate (the forced /config/matcher/ground_m, or
+    smart.get_surface_estimate; lowered to 2 m under the camera when the camera is below it; a ray
+    that does not point down keeps the camera position) and projected into image 1 with its
+    distortion; H0 is the least-squares homography float32(reproj) -> float32(grid)
+    (kernels.homography_fit).  est_rotation: both poses are turned about the optical axis by the
+    images' yaw-error estimates, an image without one inheriting its partner's."""
+    cam, smart = _deps.camera(), _deps.smart()
+    K = np.asarray(cam.get_K(), np.float64)
+    IK = np.linalg.inv(K)
+    dist = np.zeros(5)
+    dc = np.asarray(cam.get_dist_coeffs(), np.float64).ravel()
+    dist[:min(5, dc.size)] = dc[:5]
+    w, h = cam.get_image_params()
+    grid = gen_grid(w, h, SMART_GRID_STEPS)
+    if matcher_node.hasChild("ground_m"):
+        ground_m = matcher_node.getFloat("ground_m")
+        _log("Forced ground:", ground_m)
+    else:
+        ground_m = smart.get_surface_estimate(i1, i2)
+        _log("  Ground estimate: %.1f" % ground_m)
+    e1, e2 = smart.get_yaw_error_estimate(i1), smart.get_yaw_error_estimate(i2)
+    if abs(e1) < 0.0001 and abs(e2) > 0.0001:           # inherit the partner's where none is known yet
+        e1 = e2
+    if abs(e1) > 0.0001 and abs(e2) < 0.0001:
+        e2 = e1
+    body2ned = np.asarray(i2.get_body2ned(), np.float64)
+    if est_rotation:
+        body2ned = body2ned.dot(_rot_x(e2))
+    M = body2ned.dot(np.asarray(i2.get_cam2body(), np.float64)).dot(IK)
+    ned2 = [float(v) for v in i2.get_camera_pose()[0]]
+    if -ned2[2] < ground_m:
+        ground_m = -ned2[2] - 2
+    pts_ned = np.empty((len(grid), 3))
+    for k, (u, v) in enumerate(grid):
+        p = M.dot(np.array([u, v, 1.0]))
+        p = p / sqrt(np.dot(p, p))
+        if p[2] > 0.0:
+            d_proj = -(ned2[2] + ground_m)
+            factor = d_proj / p[2]
+            pts_ned[k] = [ned2[0] + p[0] * factor, ned2[1] + p[1] * factor, ned2[2] + d_proj]
+        else:
+            pts_ned[k] = ned2
+    # lib/image.py:542-553 get_proj(opt=False, yaw_error_est): R = body2cam . ned2body, t = -R . ned
+    b2n1 = np.asarray(i1.get_body2ned(), np.float64)
+    if est_rotation and abs(e1) > 0.001:
+        b2n1 = b2n1.dot(_rot_x(e1))
+    body2cam = np.asarray(i1.get_body2cam(), np.float64) if hasattr(i1, 'get_body2cam') else \
+        np.linalg.inv(np.asarray(i1.get_cam2body(), np.float64))
+    R = body2cam.dot(b2n1.T)
+    t = -R.dot(np.asarray(i1.get_camera_pose()[0], np.float64))
+    with np.errstate(all='ignore'):
+        Xc = pts_ned.dot(R.T) + t
+        x, y = Xc[:, 0] / Xc[:, 2], Xc[:, 1] / Xc[:, 2]
+        k1, k2, p1, p2, k3 = dist
+        r2 = x * x + y * y
+        radial = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+        xd = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        yd = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        reproj = np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], axis=1)
+    fit = smart_prior_fit if smart_prior_fit is not None else _device_prior_fit
+    return fit(np.concatenate([reproj.astype(np.float32), grid.astype(np.float32)], axis=1)), ground_m, reproj
+
+
+def _device_prior_fit(pts):
+    from . import kernels
+    H, status = kernels.homography_fit(pts, np.array([0, len(pts)], np.int64))
+    if int(status.cpu()[0]) != kernels.FIT_OK:
+        raise ValueError("smart_prior: the predicted grid has no homography (status %d)" % int(status.cpu()[0]))
+    return H.cpu().numpy()[0]
+
+
+def _smart_device_pair(i1, i2, H0, tol, match_ratio, hypotheses, seed):
+    """the device part of one pair, on the survey's arenas (the images go up once, however many
+    pairs they take part in): -> (pairs int32 [m, 2], stats per pass, taken per pass, flag [2], H)"""
+    from . import kernels
+    dm = the_matcher
+    slots = [[dm.slot_of(i1), dm.slot_of(i2)]]
+    store = dm.store()
+    kp_off, xy, key2 = dm.keypoints()
+    r = kernels.smart_pairs(store, slots, kp_off, xy, dm.sizes(), key2, [H0], tol, min_pairs, match_ratio,
+                            hypotheses=hypotheses, seed=seed)
+    pairs = r.rows[:int(r.off[-1])].cpu().numpy()
+    return pairs, [s[0] for s in r.stats], [int(t[0]) for t in r.taken], r.flag, r.H.cpu().numpy()[0]
+
+
+def smart_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None, seed=0):
+    """matcher.py:358-593 for one ordered pair -> (idx_pairs, rev_pairs).  review is accepted and
+    unused (the reference's review path opens windows).  The RANSAC homography of every bin is this
+    package's rule (iamx_verify_pairs with `hypotheses`, default RATIO_HYPOTHESES, and `seed`) followed
+    by a least-squares refit of its inliers (iamx_homography_fit), not cv2's."""
+    global smart_last
+    smart_last = None
+    H0, _ground_m, _reproj = smart_prior(i1, i2, est_rotation)
+    match_ratio = matcher_node.getFloat("match_ratio")
+    if i1.des_list is None or i2.des_list is None:
+        return [], []
+    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
+        return [], []
+    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+        return [], []
+    if the_matcher is None:
+        configure()
+    run = smart_pair_hook if smart_pair_hook is not None else _smart_device_pair
+    pairs, stats, taken, flag, H = run(i1, i2, H0, _smart_tol(), match_ratio,
+                                       RATIO_HYPOTHESES if hypotheses is None else hypotheses, seed)
+    _ratio_flags(flag)                                  # (matcher.py:489: 0.0 / 0.0)
+    smart_last = dict(stats=stats, taken=taken, passes=len(stats), H0=H0, H=H)
+    _qlog("  raw matches:", int(i1.des_list.shape[0]))
+    for st, tk in zip(stats, taken):
+        for b, (n, fit, unique) in enumerate(np.asarray(st).tolist()):
+            _qlog("bin:", b, "cutoff:", SMART_CUTOFFS[b], "len:", n)
+            if fit >= 0:
+                _qlog(" fit:", fit, "unique:", unique)
+            if b + 1 == tk:
+                _qlog("Filtered matches:", n, "Fitted matches:", fit, "Unique matches:", unique)
+    pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+    if not len(pairs):
+        return [], []
+    _qlog("  found matches =", len(pairs))
+    return pairs.tolist(), pairs[:, ::-1].tolist()
+
+
+def smart_matches(proj, K, sort=False):
+    """The pair loop of matcher.py:923-1031 for strategy 'smart' (est_rotation = True, as the
+    reference calls it).  Every pair's prediction depends on every earlier pair that shares an image
+    -- through tri_surface_m, the yaw-error averages and the rewritten camera poses --, so the pairs
+    are processed one after another in schedule order; find_matches(strategy='smart') itself still
+    ends in quit() and is routed here in a later change.  One rank only."""
+    import time
+    try:
+        import torch.distributed as td
+        if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+            raise NotImplementedError("smart_matches: the pair loop is serial; run it on one rank")
+    except ImportError:
+        pass
+    if the_matcher is None:
+        configure()
+    smart = _deps.smart()
+    work_list = _work_list(proj, sort)
+    save_time = time.time()
+    _log("Processing worklist matches:")
+    for n_count, (dist, i, j) in enumerate(work_list):
+        i1, i2 = proj.image_list[i], proj.image_list[j]
+        if i2.name in i1.match_list and i1.name in i2.match_list:
+            if len(i1.match_list[i2.name]) == 0:
+                _log("Retrying: ", i1.name, "vs", i2.name, "(no matches found previously)")
+            else:
+                _log("Skipping: ", i1.name, "vs", i2.name, "already done.")
+                continue
+        _qlog("Matching %s vs %s - %.1f%% done: " % (i1.name, i2.name, 100.0 * n_count / float(len(work_list))))
+        _qlog("  separation (approx) = %.0f (m)" % dist)
+        i1.desc_timestamp = i2.desc_timestamp = time.time()
+        _ensure_features(i1)
+        _ensure_features(i2)
+        match_fwd, match_rev = smart_pair_matches(i1, i2, False, True)
+        i1.match_list[i2.name] = match_fwd
+        i2.match_list[i1.name] = match_rev
+        i1.matches_clean = False
+        i2.matches_clean = False
+        avg, std = smart.update_surface_estimate(i1, i2)
+        if avg and std:
+            _qlog(" ", i1.name, i2.name, "surface est: %.1f" % avg, "std: %.1f" % std)
+        i1.set_aircraft_yaw_error_estimate(smart.update_yaw_error_estimate(i1, i2))
+        i2.set_aircraft_yaw_error_estimate(smart.update_yaw_error_estimate(i2, i1))
+        if std and std >= 50 and len(i1.match_list[i2.name]) < 100:
+            _log("Std dev of surface triangulation blew up, matches are probably bad so discarding them!",
+                 i1.name, i2.name, "avg:", avg, "std:", std, "count:", len(match_fwd))
+            i1.match_list[i2.name] = []
+            i2.match_list[i1.name] = []
+        if time.time() >= save_time + SAVE_INTERVAL:
+            saveMatches(proj.image_list, check_if_dirty=True)
+            smart.save(proj.analysis_dir)
+            save_time = time.time()
+    saveMatches(proj.image_list)
+    smart.save(proj.analysis_dir)
+    print('Pair-wise matches successfully saved.')
+
+
+# --------------------------------------------------------------------------------------
 # pair schedule -- matcher.py:852-916
 # --------------------------------------------------------------------------------------
-_WORK_MATRIX_MAX = 4096      # images up to which the schedule is built from the n x n distance matrix (~0.4 GB of temporaries)
+_WORK_MATRIX_MAX = 4096     # images up to which the schedule is built from the n x n distance matrix (~0.4 GB of temporaries)
 
 
 def _work_arrays(proj, sort):

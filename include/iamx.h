@@ -95,6 +95,19 @@ int iamx_knn2_l2_u8(const int8_t *q_desc, const int32_t *q_norm_q, int nq,
                     const int8_t *t_desc, const int32_t *t_norm_t, int nt,
                     int32_t *idx, int32_t *d2, void *stream);
 
+/* K3: the exact 3-nearest-neighbour search of the 'smart' strategy -- replaces
+ *   the_matcher.knnMatch(des1, des2, k=3)           scripts/lib/matcher.py:456-470
+ * Every argument table is that of iamx_knn2_l2_pairs (wg_off from iamx_knn2_wg_per_pair too);
+ *   out_idx / out_d2  DEV [sum n_q][3] int32, ascending by (squared distance, train row): equal
+ *   distances go to the lower train row.  Columns 0-1 are what iamx_knn2_l2_pairs writes.
+ * A train image of fewer than 3 rows leaves the missing neighbours as idx = -1, d2 = 0x7FFFFFFF
+ * (cv2 returns a shorter list there: the reference's `for j in range(len(m))` then sees two). */
+int iamx_knn3_l2_pairs(const int8_t *desc, const int32_t *norm_q, const int32_t *norm_t,
+                       const int32_t *img_off, const int32_t *img_n,
+                       const int32_t *pairs, const int32_t *wg_off, const int64_t *out_off,
+                       int n_pairs, int total_wg,
+                       int32_t *out_idx, int32_t *out_d2, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * Quality metric + threshold -- replaces the python loop scripts/lib/matcher.py:253-263:
  *     ratio = d0/d1 ; metric = d0*ratio ; keep metric < max_distance*match_ratio
@@ -1537,6 +1550,77 @@ int iamx_ratio_select(const int32_t *pairs, const int64_t *kp_off, const int32_t
                       int tab_size, int32_t *work, int32_t *out_slots, int32_t *out_cnt,
                       int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *chosen,
                       int32_t *stats, int32_t *flag, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * The 'smart' strategy -- scripts/lib/matcher.py:358-593 smart_pair_matches(): a homography
+ * predicted from the camera poses picks, among every feature's three nearest neighbours
+ * (iamx_knn3_l2_pairs), the one nearest to the prediction; a RANSAC homography per distance bin
+ * tightens the prediction until no bin gains unique inliers.  One pass of the loop (:474-580) is
+ * iamx_smart_stats, iamx_verify_pairs(model = homography) over the n_pairs * IAMX_SMART_BINS
+ * segments it leaves, iamx_smart_select.  The Python-level rules are the reference's; the consensus is
+ * iamx_verify_pairs' rule and the refit is iamx_homography_fit's (parity with cv2 UNPINNED).
+ *
+ * iamx_homography_fit, one workgroup per segment: the least-squares homography x2 ~ H x1 of the
+ * segment's points -- cv2's kernel (HomographyEstimatorCallback::runKernel) without its LM polish:
+ *   both sides normalised (centroid, mean distance sqrt 2), the 9 x 9 L^T L of the rows
+ *   [X Y 1 0 0 0 -xX -xY -x], [0 0 0 X Y 1 -yX -yY -y] summed in f64 (fixed reduction trees), the
+ *   eigenvector of its least eigenvalue by 12 sweeps of cyclic Jacobi, H = T2^-1 H0 T1 divided by h22.
+ *   pts DEV [total][4] x1 y1 x2 y2 (16-byte aligned); seg_off DEV [n_seg + 1] int64; mask DEV [total]
+ *   or NULL: only points with a non-zero mask byte count.  H DEV [n_seg][9] row major, status DEV
+ *   [n_seg]: IAMX_FIT_TOO_FEW below 4 points, IAMX_FIT_DEGENERATE where a side's points coincide,
+ *   an entry of the result is not finite (a NaN among the points, h22 == 0) or the segment's
+ *   offsets leave [0, total]; H is NaN wherever status != IAMX_FIT_OK.
+ *
+ * iamx_smart_stats, one workgroup per ordered pair over its top-3 rows:
+ *   idx / d2 DEV [total rows][3]; row_off, pairs, kp_off, xy, cap, pts, rows, flag as for
+ *   iamx_ratio_bins; size DEV [total kp] float32 kp.size beside xy; H DEV [n_pairs][9] f64 the pair's
+ *   current prediction; active DEV [n_pairs] int32 or NULL (all): a pair with active == 0 gets
+ *   bin_cnt = seg_cnt = 0 and nothing else.
+ *   Query row i: p1 = pi(H kp.pt) in doubles with the quotient taken by the reciprocal, stored as
+ *   float32, (0, 0) where w == 0 (cv2.perspectiveTransform).  Neighbours j = 0, 1, 2 in order, with
+ *   d* = float32(sqrt(d2*)): stop at d2[j] >= 90000 (distance >= 300; a missing neighbour); ratio =
+ *   (double)d0 / (double)dj, stop at ratio < match_ratio; raw_dist = float32 |kp2.pt - p1| (float32
+ *   differences, squares and sum, then the correctly rounded root); size_diff = the larger of the two
+ *   kp.size over the smaller as doubles, the neighbour is passed over at size_diff > 1.25; metric =
+ *   (double)raw_dist * size_diff / ratio; the first neighbour that gets here is the row's choice, a
+ *   later one replaces it at a strictly smaller metric.  The choice is in bin b where its raw_dist <
+ *   32 << b, in query-row order.  A row with d2[0] == 0 has no choice and adds 1 to flag[0] (python
+ *   divides 0.0 by 0.0: the caller raises ZeroDivisionError).
+ *   bin_cnt / seg_cnt / seg_off as for iamx_ratio_bins with n_bins = IAMX_SMART_BINS.
+ *
+ * iamx_smart_select, one workgroup per pair, over mask / status / model of iamx_verify_pairs:
+ *   the walk of iamx_ratio_select with the pair's running best READ from and written to best DEV
+ *   [n_pairs][2] = (unique, fitted) of the pair's list (the caller starts it at (20, 0)).  A bin with
+ *   strictly more unique inliers than the best so far becomes the pair's list -- out_slots holds its
+ *   de-duplicated inliers, out_cnt their number where fitted and unique are both >= min_pairs (else
+ *   0) -- and improved DEV [n_pairs] is 1 + the last such bin of the walk.  A pair without such a
+ *   bin keeps best, out_slots, out_cnt and H as they are and gets improved = 0; so does a pair with
+ *   active == 0, whose stats stay too.  For a pair that improved, the taken bin's inliers go through
+ *   iamx_homography_fit's kernel: H DEV [n_pairs][9] becomes the fit, or vmodel's model of the bin
+ *   where fit_status DEV [n_pairs] is not IAMX_FIT_OK.  stats, out_off, out_rows, stride, tab_size,
+ *   work as for iamx_ratio_select; out_off / out_rows are packed on every call from out_cnt /
+ *   out_slots.  The loop ends when no pair improves: best strictly rises and cannot pass the rows.
+ * Null pointers, negative counts, a stride or tab_size out of range: IAMX_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_SMART_BINS 7
+#define IAMX_FIT_OK 0
+#define IAMX_FIT_TOO_FEW 1
+#define IAMX_FIT_DEGENERATE 2
+int iamx_homography_fit(const float *pts, const int64_t *seg_off, const uint8_t *mask, int n_seg,
+                        int64_t total, double *H, int32_t *status, void *stream);
+int iamx_smart_stats(const int32_t *idx, const int32_t *d2, const int64_t *row_off,
+                     const int32_t *pairs, const int64_t *kp_off, const float *xy, const float *size,
+                     const double *H, const int32_t *active, int n_pairs, double match_ratio,
+                     double min_pairs, int64_t cap, int32_t *bin_cnt, int32_t *seg_cnt,
+                     int64_t *seg_off, float *pts, int32_t *rows, int32_t *flag, void *stream);
+int iamx_smart_select(const int32_t *pairs, const int64_t *kp_off, const int32_t *key2,
+                      const int32_t *active, int n_pairs, double min_pairs, const int32_t *bin_cnt,
+                      const int32_t *seg_cnt, const int64_t *seg_off, const float *pts,
+                      const int32_t *rows, const uint8_t *mask, const int32_t *vstatus,
+                      const double *vmodel, int64_t cap, int stride, int tab_size, int32_t *work,
+                      int32_t *best, int32_t *improved, int32_t *out_slots, int32_t *out_cnt,
+                      int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *stats, double *H,
+                      int32_t *fit_status, int32_t *flag, void *stream);
 
 #ifdef __cplusplus
 }
