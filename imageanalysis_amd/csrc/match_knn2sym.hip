@@ -1243,6 +1243,440 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
 }
 
 // ---------------------------------------------------------------------------------
+// Form 2's item sweep on v_mfma_i32_16x16x64_i8 (round 17): the same workgroup (four waves, one
+// per SIMD, a 1024-row B slice in the AGPR half, A streamed in 128-row chunks through the same
+// stage and swizzle), the same item walk, merge and outputs, bit for bit -- on the MFMA shape the
+// chip clocks higher (profiles/r17_ubench_mfma_clock.txt).  Two chained MFMAs (K = 2 x 64) make a
+// 16 x 16 tile with Ct as the C operand; 256 MFMAs a chunk and wave.
+//   Lane (n = lane & 15, lg = lane >> 4) holds bytes [64 s + 16 lg, +16) of the 16 CONSECUTIVE
+//   sorted B rows q0 + 16 rn + block, rn = n's bit 3 moved to the bottom: lanes n and n ^ 8 hold
+//   a group of 32 consecutive rows (form 2's groups, so R_w and S_w are form 2's).  An accumulator
+//   is query n against train rows 4 lg + i of the tile.
+//   Row direction: the v_min3 chain over the 16 blocks is lane local (4 registers a tile); a
+//   transposing butterfly over the 16 lanes of a DPP row -- xor 8 (4 -> 2 registers, then the
+//   group floor), xor 4 (2 -> 1), inside the quad -- leaves train row 4 lg + 2 b2 + b3 in quad
+//   (b3, b2).  No lane exchange across DPP rows.
+//   Column direction: running minima per block and (tile32 & 3); train row bit 2 is lg & 1, so
+//   lane groups lg and lg ^ 2 are merged at the pair's end into form 2's eight groups (k, g).
+// The chunk loop is a compiler-scheduled software pipeline: 32 steps of 8 MFMAs (four blocks),
+// step s issues the MFMAs of step s + 1 beside the minima of step s, PIPE valu instructions a gap.
+// ---------------------------------------------------------------------------------
+// (in three pieces, which the chunk loop runs in three steps of the next tile)
+__device__ __forceinline__ void row16_level8(const int (&r)[4], int lo, int (&u)[2])
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {              // lanes xor 8: quads 0,1 keep r[2k], quads 2,3 r[2k+1]
+        const int a = r[2 * k], b = r[2 * k + 1];
+        const int t1 = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);   // row_ror:8
+        const int t2 = __builtin_amdgcn_update_dpp(a, b, 0x128, 0xF, 0xC, false);
+        u[k] = min(t1, t2) + lo;
+    }
+}
+__device__ __forceinline__ int row16_level4(const int (&u)[2])
+{
+    // lanes xor 4: quads 0,2 keep u[0], quads 1,3 u[1]
+    const int t1 = __builtin_amdgcn_update_dpp(u[1], u[0], 0x12C, 0xF, 0x5, false);   // row_ror:12 = lane+4
+    const int t2 = __builtin_amdgcn_update_dpp(u[0], u[1], 0x124, 0xF, 0xA, false);   // row_ror:4  = lane-4
+    return min(t1, t2);
+}
+__device__ __forceinline__ int row16_quad(int w)
+{
+    w = min(w, __builtin_amdgcn_update_dpp(0, w, 0xB1, 0xF, 0xF, true));    // quad_perm:[1,0,3,2]
+    w = min(w, __builtin_amdgcn_update_dpp(0, w, 0x4E, 0xF, 0xF, true));    // quad_perm:[2,3,0,1]
+    return w;
+}
+__device__ __forceinline__ int row16_min4(const int (&r)[4], int lo)
+{
+    int u[2];
+    row16_level8(r, lo, u);
+    return row16_quad(row16_level4(u));
+}
+
+// valu instructions behind MFMA `g` (0..7) of a step of the 16x16x64 chunk loop that has `nv` of them
+constexpr int sweep16_gap_valu(int nv, int g) { return nv / 8 + (g < nv % 8 ? 1 : 0); }
+
+template <int PIPE>
+__global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
+{
+    constexpr int NW = 4, QB = 16, WGROWS = NW * QB * 16, NT = NW * 64;
+    constexpr int PIECES = CHUNK * D / 16 / NT;
+    constexpr int NT16 = CHUNK / 16, SPT = 4, QS = QB / SPT, NS = NT16 * SPT;    // tiles, steps a tile, blocks a step
+    static_assert(WGROWS == 1024 && PIECES == 4 && NS == 32 && D == 128, "form 2's workgroup");
+    // (the LDS layout of knn2sym_kernel: two stages, Ct, three R_w buffers, S_w, the dump area)
+    __shared__ __attribute__((aligned(16))) int8_t lds[2 * CHUNK * D + 2 * CHUNK * 4 + 3 * NW * CHUNK * 4 + 2 * NW * 4 + (2 * NW * CHUNK + NW * 256) * 4];
+    int8_t *lds_tile = lds;
+    int *lds_tb = reinterpret_cast<int *>(lds + 2 * CHUNK * D);      // [2][CHUNK]     Ct
+    int *lds_row = lds_tb + 2 * CHUNK;                               // [3][NW][CHUNK] R_w
+    int *lds_cq = lds_row + 3 * NW * CHUNK;                          // [NW] (2 NW reserved) S_w
+    int *lds_dump = lds_cq + 2 * NW;                                 // [NW][256] (+ 2 buffer strides) unused stores
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 15, lg = lane >> 4;
+    const int rn = ((n & 7) << 1) | (n >> 3);
+
+    int vid;
+    {
+        const int total = A.total_wg, bid = blockIdx.x;
+        const int xcd = bid & 7, k = bid >> 3, q = total >> 3, r = total & 7;
+        vid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
+    }
+    int u = A.wg_off[3 * vid], u_end = u + A.wg_off[3 * vid + 1], item_wgi = A.wg_off[3 * vid + 2];
+    v4i bq[QB][2];
+    int lo_lane;
+    int bimg_held = -1;              // the B image whose slice bq holds
+    asm volatile("" : "+v"(u_end), "+v"(item_wgi), "+v"(bimg_held));
+#if defined(IAMX_T_STAMPS)
+    // (the diagnostic build stamps this kernel's whole chunk loop only: chunks, cycles, 100 MHz ticks)
+    unsigned long long stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0;
+#endif
+    // the table entries of the pair the loop runs next, read one pair ahead (see knn2sym_kernel)
+    int nx_b = A.upairs[2 * u], nx_a = A.upairs[2 * u + 1];
+    int nx_boff = A.img_off[nx_b], nx_nb = A.img_n[nx_b], nx_aoff = A.img_off[nx_a], nx_na = A.img_n[nx_a];
+    int64_t nx_rowp = A.rowp_off[u];
+    for (;;) {
+        const int bimg = uniform32(nx_b);
+        const int boff = uniform32(nx_boff), nb = uniform32(nx_nb);
+        const int aoff = uniform32(nx_aoff), na = uniform32(nx_na);
+        const int capA = (na + CHUNK - 1) / CHUNK * CHUNK;
+        const int nchunks = capA / CHUNK;
+        const int wgi = uniform32(item_wgi);
+        const int q0 = wgi * WGROWS + wave * (QB * 16);
+        const bool wave_valid = q0 < nb;
+        const int64_t rbase = uniform64(nx_rowp) + (int64_t)wgi * capA;
+        // (from the item's second pair on: every wave is past the previous pair's last merge -- its
+        //  lds_row reads -- before an invalid wave refills its rows with BIG below)
+        if (uniform32(bimg_held) >= 0) __syncthreads();
+
+        // B operand: rows past the end repeat the last row; the Cq floor of a lane's group of 32 rows
+        // and the wave's largest spread S_w as in knn2sym_kernel
+        if (bimg != uniform32(bimg_held)) {
+            bimg_held = bimg;
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb) {
+                int row = q0 + QB * rn + qb;
+                row = row < nb ? row : nb - 1;
+                const v4i *src = reinterpret_cast<const v4i *>(A.sdesc + (int64_t)(boff + row) * D);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    bq[qb][s] = ~src[4 * s + lg];
+                    asm volatile("" : "+a"(bq[qb][s]));      // (only ever an MFMA source: the AGPR half)
+                }
+            }
+            lo_lane = 0;
+            {
+                int spread = 0;
+                if (wave_valid) {
+                    const int g_lo = rn & ~1, g_hi = rn | 1;
+                    const int r_lo = q0 + QB * g_lo < nb ? q0 + QB * g_lo : nb - 1;
+                    const int r_hi = q0 + QB * g_hi + QB - 1 < nb ? q0 + QB * g_hi + QB - 1 : nb - 1;
+                    lo_lane = A.sn2[boff + r_lo] >> 1;
+                    spread = (A.sn2[boff + r_hi] >> 1) - lo_lane;
+                }
+#pragma unroll
+                for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
+                if (lane == 0) lds_cq[wave] = spread;
+            }
+        }
+        if (!wave_valid) {
+#pragma unroll
+            for (int k = 0; k < 3 * CHUNK / 64; ++k)
+                lds_row[((k / (CHUNK / 64)) * NW + wave) * CHUNK + (k % (CHUNK / 64)) * 64 + lane] = BIG;
+        }
+        int m[QB][4];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m[qb][k] = BIG;
+
+        const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
+        const int32_t *tci = A.sct + aoff;
+        // global -> LDS directly; the XOR swizzle of the 16-byte slots is applied on the source side
+        typedef __attribute__((address_space(3))) void *lds_ptr;
+        auto stage_direct = [&](int ch, int buf) {
+#pragma unroll
+            for (int j = 0; j < PIECES; ++j) {
+                const int e = j * NT + tid, row = e >> 3, slot = (e & 7) ^ ((row >> 1) & 7);
+                const int8_t *gsrc = tbase + (int64_t)(ch * CHUNK + row) * D + slot * 16;
+                int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
+                __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
+            }
+            __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + (tid & (CHUNK - 1)),
+                                             (lds_ptr)(lds_tb + buf * CHUNK + (wave & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
+        };
+        auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
+        // per train row: the waves' group minima -> (L, U1, U2), stored by waves 0 and 1 through a buffer
+        // resource over this workgroup's partials (an offset past num_records drops the store)
+        const int mrow = (wave & 1) * 64 + lane;
+        const bool merger = wave < 2;
+        constexpr int RSRC_WORD3_DATA_FORMAT_32 = 4 << 15;
+        constexpr int RANGE_DROP = 0x7FFFFFF0;
+        const __amdgpu_buffer_rsrc_t rowp_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(A.rowp + 2 * rbase, (short)0, capA * 8, RSRC_WORD3_DATA_FORMAT_32);
+        int spread_w[NW];
+        auto merge_rows = [&](int ch, int rbo, bool store) {
+            int L = BIG, U1 = BIG, U2 = BIG;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const int R = lds_row[rbo + w * CHUNK + mrow];
+                const int uw = R + spread_w[w];
+                L = min(L, R);
+                U2 = min(max(U1, uw), U2);
+                U1 = min(U1, uw);
+            }
+            __builtin_amdgcn_raw_buffer_store_b64(v2i{L, pack_row_bounds(L, U1, U2)}, rowp_rsrc,
+                                                  store ? (ch * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
+        };
+
+        // after the butterfly quad (b3, b2) = (n >> 3, (n >> 2) & 1) of lane group lg holds train row
+        // 4 lg + 2 b2 + b3 of the tile.  One lane per quad stores it; the others, and a wave past the end of
+        // the B image, store into the dump area (no branch in the tile loop)
+        int *const row_dst = (lane & 3) == 0 && wave_valid
+            ? lds_row + wave * CHUNK + 4 * lg + 2 * ((n >> 2) & 1) + (n >> 3)
+            : lds_dump + wave * 256 + lane;                 // (+ row buffer offset + tile * 16: inside the dump area)
+        v4i aop[2][2], ct[2];
+        v4i accs[2][QS];
+        int r[2][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[1][k] = BIG;
+
+        {                                  // (the last pair of the item reads its own entries again)
+            const int un = u + 1 < u_end ? u + 1 : u;
+            nx_b = A.upairs[2 * un];
+            nx_a = A.upairs[2 * un + 1];
+            nx_rowp = A.rowp_off[un];
+        }
+        stage_direct(0, 0);
+        stage_direct(nchunks > 1 ? 1 : 0, 1);
+        wait_direct();
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < NW; ++w) spread_w[w] = __builtin_amdgcn_readfirstlane(lds_cq[w]);
+        {
+            const int b = uniform32(nx_b), a = uniform32(nx_a);
+            nx_boff = A.img_off[b];
+            nx_nb = A.img_n[b];
+            nx_aoff = A.img_off[a];
+            nx_na = A.img_n[a];
+        }
+        // a lane's LDS offsets in the stage buffer the operand reads go to, switched by one xor each where
+        // the reads move on to the next chunk's buffer; the tile rides in the instruction's offset.  Row
+        // 16 T + n sits at slot (4 s + lg) ^ ((n >> 1) & 7): the 16 lanes of a group read 16 different
+        // 16-byte slots of a 256-byte line pair (rows n, n ^ 1 share a slot index, 128 bytes apart)
+        typedef __attribute__((address_space(3))) const int8_t *lds_bytes;
+        int opoff[2], tboff = 2 * CHUNK * D + 16 * lg;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) opoff[s] = n * D + (((4 * s + lg) ^ ((n >> 1) & 7)) * 16);
+        auto load_ops = [&](int tile, v4i (&a)[2], v4i &c) {
+            c = *reinterpret_cast<const __attribute__((address_space(3))) v4i *>((lds_bytes)lds + tboff + tile * 64);
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                a[s] = *reinterpret_cast<const __attribute__((address_space(3))) v4i *>((lds_bytes)lds + opoff[s] + tile * (16 * D));
+        };
+        // the MFMAs of a step: blocks qp .. qp + 3 of tile parity tp, the four chains interleaved
+        auto issue = [&](auto tp_c, auto qp_c, v4i (&acc)[QS]) {
+            constexpr int tp = decltype(tp_c)::value, qp = decltype(qp_c)::value;
+#pragma unroll
+            for (int j = 0; j < QS; ++j) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aop[tp][0], bq[qp + j][0], ct[tp], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < QS; ++j) acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aop[tp][1], bq[qp + j][1], acc[j], 0, 0, 0);
+        };
+        load_ops(0, aop[0], ct[0]);
+        load_ops(1, aop[1], ct[1]);
+        issue(int_c<0>{}, int_c<0>{}, accs[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
+        // (meaningless) last tile into the buffer chunk 2 overwrites
+        int rbo = 0, rbo_prev = 2 * NW * CHUNK;
+        // (the stage inside the chunk loop, as in form 2's: one lane offset for every piece and chunk beside a
+        //  scalar base, the wave's LDS destination from a scalar register, one held piece a step)
+        const int wave_u = uniform32(wave);
+        const unsigned stage_voff = (unsigned)((tid >> 3) * D + (((tid & 7) ^ ((tid >> 4) & 7)) * 16));
+        const unsigned lds_tile_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tile + wave_u * (64 * 16));
+        const unsigned lds_tb_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tb + (wave_u & (CHUNK / 64 - 1)) * 64);
+        const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
+        int bu[2] = {BIG, BIG}, bw = BIG;
+#if defined(IAMX_T_STAMPS)
+        const unsigned long long loop_c0 = __builtin_amdgcn_s_memtime(), loop_r0 = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0) alone
+#endif
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const int buf = ch & 1;
+            // the barrier step: every read of this chunk's stage has been issued (tile NT16 - 1's in the step
+            // in front of it), the next chunk's stage has landed; the stage of chunk + 2 follows it, one piece
+            // a step held between two column minima, and the merge of the previous chunk in three steps
+            constexpr int BAR = (NT16 - 2) * SPT;
+            static_assert(BAR + PIECES < NS, "the stage's five pieces fit behind the barrier");
+            const int chs = ch + 2 < nchunks ? ch + 2 : nchunks - 1;
+            const int8_t *const sg_tile = tbase + (int64_t)chs * (CHUNK * D);
+            const int8_t *const sg_ct = reinterpret_cast<const int8_t *>(tci + chs * CHUNK);
+            int mR[NW], mL = BIG, mU1 = BIG, mU2 = BIG;
+            static_for<0, NS>([&](auto st_c) {
+                constexpr int st = decltype(st_c)::value;
+                constexpr int t = st / SPT, ph = st % SPT, qp = QS * ph, cur = st & 1, kk = (t >> 1) & 3;
+                constexpr int nst = st + 1 < NS ? st + 1 : 0;
+                constexpr bool staging = st >= BAR && st <= BAR + PIECES;
+                if constexpr (st == BAR) {
+                    __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
+                    __syncthreads();
+                }
+                issue(int_c<(nst / SPT) & 1>{}, int_c<QS * (nst % SPT)>{}, accs[cur ^ 1]);
+                // minima of this step, oldest accumulator first: the column minima of its four blocks (two a
+                // block), then the row chain
+#pragma unroll
+                for (int j = 0; j < QS; ++j) {
+                    const v4i &a = accs[cur][j];
+                    int &mm = m[qp + j][kk];
+                    mm = min(min(mm, a[0]), a[1]);
+                    if constexpr (staging) {
+                        if (j == 1) {
+                            if constexpr (st < BAR + PIECES)
+                                stage_piece_held<16>(sg_tile + (st - BAR) * ((NT / 8) * D) + stage_voff,
+                                                     lds_tile_at + buf * (CHUNK * D) + (st - BAR) * NT * 16, mm);
+                            else
+                                stage_piece_held<4>(sg_ct + ct_voff, lds_tb_at + buf * (CHUNK * 4), mm);
+                        }
+                    }
+                    mm = min(min(mm, a[2]), a[3]);
+                }
+                const v4i a0 = accs[cur][0], a1 = accs[cur][1], a2 = accs[cur][2], a3 = accs[cur][3];
+                int (&rc_)[4] = r[t & 1];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    rc_[i] = ph == 0 ? min(min(min(a0[i], a1[i]), a2[i]), a3[i])
+                                     : min(min(min(min(rc_[i], a0[i]), a1[i]), a2[i]), a3[i]);
+                // the previous tile's row butterfly (tile NT16 - 1 of the previous chunk for t = 0), a level a step
+                if constexpr (ph == 1) row16_level8(r[(t + 1) & 1], lo_lane, bu);
+                if constexpr (ph == 2) bw = row16_level4(bu);
+                if constexpr (ph == 3) row_dst[(t > 0 ? rbo : rbo_prev) + (t > 0 ? t - 1 : NT16 - 1) * 16] = row16_quad(bw);
+                // the operand reads of tile t + 2 (flattened across chunks), behind the last MFMAs of tile t;
+                // from tile NT16 on they read the next chunk's stage
+                if constexpr (ph == SPT - 1) {
+                    if constexpr (t + 2 == NT16) {
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) opoff[s] ^= CHUNK * D;
+                        tboff ^= CHUNK * 4;
+                    }
+                    load_ops((t + 2) % NT16, aop[t & 1], ct[t & 1]);
+                }
+                // the merge of the previous chunk (its rows' last minima were stored in this chunk's first tile)
+                if constexpr (st == BAR + 1) {
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) mR[w] = lds_row[rbo_prev + w * CHUNK + mrow];
+                }
+                if constexpr (st == BAR + 2) {
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        const int uw = mR[w] + spread_w[w];
+                        mL = min(mL, mR[w]);
+                        mU2 = min(max(mU1, uw), mU2);
+                        mU1 = min(mU1, uw);
+                    }
+                }
+                if constexpr (st == BAR + 3)
+                    __builtin_amdgcn_raw_buffer_store_b64(v2i{mL, pack_row_bounds(mL, mU1, mU2)}, rowp_rsrc,
+                                                          merger && ch > 0 ? ((ch - 1) * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
+                // 16 minima a step, the butterfly's piece, the chunk's own work: spread evenly over the eight gaps
+                constexpr int nv = 16 + (ph == 1 ? 8 : ph == 2 ? 3 : ph == 3 ? 2 : 0) + (staging ? 2 : 0) +
+                                   (st == BAR + 2 ? 11 : 0) + (st == BAR + 3 ? 5 : 0) + (st == NS - 1 ? 2 : 0) + (PIPE - 2);
+                static_for<0, 8>([&](auto g_c) {
+                    constexpr int g = decltype(g_c)::value;
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x002, sweep16_gap_valu(nv, g) + (g == 7 ? 3 : 0), 0);
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            rbo_prev = rbo;
+            rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
+        }
+        (void)bu;
+#if defined(IAMX_T_STAMPS)
+        {
+            unsigned long long loop_c1;
+            SWEEP_STAMP(loop_c1);
+            stamp_cycles += loop_c1 - loop_c0;
+            stamp_ticks += __builtin_amdgcn_s_memrealtime() - loop_r0;
+            stamp_chunks += (unsigned)nchunks;
+            if (A.stamps && lane == 0) {
+                unsigned long long *o = A.stamps + ((size_t)blockIdx.x * NW + wave) * 4;
+                o[0] = 0;
+                o[1] = stamp_chunks;
+                o[2] = stamp_cycles;
+                o[3] = stamp_ticks;
+            }
+        }
+#endif
+        // this pair's first column-result row (it lands with the vmcnt(0) below)
+        const int64_t col_v = A.col_off[u];
+        // the last chunk's last tile, its merge
+        row_dst[rbo_prev + (NT16 - 1) * 16] = row16_min4(r[(NT16 - 1) & 1], lo_lane);
+        wait_direct();
+        __syncthreads();
+        merge_rows(nchunks - 1, rbo_prev, merger);
+
+        const int64_t col_u = uniform64(col_v);
+        // ---- column results: lane groups lg and lg ^ 2 hold the same group g = lg & 1 of train rows; merged,
+        // a lane has form 2's 4 x 2 group minima of its 16 queries: the two smallest, and the groups whose
+        // minimum is <= the second smallest (bit k + 4 g), 4 bits a query
+        if (wave_valid) {
+            unsigned ownpack[2] = {0, 0};
+            int v1s[QB], v2s[QB];
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb) {
+                int mk[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) mk[k] = min(m[qb][k], __shfl_xor(m[qb][k], 32));
+                const int lo01 = min(mk[0], mk[1]), hi01 = max(mk[0], mk[1]);
+                const int lo23 = min(mk[2], mk[3]), hi23 = max(mk[2], mk[3]);
+                const int a1 = min(lo01, lo23), a2 = min(max(lo01, lo23), min(hi01, hi23));
+                const int b1 = __shfl_xor(a1, 16), b2 = __shfl_xor(a2, 16);
+                const int v1 = min(a1, b1), v2 = min(max(a1, b1), min(a2, b2));
+                v1s[qb] = v1;
+                v2s[qb] = v2;
+                const unsigned own = (mk[0] <= v2 ? 1u : 0u) | (mk[1] <= v2 ? 2u : 0u) |
+                                     (mk[2] <= v2 ? 4u : 0u) | (mk[3] <= v2 ? 8u : 0u);
+                ownpack[qb >> 3] |= own << (4 * (qb & 7));
+            }
+            unsigned othpack[2] = {0, 0};
+            if (A.colmask) {
+                othpack[0] = (unsigned)__shfl_xor((int)ownpack[0], 16);
+                othpack[1] = (unsigned)__shfl_xor((int)ownpack[1], 16);
+            }
+            const int row0 = q0 + QB * rn;
+            if (lg == 0) {
+#pragma unroll
+                for (int qb = 0; qb < QB; ++qb)
+                    if (row0 + qb < nb)
+                        *reinterpret_cast<v2i *>(A.col + 2 * (col_u + row0 + qb)) = v2i{v1s[qb], v2s[qb]};
+                if (A.colmask) {
+                    // byte qb = own nibble | other half's nibble << 4
+                    uint8_t *dst = A.colmask + col_u + row0;
+                    if (row0 + QB <= nb) {
+                        auto spread = [](unsigned nib4) {    // four nibbles -> the low nibbles of four bytes
+                            const unsigned x = (nib4 | (nib4 << 8)) & 0x00FF00FFu;
+                            return (x | (x << 4)) & 0x0F0F0F0Fu;
+                        };
+                        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                        v4u o;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            o[2 * h] = spread(ownpack[h] & 0xFFFFu) | (spread(othpack[h] & 0xFFFFu) << 4);
+                            o[2 * h + 1] = spread(ownpack[h] >> 16) | (spread(othpack[h] >> 16) << 4);
+                        }
+                        *reinterpret_cast<v4u *>(dst) = o;
+                    } else {
+#pragma unroll
+                        for (int qb = 0; qb < QB; ++qb)
+                            if (row0 + qb < nb)
+                                dst[qb] = (uint8_t)(((ownpack[qb >> 3] >> (4 * (qb & 7))) & 15u) |
+                                                    (((othpack[qb >> 3] >> (4 * (qb & 7))) & 15u) << 4));
+                    }
+                }
+            }
+        }
+        if (++u == uniform32(u_end)) break;
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // candidates.  Pass 1 (symcand_rows_kernel, one thread per query row) visits the rows in SORTED
 // order (the order the sweep wrote its bounds in: coalesced reads) and drops a flag at the row's
 // original position; pass 2 (symcand_kernel, one workgroup per ORDERED pair) lists the flagged rows
@@ -2576,6 +3010,33 @@ extern "C" int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2,
     hipLaunchKernelGGL((knn2sym_kernel<SWEEP_ITEMS2>), dim3((unsigned)n_items), dim3(256), 0,
                        iamx::as_stream(stream), a);
     return iamx::check_launch("iamx_knn2sym_sweep_items");
+}
+
+// the item walk on v_mfma_i32_16x16x64_i8 (knn2sym16_kernel): the arguments and the outputs of
+// iamx_knn2sym_sweep_items, bit for bit
+#define SWEEP16_PIPE 2
+extern "C" const char *iamx_knn2sym_items16_kernel_id(void)
+{
+    return "knn2sym16_kernel<" SWEEP_STR(SWEEP16_PIPE) ">";
+}
+
+extern "C" int iamx_knn2sym_sweep_items16(const int8_t *sdesc, const int32_t *sn2, const int32_t *sct,
+                                          const int32_t *img_off, const int32_t *img_n,
+                                          const int32_t *upairs, const int32_t *items,
+                                          const int64_t *col_off, const int64_t *rowp_off, int n_u,
+                                          int n_items, int32_t *col, int32_t *rowp, uint8_t *colmask,
+                                          void *stream)
+{
+    IAMX_REQUIRE(sdesc && sn2 && sct && img_off && img_n && upairs && items && col_off && rowp_off &&
+                     col && rowp,
+                 "null pointer");
+    IAMX_REQUIRE(n_u >= 0 && n_items >= 0, "negative count");
+    if (n_u == 0 || n_items == 0) return IAMX_OK;
+    SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, items, col_off, rowp_off, col, rowp, n_u, n_items,
+              colmask SWEEP_STAMPS_ARG};
+    hipLaunchKernelGGL((knn2sym16_kernel<SWEEP16_PIPE>), dim3((unsigned)n_items), dim3(256), 0,
+                       iamx::as_stream(stream), a);
+    return iamx::check_launch("iamx_knn2sym_sweep_items16");
 }
 
 // IAMX_EXACT_NARROW=0: every candidate through the full scan (A/B, tests)

@@ -1185,6 +1185,7 @@ class PairBatch(object):
         self.d_rowp_off = up(t['rowp_off'][:-1].copy())
         self.d_osrc = up(t['osrc'])
         self.sym_items_s = t['S']
+        self.sym_items_entry = 'iamx_knn2sym_sweep_items16'
         # form 2 with S > 1 walks items of S pairs that share their B image; at S = 1 (long images) the
         # one-pair kernel runs: the item kernel with one pair per item measured 0.6-0.9 % slower there
         # (profiles/r8_sweep_time.txt)
@@ -1197,11 +1198,14 @@ class PairBatch(object):
         st = self.store
         ws.ensure_sym(self.sym_col_rows, self.sym_rowp_rows)
         if self.sym_items_s > 1:
-            check(lib().iamx_knn2sym_sweep_items(_ptr(st.desc3), _ptr(st.sn2), _ptr(st.sct), _ptr(st.img_off3),
-                                                 _ptr(st.img_n), _ptr(self.d_upairs), _ptr(self.d_sym_items),
-                                                 _ptr(self.d_col_off), _ptr(self.d_rowp_off), self.n_u,
-                                                 self.n_sym_items, _ptr(ws.col), _ptr(ws.rowp),
-                                                 _ptr(ws.colmask), stream_ptr()), 'iamx_knn2sym_sweep_items')
+            # the item walk on v_mfma_i32_16x16x64_i8: iamx_knn2sym_sweep_items' outputs, bit for bit
+            # (`sym_items_entry`: tests run the 32x32x32 item kernel through the same batch)
+            entry = self.sym_items_entry
+            check(getattr(lib(), entry)(_ptr(st.desc3), _ptr(st.sn2), _ptr(st.sct), _ptr(st.img_off3),
+                                        _ptr(st.img_n), _ptr(self.d_upairs), _ptr(self.d_sym_items),
+                                        _ptr(self.d_col_off), _ptr(self.d_rowp_off), self.n_u,
+                                        self.n_sym_items, _ptr(ws.col), _ptr(ws.rowp),
+                                        _ptr(ws.colmask), stream_ptr()), entry)
             return
         check(lib().iamx_knn2sym_sweep(_ptr(st.desc3), _ptr(st.sn2), _ptr(st.sct), _ptr(st.img_off3),
                                        _ptr(st.img_n), _ptr(self.d_upairs), _ptr(self.d_sym_wg),

@@ -290,6 +290,15 @@ int iamx_knn2sym_sweep_items(const int8_t *sdesc, const int32_t *sn2, const int3
                              const int32_t *items, const int64_t *col_off, const int64_t *rowp_off,
                              int n_u, int n_items, int32_t *col, int32_t *rowp,
                              uint8_t *colmask /* may be NULL */, void *stream);
+/* iamx_knn2sym_sweep_items on v_mfma_i32_16x16x64_i8 (the shape the chip clocks higher): the same
+ * arguments, the same col, rowp and colmask bit for bit; iamx_knn2sym_items16_kernel_id() is its
+ * kernel's name the way rocprofv3 prints it. */
+int iamx_knn2sym_sweep_items16(const int8_t *sdesc, const int32_t *sn2, const int32_t *sct,
+                               const int32_t *img_off, const int32_t *img_n, const int32_t *upairs,
+                               const int32_t *items, const int64_t *col_off, const int64_t *rowp_off,
+                               int n_u, int n_items, int32_t *col, int32_t *rowp,
+                               uint8_t *colmask /* may be NULL */, void *stream);
+const char *iamx_knn2sym_items16_kernel_id(void);
 /* iamx_knn2sym_candidates reads sn2, col and rowp 16 bytes (four sorted rows) at a time: img_off
  * (= img_off3 of the sorted store), col_off and rowp_off must be multiples of 4 rows, every image's
  * slice of sn2 / col and every workgroup's slice of rowp padded to iamx_desc3_rows_cap(n) rows, and the

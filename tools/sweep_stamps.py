@@ -72,6 +72,8 @@ def load(path):
     vp, ci = ctypes.c_void_p, ctypes.c_int
     L.iamx_knn2sym_sweep_items.restype = ci
     L.iamx_knn2sym_sweep_items.argtypes = [vp] * 9 + [ci, ci] + [vp] * 4
+    L.iamx_knn2sym_sweep_items16.restype = ci
+    L.iamx_knn2sym_sweep_items16.argtypes = [vp] * 9 + [ci, ci] + [vp] * 4
     L.iamx_knn2sym_sweep.restype = ci
     L.iamx_knn2sym_sweep.argtypes = [vp] * 9 + [ci, ci, ci] + [vp] * 4
     L.iamx_knn2sym_set_stamps.restype = ci
@@ -120,7 +122,7 @@ def startup_store():
 
 
 def measure(L, kernel, args, n_wg, seconds):
-    launch = L.iamx_knn2sym_sweep_items if kernel == 'items' else L.iamx_knn2sym_sweep
+    launch = {'items': L.iamx_knn2sym_sweep_items, 'items16': L.iamx_knn2sym_sweep_items16}.get(kernel, L.iamx_knn2sym_sweep)
     buf = torch.zeros((n_wg, NW, 4), dtype=torch.int64, device='cuda')
     L.iamx_knn2sym_set_stamps(buf.data_ptr())
     t_end = time.time() + seconds
@@ -143,6 +145,9 @@ def main():
     ap.add_argument('--dir', default='/tmp/iamx_stamps', help='where the variant libraries are built (and found)')
     ap.add_argument('--segments', default='1-19')
     ap.add_argument('--seconds', type=float, default=1.0, help='back-to-back launches per variant and store')
+    ap.add_argument('--loops', action='store_true',
+                    help='the 4096-row store only, whole chunk loop only: the 32x32x32 item kernel and the 16x16x64 one '
+                         '(which stamps nothing else), alternating, from the first library of --segments')
     ap.add_argument('--build-only', action='store_true')
     ap.add_argument('--prebuilt', action='store_true', help='take the libraries found in --dir as they are')
     args = ap.parse_args()
@@ -154,6 +159,17 @@ def main():
     if args.build_only:
         return
     torch.cuda.set_device(0)
+    if args.loops:
+        L = load(jobs[0][1])
+        _kernel, a, n_wg, _keep = startup_store()
+        print('device %s; 4096-row store, %d workgroups, %.1f s of back-to-back launches each; median over waves'
+              % (torch.cuda.get_device_name(0), n_wg, args.seconds))
+        for rep in range(3):
+            for kernel in ('items', 'items16'):
+                _seg, loop, ghz = measure(L, kernel, a, n_wg, args.seconds)
+                print('  %-8s chunk loop %7.0f cycles a chunk, in-kernel clock %.3f GHz, %.3f us a chunk'
+                      % (kernel, loop, ghz, loop / ghz * 1e-3))
+        return
     stores = [('dense', ) + dense_store(), ('4096-row', ) + startup_store()]
     res = {}
     for s, (_, path) in zip(segs, jobs):
