@@ -1,5 +1,6 @@
 """Thin python bindings over the C ABI: torch tensors are device-buffer containers only,
 every number is produced by a hand-written HIP kernel in libiamx.so (csrc/*.hip)."""
+import math
 import os
 import threading
 
@@ -1004,6 +1005,140 @@ def smart_pairs(store, pairs, kp_off, xy, size, key2, H0, tol, min_pairs, match_
     res.rows, res.cnt, res.H = out_rows, cnt_all, H.view(P, 3, 3)
     res.off = exclusive_scan(cnt_all)
     return res
+
+
+# --------------------------------------------------------------------------------------
+# the 'bruteforce' strategy (csrc/match_knn3.hip, csrc/match_brute.hip): candidate choice and 41 x 21
+# motion cells -> RANSAC homography per cell -> the walk with the early exit
+# --------------------------------------------------------------------------------------
+BRUTE_DIST_BINS, BRUTE_ANGLE_BINS = 41, 21                        # matcher.py:758, :779 (divs + 1)
+BRUTE_CELLS = BRUTE_DIST_BINS * BRUTE_ANGLE_BINS
+BRUTE_STEP_A = 2 * math.pi / (BRUTE_ANGLE_BINS - 1)               # matcher.py:780
+BRUTE_BATCH_BYTES = 4 << 30
+
+
+class BruteResult(object):
+    """what brute_pairs() returns, device tensors over its n pairs: rows int32 [total, 2] (query
+    row, train row) packed back to back, off int64 [n + 1], cnt int32 [n], chosen int32 [n] (the
+    taken cell dbin * 21 + abin, -1: none), stats int32 [n, 4] = fitted, unique (-1: the
+    de-duplication did not run), distance bins walked, cells looked at within them, fit_cnt int32
+    [n, 861] the fitted inliers of every cell (-1: not looked at or not reached), bin_cnt int32
+    [n, 861] the members of every cell, flag int32 [2] (rows with a zero nearest distance, pairs
+    refused).  slots int32 [n, stride, 2]: the same lists in fixed slots (iamx_similarity_pairs'
+    layout) when the call was one launch, else None."""
+    __slots__ = ('rows', 'off', 'cnt', 'chosen', 'stats', 'fit_cnt', 'bin_cnt', 'flag', 'slots', 'stride')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def brute_bytes(nq):
+    """device bytes one launch of brute_pairs() over query images of `nq` rows (an array) takes: the
+    top-3 rows (24 B), nine materialised members (9 x 25 B), the packed result (8 B) per query row,
+    and per pair the 861-wide tables (members, segments, offsets, status, best, model, fitted: 112 B
+    a cell) and the select stage's slices at the launch's stride (work lists 24 B, result slot 8 B per
+    row of the largest query image, two key tables of tab_size x 4 B)"""
+    nq = np.asarray(nq, np.int64).reshape(-1)
+    if not len(nq):
+        return 0
+    stride = max(int(nq.max()), 1)
+    return int(nq.sum()) * (32 + 25 * 9) + len(nq) * (32 * stride + 8 * _ratio_tab_size(stride) + 112 * BRUTE_CELLS)
+
+
+def _brute_launch(store, pairs, kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d, hypotheses,
+                  seed, flag):
+    """one launch chain over pairs whose images all have at least 2 rows"""
+    dev = require_gpu()
+    L = lib()
+    NC, P = BRUTE_CELLS, len(pairs)
+    idx, d2, out_off = knn3_pairs(store, pairs)
+    total = int(out_off[-1])
+    nq = np.diff(out_off)
+    stride = max(int(nq.max()), 1)
+    tab = _ratio_tab_size(stride)
+    cap = 9 * total
+    d_pairs = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev)
+    row_off = torch.from_numpy(out_off).to(dev)
+    z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
+    bin_cnt, seg_cnt = z32(P, NC), z32(P, NC)
+    seg_off = torch.zeros(P * NC + 1, dtype=I64, device=dev)
+    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
+    check(L.iamx_brute_bins(_ptr(idx), _ptr(d2), _ptr(row_off), _ptr(d_pairs), _ptr(kp_off), _ptr(xy),
+                            _ptr(size), P, float(match_ratio), float(min_pairs), float(step_d),
+                            BRUTE_STEP_A, cap, _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts),
+                            _ptr(rows), _ptr(flag), stream_ptr()), 'iamx_brute_bins')
+    # every cell's consensus is iamx_verify_pairs on that cell's points as one segment (the cells the
+    # early exit leaves unreached included: the walk alone is pruned)
+    mask, _model, _best, vstatus = verify_pairs(pts[:cap], seg_off, 'homography',
+                                                float(tol), hypotheses=hypotheses, seed=seed)
+    work = torch.empty(P * (6 * stride + 2 * tab), dtype=I32, device=dev)
+    slots = torch.empty((P, stride, 2), dtype=I32, device=dev)
+    cnt, chosen, stats, fit_cnt = z32(P), z32(P), z32(P, 4), z32(P, NC)
+    off = torch.zeros(P + 1, dtype=I64, device=dev)
+    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
+    check(L.iamx_brute_select(_ptr(d_pairs), _ptr(kp_off), _ptr(key2), P, float(min_pairs), _ptr(seg_cnt),
+                              _ptr(seg_off), _ptr(rows), _ptr(mask), _ptr(vstatus), cap, stride, tab,
+                              _ptr(work), _ptr(slots), _ptr(cnt), _ptr(off), _ptr(out_rows), total,
+                              _ptr(chosen), _ptr(stats), _ptr(fit_cnt), _ptr(flag), stream_ptr()),
+          'iamx_brute_select')
+    return BruteResult(rows=out_rows, off=off, cnt=cnt, chosen=chosen, stats=stats, fit_cnt=fit_cnt,
+                       bin_cnt=bin_cnt, flag=flag, slots=slots, stride=stride)
+
+
+def brute_pairs(store, pairs, kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d, hypotheses,
+                seed, batch_bytes=BRUTE_BATCH_BYTES):
+    """scripts/lib/matcher.py:696-850 bruteforce_pair_matches() for a batch of ordered (query image,
+    train image) pairs of `store`: exact k=3 neighbours (knn3_pairs), the per-row choice and the 41 x
+    21 motion cells (iamx_brute_bins; step_d = int(diag * 0.55) / 40), a RANSAC homography per cell
+    at `tol` pixels (verify_pairs' rule with `hypotheses` and `seed`) over all n_pairs * 861 segments
+    in one launch, the walk with the early exit and the min_pairs gates (iamx_brute_select).  kp_off
+    / xy / key2: the keypoint arena of the store's slots (DeviceMatcher.keypoints()), size: kp.size
+    beside xy (DeviceMatcher.sizes()).  A pair with an image of at most 1 row ends with nothing
+    (raw_matches' guards).  The work is enqueued on the current stream in launches of at most
+    batch_bytes of device memory each (brute_bytes); -> BruteResult."""
+    dev = require_gpu()
+    NC = BRUTE_CELLS
+    if not (float(step_d) > 0.0 and math.isfinite(float(step_d))):
+        raise ValueError("brute_pairs: step_d must be positive and finite")
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    P = len(pairs)
+    counts = np.asarray(store.counts, np.int64)
+    nq = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
+    ok = (nq >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
+    live = np.nonzero(ok)[0]
+    # launches of at most batch_bytes (a launch's stride is its largest query image)
+    chunks, a = [], 0
+    while a < len(live):
+        b = a + 1
+        while b < len(live) and brute_bytes(nq[live[a:b + 1]]) <= batch_bytes:
+            b += 1
+        chunks.append(live[a:b])
+        a = b
+    flag = torch.zeros(2, dtype=I32, device=dev)            # (the launches only ever raise it)
+    parts = [_brute_launch(store, pairs[c], kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d,
+                           hypotheses, seed, flag) for c in chunks]
+    if len(parts) == 1 and len(live) == P:
+        return parts[0]
+    # the launches' results side by side (copies and one scan, no arithmetic of their own)
+    cnt = torch.zeros(P, dtype=I32, device=dev)
+    chosen = torch.full((P,), -1, dtype=I32, device=dev)
+    stats = torch.zeros((P, 4), dtype=I32, device=dev)
+    stats[:, 1] = -1
+    fit_cnt = torch.full((P, NC), -1, dtype=I32, device=dev)
+    bin_cnt = torch.zeros((P, NC), dtype=I32, device=dev)
+    rows = []
+    for c, r in zip(chunks, parts):
+        where = torch.from_numpy(c).to(dev)
+        cnt[where], chosen[where], stats[where] = r.cnt, r.chosen, r.stats
+        fit_cnt[where], bin_cnt[where] = r.fit_cnt, r.bin_cnt
+        rows.append(r.rows[:int(r.off[-1])])
+    off = exclusive_scan(cnt) if P else torch.zeros(1, dtype=I64, device=dev)
+    rows = torch.cat(rows) if rows else torch.empty((0, 2), dtype=I32, device=dev)
+    one = len(parts) == 1
+    return BruteResult(rows=rows, off=off, cnt=cnt, chosen=chosen, stats=stats, fit_cnt=fit_cnt,
+                       bin_cnt=bin_cnt, flag=flag, slots=None, stride=parts[0].stride if one else None)
 
 
 # --------------------------------------------------------------------------------------

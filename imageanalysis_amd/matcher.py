@@ -31,7 +31,16 @@ estimate picks among every feature's THREE nearest neighbours (csrc/match_knn3.h
 homography per distance bin and a least-squares refit tighten it pass by pass (csrc/match_smart.hip).
 Its pair loop is serial -- every pair's prediction depends on the pairs before it -- so it does not go
 through the batched rounds; find_matches(strategy='smart') itself still ends in quit() and is routed
-to smart_matches in a later change, and 'bruteforce' stays out.
+to smart_matches in a later change.
+The 'bruteforce' strategy (matcher.py:696-850) has entries of its own too, bruteforce_pair_matches /
+bruteforce_matches: three neighbours and no prior -- every row's choice by size_diff / ratio, the
+choices grouped by their image-space motion into 41 x 21 overlapping (length, direction) cells, a
+RANSAC homography per cell, the cell with the most fitted inliers, the distance bins walked with the
+reference's early exit (csrc/match_brute.hip).  Its pairs are independent, so bruteforce_matches runs
+through the batched rounds; find_matches(strategy='bruteforce') still ends in quit(); the entry is
+bruteforce_matches.  The review windows, a wave form of the consensus that skips what the early exit
+makes unnecessary, and a run on more than one rank are left out; the consensus is this package's rule,
+parity with cv2 UNPINNED.
 """
 import contextlib
 import ctypes
@@ -928,6 +937,209 @@ def smart_matches(proj, K, sort=False):
     saveMatches(proj.image_list)
     smart.save(proj.analysis_dir)
     print('Pair-wise matches successfully saved.')
+
+
+# --------------------------------------------------------------------------------------
+# the 'bruteforce' strategy -- matcher.py:696-850 and its pair loop :923-1031
+# --------------------------------------------------------------------------------------
+BRUTE_MAX_DISTANCE = 290        # matcher.py:719 (csrc/match_brute.hip compares d2 with its square)
+BRUTE_SIZE_RATIO = 1.25         # matcher.py:740
+BRUTE_DIST_DIVS = 40            # matcher.py:758: 41 distance bins
+BRUTE_ANGLE_DIVS = 20           # matcher.py:779: 21 angle bins
+BRUTE_BATCH_BYTES = 8 << 30     # device memory of one round's cells / consensus / select stage
+brute_last = None               # the last bruteforce_pair_matches() call: dict(stats, chosen, fit_cnt)
+# (BRUTE_HYPOTHESES = RATIO_HYPOTHESES stands beside that figure, below)
+
+
+def _brute_diag():
+    w, h = _camera_size()
+    return int(sqrt(h * h + w * w))
+
+
+def _brute_tol():
+    """matcher.py:760-761: half a percent of the image diagonal TRUNCATED (int, not int(round()) as in
+    'bestratio', :606-611), at least 5 px"""
+    tol = int(_brute_diag() * 0.005)
+    return 5 if tol < 5 else tol
+
+
+def _brute_step():
+    """matcher.py:756-759: the width of a distance bin, int(diag * 0.55) / 40"""
+    return int(_brute_diag() * 0.55) / BRUTE_DIST_DIVS
+
+
+def _brute_log(bin_cnt, fit_cnt, walked):
+    """the reference's lines of the walk (matcher.py:777, :818-819, :831-832) from the per-cell figures.
+    (The loop over a taken cell's matches, :813, re-uses the name `i`: after a taken cell the reference's
+    line at :831 shows that cell's last position where the bin number belongs, and so does this one.)"""
+    bin_cnt = np.asarray(bin_cnt).reshape(BRUTE_DIST_DIVS + 1, BRUTE_ANGLE_DIVS + 1)
+    fit_cnt = np.asarray(fit_cnt).reshape(BRUTE_DIST_DIVS + 1, BRUTE_ANGLE_DIVS + 1)
+    best = 0
+    for d in range(int(walked)):
+        n = int(bin_cnt[d].sum()) // 3              # (a row of the distance bin is in three of its cells)
+        _qlog("bin:", d, "len:", n)
+        best_of_bin, shown = 0, d
+        for a in range(BRUTE_ANGLE_DIVS + 1):
+            fit = int(fit_cnt[d, a])
+            if fit < 0:
+                continue
+            best_of_bin = max(best_of_bin, fit)
+            if fit > best:
+                best = fit
+                shown = int(bin_cnt[d, a]) - 1
+                _qlog("Filtered matches:", int(bin_cnt[d, a]), "Fitted matches:", fit)
+        _qlog("bin:", shown, "len:", n, best, best_of_bin)
+
+
+def bruteforce_pair_matches(i1, i2, review=False, hypotheses=None, seed=0):
+    """matcher.py:696-850 for one ordered pair -> (idx_pairs, rev_pairs).  review is accepted and
+    unused (the reference's review path opens windows).  The RANSAC homography of every cell is this
+    package's rule (iamx_verify_pairs with `hypotheses`, default BRUTE_HYPOTHESES, and `seed`), not cv2's."""
+    global brute_last
+    brute_last = None
+    match_ratio = matcher_node.getFloat('match_ratio')
+    if i1.des_list is None or i2.des_list is None:
+        return [], []
+    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
+        return [], []
+    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+        return [], []
+    if the_matcher is None:
+        configure()
+    import torch
+    from . import kernels
+    dev = _lib.require_gpu()
+    xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
+    store = kernels.DescriptorStore.from_arrays([np.ascontiguousarray(i1.des_list),
+                                                 np.ascontiguousarray(i2.des_list)])
+    xy = np.ascontiguousarray(np.concatenate([xy1, xy2]), np.float32)
+    size = np.ascontiguousarray(np.concatenate([_kp_size(i1), _kp_size(i2)]), np.float32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    r = kernels.brute_pairs(store, [[0, 1]], up(np.array([0, len(xy1)], np.int64)), up(xy), up(size),
+                            up(np.concatenate([kp_key2(xy1), kp_key2(xy2)])), _brute_tol(), min_pairs,
+                            match_ratio, _brute_step(),
+                            BRUTE_HYPOTHESES if hypotheses is None else hypotheses, seed)
+    _ratio_flags(r.flag.cpu().numpy())                  # (matcher.py:721: 0.0 / 0.0)
+    stats, chosen = r.stats.cpu().numpy()[0], int(r.chosen.cpu().numpy()[0])
+    fit_cnt = r.fit_cnt.cpu().numpy()[0]
+    brute_last = dict(stats=stats, chosen=chosen, fit_cnt=fit_cnt)
+    _qlog("  raw matches:", len(xy1))
+    _qlog("  collect stats...")
+    _brute_log(r.bin_cnt.cpu().numpy()[0], fit_cnt, stats[2])
+    pairs = r.rows[:int(r.off[-1])].cpu().numpy()
+    if not len(pairs):
+        return [], []
+    _qlog("  initial matches =", len(pairs))
+    return pairs.tolist(), pairs[:, ::-1].tolist()
+
+
+def _brute_pairs_per_batch(rows):
+    """ordered pairs per round of the 'bruteforce' strategy: as many as BRUTE_BATCH_BYTES hold at
+    `rows` descriptors per image (kernels.brute_bytes), at most PAIRS_PER_BATCH"""
+    from . import kernels
+    per_pair = max(kernels.brute_bytes([max(int(rows), 1)]), 1)
+    return int(max(1, min(PAIRS_PER_BATCH, BRUTE_BATCH_BYTES // per_pair)))
+
+
+def _launch_brute_batch(view, rows_i, rows_j, surface, match_ratio):
+    """a round of bruteforce_matches: ENQUEUES, on the current stream, the k=3 search of the FORWARD
+    pairs only, the cells / consensus / walk (kernels.brute_pairs) and, with `surface`, the similarity
+    fits; the handle goes to _finish_brute_arrays().  A pair with an image of at most one row never
+    reaches the device (raw_matches' guards)."""
+    import torch
+    from . import kernels
+    from .kernels import _ptr, check, lib, stream_ptr
+    dm = the_matcher
+    n = len(view)
+    live = np.nonzero((np.asarray(rows_i) > 1) & (np.asarray(rows_j) > 1))[0]
+    h = dict(brute=True, batch=view, n=n, live=live, surface=surface, r=None)
+    if len(live):
+        slot_of = np.zeros(len(view.image_list), np.int32)
+        for u in np.unique(np.concatenate([view.pi[live], view.pj[live]])).tolist():
+            slot_of[u] = dm.slot_of(view.image_list[u])
+        if dm._pending or dm._kp_dev is None or dm._kp_dev[0] != len(dm._counts):
+            # (the arenas are about to be rebuilt: an earlier traditional round's side stream may read them)
+            torch.cuda.current_stream().wait_stream(_side_stream())
+        store = dm.store()
+        kp_off, xy, key2 = dm.keypoints()
+        slots = np.ascontiguousarray(np.stack([slot_of[view.pi[live]], slot_of[view.pj[live]]], 1), np.int32)
+        # (one launch chain: the round was sized by _brute_pairs_per_batch)
+        r = h['r'] = kernels.brute_pairs(store, slots, kp_off, xy, dm.sizes(), key2, _brute_tol(), min_pairs,
+                                         match_ratio, _brute_step(), BRUTE_HYPOTHESES, 0, batch_bytes=1 << 62)
+        # the members of the taken cell: what the reference's log calls the filtered matches
+        took = r.chosen >= 0
+        h['n_fwd'] = torch.where(took, torch.gather(r.bin_cnt, 1, r.chosen.clamp(min=0).long()[:, None])[:, 0],
+                                 torch.zeros_like(r.chosen))
+        if surface:
+            dev = xy.device
+            d_pairs = torch.from_numpy(slots).to(dev)
+            h['aff'] = torch.empty((len(live), 2, 6), dtype=torch.float64, device=dev)
+            h['aff_ok'] = torch.empty((len(live), 2), dtype=torch.int32, device=dev)
+            check(lib().iamx_similarity_pairs(_ptr(d_pairs), _ptr(kp_off), _ptr(xy), _ptr(r.cnt),
+                                              _ptr(r.slots), len(live), r.stride, _ptr(h['aff']),
+                                              _ptr(h['aff_ok']), stream_ptr()), 'iamx_similarity_pairs')
+            h['tables'] = (d_pairs, kp_off, xy, key2)
+    h['done'] = torch.cuda.Event()
+    h['done'].record()
+    return h
+
+
+def _finish_brute_arrays(h):
+    """-> _RoundResult of a round of the 'bruteforce' strategy.  n_fwd: the members of the taken cell,
+    n_rev 0: there is no reverse search; the reverse list is the forward one mirrored, which is
+    _RoundResult's invariant."""
+    h['done'].synchronize()
+    n, live, r, view = h['n'], h['live'], h['r'], h['batch']
+    R = _RoundResult(n)
+    cnt = np.zeros(n, np.int64)
+    R.n_fwd, R.n_rev = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    src = np.zeros((0, 2), np.int32)
+    if r is not None:
+        _ratio_flags(r.flag.cpu().numpy())
+        cnt[live] = r.cnt.cpu().numpy()
+        R.n_fwd[live] = h['n_fwd'].cpu().numpy()
+        src = np.ascontiguousarray(r.rows[:int(cnt.sum())].cpu().numpy())
+    R.cc, R.quiet = cnt, cnt == 0
+    hit = np.nonzero(cnt > 0)[0]
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    R.hit_rows, R.lo, R.hi = hit.astype(np.int64), off[hit], off[hit] + cnt[hit]
+    if len(hit):
+        R.fwd_all, R.rev_all = src, np.ascontiguousarray(src[:, ::-1])
+    R.fit = bool(h['surface'])
+    if R.fit:
+        where = np.searchsorted(live, hit)                   # (a pair with matches is a live one)
+        aff = h['aff'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2, 6))
+        aff_ok = h['aff_ok'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2), np.int32)
+        _round_fits(R, view, aff, aff_ok)
+    return R
+
+
+def bruteforce_matches(proj, K, sort=False):
+    """The pair loop of matcher.py:923-1031 for strategy 'bruteforce', through the batched rounds of
+    find_matches: the strategy needs no prior, so its pairs are independent of each other (unlike
+    'smart') and a round is one k = 3 search, one iamx_brute_bins, one consensus launch over all its
+    cells and one walk.  find_matches(strategy='bruteforce') itself still ends in quit(); this is the
+    entry.  One rank on GPUs (a run on several is left out)."""
+    from . import dist as _dist
+    if _dist.world()[1] > 1:
+        raise NotImplementedError("bruteforce_matches: run it on one rank")
+    with _no_gc():
+        try:
+            if the_matcher is None:
+                configure()
+            _route_reset()
+            smart = _deps.smart()
+            if smart is not None:
+                smart.freeze_poses(True)
+            run = _MatchRun(proj, sort, 'bruteforce')
+            run.schedule()
+            run.prepare()
+            run.rounds()
+            run.finish()
+            print('Pair-wise matches successfully saved.')
+        finally:
+            if _deps.smart() is not None:
+                _deps.smart().freeze_poses(False)
 
 
 # --------------------------------------------------------------------------------------
@@ -2119,8 +2331,11 @@ class _MatchRun(object):
                     first = image_list[int(wi[rank])]
                     _ensure_features(first)
                     known = [_rows_of(first)]
-                ppb = _pairs_per_batch(1.25 * max(known)) if self.strategy == 'traditional' else \
-                    _ratio_pairs_per_batch(max(known))
+                if self.strategy == 'bruteforce':
+                    ppb = _brute_pairs_per_batch(max(known))
+                else:
+                    ppb = _pairs_per_batch(1.25 * max(known)) if self.strategy == 'traditional' else \
+                        _ratio_pairs_per_batch(max(known))
         except (Exception, SystemExit) as exc:
             if ws == 1:
                 raise
@@ -2219,7 +2434,10 @@ class _MatchRun(object):
             if rows[k] <= 1 and self.strategy == 'traditional':
                 # raw_matches() returns [] and basic_pair_matches divides by len([]) (:232)
                 raise ZeroDivisionError("float division by zero")
-        if self.strategy == 'bestratio':
+        if self.strategy == 'bruteforce':
+            # (bruteforce_pair_matches returns [], [] under raw_matches' guards, as below)
+            handle = _launch_brute_batch(view, rows[view.pi], rows[view.pj], bool(self.surface), self.match_ratio)
+        elif self.strategy == 'bestratio':
             # (ratio_pair_matches returns [], [] under raw_matches' guards: such a pair ends with nothing)
             handle = _launch_ratio_batch(view, rows[view.pi], rows[view.pj], bool(self.surface))
         else:
@@ -2229,6 +2447,9 @@ class _MatchRun(object):
     def finish_round(self, launched):
         """-> _Part: the round's pairs of this rank and their results as arrays"""
         view, sl, handle = launched
+        if isinstance(handle, dict) and handle.get('brute'):
+            R = _finish_brute_arrays(handle)
+            return _Part(sl, view.pi, view.pj, self.wd[sl], self.rows[view.pi], self.rows[view.pj], R)
         R = _finish_ratio_arrays(handle) if isinstance(handle, dict) and handle.get('ratio') else \
             _finish_batch_arrays(handle)
         return _Part(sl, view.pi, view.pj, self.wd[sl], self.rows[view.pi], self.rows[view.pj], R)
@@ -2648,6 +2869,7 @@ def saveMatches(image_list, check_if_dirty=False):
 VERIFY_BATCH_MATCHES = 1 << 22          # matches per launch of verify_matches (64 MiB of points)
 VERIFY_HYPOTHESES = {'homography': 2048, 'fundamental': 2048, 'essential': 256}
 RATIO_HYPOTHESES = VERIFY_HYPOTHESES['homography']      # the consensus of every bin of 'bestratio'
+BRUTE_HYPOTHESES = RATIO_HYPOTHESES                     # ... and of every cell of 'bruteforce'
 _ESSENTIAL_REASON = ("transform 'essential': the five-point solver works on calibrated rays and no "
                      "camera matrix was given.  Pass K, or use 'fundamental' or 'homography'.")
 

@@ -1631,6 +1631,74 @@ int iamx_smart_select(const int32_t *pairs, const int64_t *kp_off, const int32_t
                       int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *stats, double *H,
                       int32_t *fit_status, int32_t *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * The 'bruteforce' strategy -- scripts/lib/matcher.py:696-850 bruteforce_pair_matches(): ONE
+ * direction of every pair, no pose prior.  Among every feature's three nearest neighbours
+ * (iamx_knn3_l2_pairs) the one of the smallest size_diff / ratio; the choices grouped by their
+ * image-space motion into 41 x 21 overlapping (length, direction) cells; a RANSAC homography per
+ * cell; the cell with the most fitted inliers, the distance bins walked with the reference's early
+ * exit.  Three launches: iamx_brute_bins, iamx_verify_pairs(model = homography) over the n_pairs *
+ * IAMX_BRUTE_CELLS segments it leaves, iamx_brute_select.  The Python-level rules are the
+ * reference's; the consensus is iamx_verify_pairs' rule (parity with cv2 UNPINNED).
+ *
+ * iamx_brute_bins, one workgroup per ordered pair over its top-3 rows:
+ *   idx / d2 DEV [total rows][3]; row_off, pairs, kp_off, xy, size, pts, rows, flag as for
+ *   iamx_smart_stats.  step_d = int(diag * 0.55) / 40 with diag = int(sqrt(h * h + w * w)) and
+ *   step_a = 2 pi / 20, computed by the caller as doubles; both positive and finite.
+ *   Query row i: neighbours j = 0, 1, 2 in order, with d* = float32(sqrt(d2*)): stop at d2[j] >=
+ *   84100 (distance >= 290; a missing neighbour, idx -1 / d2 0x7FFFFFFF, too); ratio = (double)d0 /
+ *   (double)dj, stop at ratio < match_ratio; v = kp2.pt - kp1.pt in float32; raw_dist = the
+ *   correctly rounded float32 root of the float32 sum of v's squares; size_diff = the larger of the
+ *   two kp.size over the smaller as doubles, the neighbour is passed over (not a stop) at size_diff >
+ *   1.25; metric = size_diff / ratio; the first neighbour that gets here is the row's choice, a later
+ *   one replaces it at a strictly smaller metric.  vangle = atan2((double)v.y, (double)v.x), plus
+ *   2 pi where it is negative (-0.0 is not).  A row with d2[0] == 0 has no choice and adds 1 to
+ *   flag[0] (python divides 0.0 by 0.0: the caller raises ZeroDivisionError).
+ *   dbin = rint((double)raw_dist / step_d), round-half-even -- a FLOAT64 quotient: the reference's
+ *   environment pins NumPy 1.20, where np.float32 / float is one (under NumPy 2 the same expression
+ *   is a float32 quotient; the goldens refuse every row on which the two differ).  A row with dbin >
+ *   40 is in no cell; else it is in distance bins dbin, dbin - 1 (dbin > 0) and dbin + 1 (dbin < 40).
+ *   abin = rint(vangle / step_a) in 0..20; the row is in angle bins abin - 1, abin, abin + 1, for
+ *   abin == 0 in 20, 0, 1 and for abin == 20 in 19, 20, 0 (matcher.py:785-795 as it stands).  So a
+ *   row is in up to nine of the cells dbin * 21 + abin, once in each, and every cell's members are
+ *   in QUERY-ROW ORDER (the consensus' sample sequence and filter_duplicates depend on it).
+ *   bin_cnt DEV [n_pairs][861] members of every cell.  seg_cnt DEV [n_pairs][861]: the same where
+ *   the cell is looked at -- at least min_pairs members (matcher.py:797) and at least 4 (a
+ *   homography's sample) -- else 0.  seg_off DEV [n_pairs * 861 + 1] int64: exclusive scan of seg_cnt
+ *   = the m_off of iamx_verify_pairs.  pts DEV [cap][4] / rows DEV [cap][2]: the looked-at cells;
+ *   cap >= 9 * total rows.  A pair of more than 2^24 rows gets nothing and adds 1 to flag[1].
+ *
+ * iamx_brute_select, one workgroup per pair, over mask / status of iamx_verify_pairs:
+ *   distance bins 0..40 in order, within each the angle bins 0..20 in order.  A looked-at cell's
+ *   num_fit is its inlier count (0 where status != IAMX_VERIFY_OK); best_of_bin the largest num_fit of
+ *   the distance bin (0 without a looked-at cell); a cell with num_fit strictly above the best so far
+ *   (0 at the start) becomes the pair's list -- the comparison is on FITTED inliers, not unique ones,
+ *   unlike iamx_ratio_select.  After each distance bin the walk stops at best > 50 && best_of_bin <
+ *   10.  After the walk: the taken cell's inliers in order if they are at least min_pairs, through
+ *   filter_duplicates (as for iamx_ratio_select), kept if at least min_pairs remain, else empty.
+ *   chosen DEV [n_pairs]: the taken cell dbin * 21 + abin, or -1.  stats DEV [n_pairs][4] = fitted
+ *   (the best; 0 without a taken cell), unique (-1 where filter_duplicates did not run), distance bins
+ *   walked, cells looked at within them.  fit_cnt DEV [n_pairs][861]: num_fit, -1 where the cell is
+ *   not looked at or not reached.  out_slots / out_cnt / out_off / out_rows / out_cap, stride,
+ *   tab_size, work as for iamx_ratio_select.
+ * Null pointers, negative counts, a step, stride or tab_size out of range: IAMX_EINVAL without a
+ * launch; n_pairs == 0: IAMX_OK without one, and nothing is written (out_off[0] included).
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_BRUTE_DIST_BINS 41
+#define IAMX_BRUTE_ANGLE_BINS 21
+#define IAMX_BRUTE_CELLS 861
+int iamx_brute_bins(const int32_t *idx, const int32_t *d2, const int64_t *row_off,
+                    const int32_t *pairs, const int64_t *kp_off, const float *xy, const float *size,
+                    int n_pairs, double match_ratio, double min_pairs, double step_d, double step_a,
+                    int64_t cap, int32_t *bin_cnt, int32_t *seg_cnt, int64_t *seg_off, float *pts,
+                    int32_t *rows, int32_t *flag, void *stream);
+int iamx_brute_select(const int32_t *pairs, const int64_t *kp_off, const int32_t *key2, int n_pairs,
+                      double min_pairs, const int32_t *seg_cnt, const int64_t *seg_off,
+                      const int32_t *rows, const uint8_t *mask, const int32_t *vstatus, int64_t cap,
+                      int stride, int tab_size, int32_t *work, int32_t *out_slots, int32_t *out_cnt,
+                      int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *chosen,
+                      int32_t *stats, int32_t *fit_cnt, int32_t *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
