@@ -2242,3 +2242,85 @@ def colour_lut(img, lut, mask=None):
             torch.cuda.current_stream().synchronize()  # (the uploads' staging copies have been read)
         return out
     return out.cpu().numpy()
+
+
+# --------------------------------------------------------------------------------------
+# surface-consistency and depth culls of chains (csrc/chain_surface.hip)
+# --------------------------------------------------------------------------------------
+SURFACE_MAX_K = 32                                                 # IAMX_SURFACE_MAX_K
+SURFACE_FITTED, SURFACE_SKIPPED_SMALL, SURFACE_SKIPPED_FLAT = 1, 2, 3
+SURFACE_N_SMALL, SURFACE_N_FLAT, SURFACE_N_UNCOUNTED, SURFACE_N_LOOKED = range(4)
+CHAIN_STATS_TILE = 256                                             # IAMX_CHAIN_STATS_TILE
+STATS_AVERAGE, STATS_STDDEV, STATS_N, STATS_BAND = range(4)
+
+
+def surface_knn_fit(img_ptr, uv, ned, chain, k=30, n_pos=10):
+    """The observation table (device tensors: img_ptr i64 [n_images + 1], uv f64 [n_obs, 2], ned f64
+    [n_obs, 3], chain i32 [n_obs]) -> device (tgt i32 [n_obs, k], val f64 [n_obs, k], used i32,
+    fit f64 [n_obs, 2], status i32).  Enqueued on the current stream, no synchronisation."""
+    dev = require_gpu()
+    n_obs, n_images = chain.numel(), img_ptr.numel() - 1
+    m = max(n_obs, 1)
+    tgt = torch.empty((m, k), dtype=I32, device=dev)
+    val = torch.empty((m, k), dtype=F64, device=dev)
+    used = torch.empty(m, dtype=I32, device=dev)
+    fit = torch.empty((m, 2), dtype=F64, device=dev)
+    status = torch.empty(m, dtype=I32, device=dev)
+    check(lib().iamx_surface_knn_fit(_ptr(img_ptr), _ptr(uv), _ptr(ned), _ptr(chain), n_images, n_obs,
+                                     int(k), int(n_pos), _ptr(tgt), _ptr(val), _ptr(used), _ptr(fit),
+                                     _ptr(status), stream_ptr()), 'iamx_surface_knn_fit')
+    return tgt[:n_obs], val[:n_obs], used[:n_obs], fit[:n_obs], status[:n_obs]
+
+
+def surface_chain_metric(tgt, val, status, looked, n_chains):
+    """-> device (sum f64 [n_chains], count i32, metric f64, counters i64 [4]: SURFACE_N_*)."""
+    dev = require_gpu()
+    n_obs, k = tgt.shape
+    m = max(n_chains, 1)
+    total = torch.empty(m, dtype=F64, device=dev)
+    count = torch.empty(m, dtype=I32, device=dev)
+    metric = torch.empty(m, dtype=F64, device=dev)
+    counters = torch.zeros(4, dtype=I64, device=dev)
+    off = torch.empty(m + 1, dtype=I64, device=dev)
+    order = torch.empty(max(n_obs * k, 1), dtype=I32, device=dev)
+    check(lib().iamx_surface_chain_metric(_ptr(tgt), _ptr(val), _ptr(status), n_obs, k, _ptr(looked),
+                                          n_chains, _ptr(total), _ptr(count), _ptr(metric), _ptr(counters),
+                                          _ptr(off), _ptr(order), stream_ptr()), 'iamx_surface_chain_metric')
+    return total[:n_chains], count[:n_chains], metric[:n_chains], counters
+
+
+def chain_outlier_stats(metric, looked, factor, two_sided):
+    """-> device (stats f64 [4]: STATS_*, flag u8 [n], idx i32 [n], metric of idx f64 [n], n_flagged
+    i64 [1]); the first n_flagged entries of idx are the flagged chains in ascending order."""
+    dev = require_gpu()
+    n = metric.numel()
+    m = max(n, 1)
+    tiles = (m + CHAIN_STATS_TILE - 1) // CHAIN_STATS_TILE
+    stats = torch.zeros(4, dtype=F64, device=dev)
+    flag = torch.zeros(m, dtype=U8, device=dev)
+    idx = torch.empty(m, dtype=I32, device=dev)
+    sel = torch.empty(m, dtype=F64, device=dev)
+    n_flagged = torch.zeros(1, dtype=I64, device=dev)
+    part = torch.empty(tiles, dtype=F64, device=dev)
+    cnt = torch.empty(tiles, dtype=I32, device=dev)
+    off = torch.empty(tiles + 1, dtype=I64, device=dev)
+    check(lib().iamx_chain_outlier_stats(_ptr(metric), _ptr(looked), n, float(factor), int(bool(two_sided)),
+                                         _ptr(stats), _ptr(flag), _ptr(idx), _ptr(sel), _ptr(n_flagged),
+                                         _ptr(part), _ptr(cnt), _ptr(off), stream_ptr()),
+          'iamx_chain_outlier_stats')
+    return stats, flag[:n], idx[:n], sel[:n], n_flagged
+
+
+def chain_depths(img_ptr, ned, pos, chain_ptr, chain_obs):
+    """-> device (depth f64 [n_obs], z f64 [n_images, 3] = mean, deviation, count, metric f64
+    [n_chains], looked u8 [n_chains])."""
+    dev = require_gpu()
+    n_obs, n_images, n_chains = ned.shape[0], img_ptr.numel() - 1, chain_ptr.numel() - 1
+    depth = torch.empty(max(n_obs, 1), dtype=F64, device=dev)
+    z = torch.zeros((max(n_images, 1), 3), dtype=F64, device=dev)
+    metric = torch.zeros(max(n_chains, 1), dtype=F64, device=dev)
+    looked = torch.zeros(max(n_chains, 1), dtype=U8, device=dev)
+    check(lib().iamx_chain_depths(_ptr(img_ptr), _ptr(ned), n_images, n_obs, _ptr(pos), _ptr(chain_ptr),
+                                  _ptr(chain_obs), n_chains, _ptr(depth), _ptr(z), _ptr(metric),
+                                  _ptr(looked), stream_ptr()), 'iamx_chain_depths')
+    return depth[:n_obs], z[:n_images], metric[:n_chains], looked[:n_chains]

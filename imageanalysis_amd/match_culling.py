@@ -26,6 +26,19 @@ New, for the 4b-colocated-feats.py twin (imageanalysis_amd/scripts/4b-colocated-
         than min_angle degrees, in the reference's order: one pass of iamx_chain_pair_angles, the
         per-member counts come back and are unrolled on the host
 
+New, for the 4c-surface-outliers.py and 4c-by-depth.py twins (the rules: include/iamx.h):
+
+    surface_consistency(proj, matches, group_list, group_index, k=30, positives=10, alive=None)
+        -> SurfaceReport: per chain the mean misfit of its members against the line of 3-D over
+        pixel distance that each of their image neighbours fits (iamx_surface_knn_fit,
+        iamx_surface_chain_metric); the arrays stay on the device
+    surface_outliers(report, stddev=5) -> (chains by descending |metric|, average, deviation)
+    cull_surface(proj, matches, group_list, group_index, stddev=5, max_rounds=None) -> rounds
+        the reference's `while result > 0` loop on an alive mask; every member of a culled chain
+        is marked at the end
+    depth_outliers(proj, matches, group_list, group_index, stddev=3) -> (mark list, image rows)
+    weak_images(matches, n_images, min_features=25) -> mark list (host)
+
 `matches` is the reference's list of `[ned, group, [image, [u, v]], ...]` chains, or the
 array-backed match_cleanup.Chains: marks on an untouched Chains are kept in a member mask
 (`chains.marked`) and delete_marked_features() rebuilds its arrays with numpy.
@@ -52,8 +65,9 @@ def _arrays(matches):
     return isinstance(matches, Chains) and matches.untouched()
 
 
-def mark_feature(matches, match_index, feat_index, error):
-    print('  outlier - match index:', match_index, 'feature index:', feat_index, 'error:', error)
+def mark_feature(matches, match_index, feat_index, error, quiet=False):
+    if not quiet:
+        print('  outlier - match index:', match_index, 'feature index:', feat_index, 'error:', error)
     if _arrays(matches):
         lo, hi = int(matches.ptr[match_index]), int(matches.ptr[match_index + 1])
         if not 0 <= feat_index < hi - lo:
@@ -299,6 +313,215 @@ def colocated_features(proj, matches, group_list, group_index, min_angle):
     mark_list = marks_from_counts(ptr, d_count[:len(img)].cpu().numpy())
     assert len(mark_list) == int(d_total.item())
     return mark_list
+
+
+# ---------------------------------------------------------------------------------------------
+# surface consistency and depth (the reference's 4c-surface-outliers3.py and 4c-by-depth.py; the
+# rules are stated in include/iamx.h and DESIGN.md section 4, restated by tests/surface_cull_restatement.py)
+# ---------------------------------------------------------------------------------------------
+class ObservationTable(object):
+    """host arrays: img_ptr i64 [n_images + 1], uv [n_obs, 2], ned [n_obs, 3], chain i32 [n_obs]
+    (image-major: a stable sort of the looked-at chains' in-group members by image), chain_ptr i64
+    [n_chains + 1] / chain_obs i32 [n_obs] (each chain's observations in member order), looked bool
+    [n_chains]; after upload() the same names with a d_ prefix are device tensors."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def upload(self):
+        import torch
+        from . import kernels
+        dev = kernels.require_gpu()
+        for name in ('img_ptr', 'uv', 'ned', 'chain', 'chain_ptr', 'chain_obs'):
+            setattr(self, 'd_' + name, torch.from_numpy(np.ascontiguousarray(getattr(self, name))).to(dev))
+        self.d_looked = torch.from_numpy(self.looked.astype(np.uint8)).to(dev)
+        return self
+
+
+def observation_table(proj, matches, group_list, group_index, alive=None, min_members=1):
+    """The members of the looked-at chains (group tag == group_index, alive, and at least
+    `min_members` members in the group) whose image is in the group.  A looked-at chain without a
+    position raises ValueError, an image index outside the project IndexError."""
+    from . import match_cleanup
+    if not 0 <= group_index < len(group_list):
+        raise IndexError("group %d of %d" % (group_index, len(group_list)))
+    n_img = len(proj.image_list)
+    ptr, img, uv, group, ned, has_ned = match_cleanup.chain_arrays(matches)
+    n = len(ptr) - 1
+    looked = group == group_index
+    if alive is not None:
+        looked = looked & np.asarray(alive, bool)
+    missing = np.nonzero(looked & ~has_ned)[0]
+    if len(missing):
+        raise ValueError("chain %d of group %d has no position (match[0] is None): triangulate the "
+                         "chains before culling them by surface or depth" % (int(missing[0]), group_index))
+    chain_of = np.repeat(np.arange(n), np.diff(ptr))
+    sel = looked[chain_of]
+    bad = np.nonzero(sel & ((img < 0) | (img >= n_img)))[0]
+    if len(bad):
+        raise IndexError("observation_table: chain %d refers to image %d, the project has %d images"
+                         % (int(chain_of[bad[0]]), int(img[bad[0]]), n_img))
+    in_group = match_cleanup.group_membership(proj, group_list, group_index).astype(bool)
+    sel = sel & in_group[np.where(sel, img, 0)] if n_img else np.zeros(len(img), bool)
+    if min_members > 1:
+        looked = looked & (np.bincount(chain_of[sel], minlength=n) >= min_members)
+        sel = sel & looked[chain_of]
+    members = np.nonzero(sel)[0]
+    order = np.argsort(img[members], kind='stable')
+    obs = members[order]
+    img_ptr = np.zeros(n_img + 1, np.int64)
+    np.cumsum(np.bincount(img[members], minlength=n_img), out=img_ptr[1:])
+    chain_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(chain_of[members], minlength=n), out=chain_ptr[1:])
+    chain_obs = np.zeros(len(members), np.int32)
+    chain_obs[order] = np.arange(len(members), dtype=np.int32)
+    chain = chain_of[obs].astype(np.int32)
+    return ObservationTable(img_ptr=img_ptr, uv=np.ascontiguousarray(uv[obs]), ned=np.ascontiguousarray(ned[chain]),
+                            chain=chain, chain_ptr=chain_ptr, chain_obs=chain_obs, looked=looked,
+                            n_chains=n, n_images=n_img)
+
+
+class SurfaceReport(object):
+    """metric f64 / count i32 / looked u8 [n_chains] (device tensors), n_small and n_flat (queries
+    skipped because their image has fewer than 3 observations / no neighbour at a distance),
+    n_uncounted (looked-at chains nobody addressed: the reference's "count is zero"), n_looked,
+    table (the ObservationTable)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def surface_consistency(proj, matches, group_list, group_index, k=30, positives=10, alive=None):
+    """One pass of the reference's compute_surface_outliers() up to its metric: every observation's
+    nearest neighbours in its image, the line of 3-D over pixel distance through them, and per chain
+    the mean misfit of the neighbours that are its members (iamx_surface_knn_fit,
+    iamx_surface_chain_metric).  One synchronisation, for the four counts."""
+    from . import kernels
+    if not (1 <= k <= kernels.SURFACE_MAX_K and 1 <= positives <= kernels.SURFACE_MAX_K):
+        raise ValueError("k and positives must be within 1..%d" % kernels.SURFACE_MAX_K)
+    table = observation_table(proj, matches, group_list, group_index, alive).upload()
+    tgt, val, _used, _fit, status = kernels.surface_knn_fit(table.d_img_ptr, table.d_uv, table.d_ned,
+                                                            table.d_chain, k, positives)
+    _sum, count, metric, counters = kernels.surface_chain_metric(tgt, val, status, table.d_looked,
+                                                                 table.n_chains)
+    c = counters.cpu().numpy()                                             # the one synchronisation
+    return SurfaceReport(metric=metric, count=count, looked=table.d_looked, table=table,
+                         n_small=int(c[kernels.SURFACE_N_SMALL]), n_flat=int(c[kernels.SURFACE_N_FLAT]),
+                         n_uncounted=int(c[kernels.SURFACE_N_UNCOUNTED]),
+                         n_looked=int(c[kernels.SURFACE_N_LOOKED]))
+
+
+def outlier_stats(metric, looked, factor, two_sided):
+    """iamx_chain_outlier_stats -> host (flagged chains ascending, their metric, average, stddev)"""
+    from . import kernels
+    stats, _flag, idx, sel, n_flagged = kernels.chain_outlier_stats(metric, looked, factor, two_sided)
+    s = stats.cpu().numpy()
+    n = int(n_flagged.item())
+    return (idx[:n].cpu().numpy().astype(np.int64), sel[:n].cpu().numpy(),
+            float(s[kernels.STATS_AVERAGE]), float(s[kernels.STATS_STDDEV]))
+
+
+def surface_outliers(report, stddev=5):
+    """-> (chains with |average - metric| >= stddev * deviation by descending |metric|, ties in chain
+    order: the reference's sorted report; average; deviation)"""
+    idx, sel, average, dev = outlier_stats(report.metric, report.looked, stddev, True)
+    order = np.argsort(-np.abs(sel), kind='stable')
+    return idx[order], average, dev
+
+
+def cull_surface(proj, matches, group_list, group_index, stddev=5, max_rounds=None, k=30, positives=10):
+    """The reference's `while result > 0` loop: rounds of surface_consistency / surface_outliers on
+    an alive mask (a culled chain leaves the observation table; `matches` is not edited between
+    rounds), then every member of every culled chain is marked, so that
+    delete_marked_features(matches, min_chain_len) removes the chain.  -> the chains culled per
+    round (a last empty list when the loop ended by itself)."""
+    alive = np.ones(len(matches), bool)
+    rounds = []
+    while max_rounds is None or len(rounds) < max_rounds:
+        report = surface_consistency(proj, matches, group_list, group_index, k, positives, alive)
+        idx, average, dev = surface_outliers(report, stddev)
+        print("average value = %.2f" % average)
+        print("standard deviation = %.2f" % dev)
+        print("round %d: culled %d chains (skipped: %d observations in images with < 3, %d without a "
+              "distant neighbour; %d chains never a neighbour)"
+              % (len(rounds) + 1, len(idx), report.n_small, report.n_flat, report.n_uncounted))
+        rounds.append([int(c) for c in idx])
+        if len(idx) == 0:
+            break
+        alive[idx] = False
+    for c in sorted(c for r in rounds for c in r):
+        if _arrays(matches):                       # (indexing a Chains would turn it into lists)
+            members = int(matches.ptr[c + 1] - matches.ptr[c])
+        else:
+            members = len(matches[c]) - 2
+        for j in range(members):
+            mark_feature(matches, c, j, "-", quiet=True)
+    return rounds
+
+
+class DepthReport(object):
+    """metric f64 / looked u8 [n_chains] (device tensors), z: host [n_images, 3] = mean, population
+    deviation and count of each image's depths, table (the ObservationTable)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def chain_depths(proj, matches, group_list, group_index):
+    """scripts/4c-by-depth.py's compute_feature_depths(): chains of the group with at least two
+    members in it; per member the distance from its camera (camera_pose_opt) to the chain's position,
+    per image their mean and deviation, per chain the mean |depth - image mean| (iamx_chain_depths)."""
+    import torch
+    from . import kernels
+    table = observation_table(proj, matches, group_list, group_index, min_members=2).upload()
+    pos = np.zeros((table.n_images, 3))
+    for i, image in enumerate(proj.image_list):
+        pos[i] = image.get_camera_pose(opt=True)[0]
+    d_pos = torch.from_numpy(pos).to(table.d_ned.device)
+    _depth, z, metric, looked = kernels.chain_depths(table.d_img_ptr, table.d_ned, d_pos, table.d_chain_ptr,
+                                                     table.d_chain_obs)
+    return DepthReport(metric=metric, looked=looked, z=z.cpu().numpy(), table=table)
+
+
+def depth_outliers(proj, matches, group_list, group_index, stddev=3):
+    """-> (mark list [[chain, 0], ...] of the chains whose metric > mean + stddev * deviation, by
+    descending metric, ties in chain order; per-image rows (name, count, avg, std), avg and std None
+    for an image without depths).  Member 0 is what the reference marks: its rows are
+    [metric_avg, i, 0]."""
+    report = chain_depths(proj, matches, group_list, group_index)
+    rows = [(image.name, int(z[2]), float(z[0]) if z[2] else None, float(z[1]) if z[2] else None)
+            for image, z in zip(proj.image_list, report.z)]
+    print("Marking outliers...")
+    print(" computing stats...")
+    idx, sel, mean, dev = outlier_stats(report.metric, report.looked, stddev, False)
+    print("mean = %.4f stddev = %.4f" % (mean, dev))
+    order = np.argsort(-sel, kind='stable')
+    return [[int(c), 0] for c in idx[order]], rows
+
+
+def weak_images(matches, n_images, min_features=25):
+    """scripts/4c-by-depth.py's weak-image rule: [chain, member] of every unmarked member that lies
+    in an image holding between 1 and min_features - 1 unmarked members."""
+    if _arrays(matches):
+        img = matches.img
+        if len(img) and (img.min() < 0 or img.max() >= n_images):
+            raise IndexError("weak_images: an image index outside the project's %d images" % n_images)
+        live = ~_marks(matches)
+        count = np.bincount(img[live], minlength=n_images)
+        weak = (count > 0) & (count < min_features)
+        hit = np.nonzero(live & weak[img])[0]
+        chain = np.searchsorted(matches.ptr, hit, side='right') - 1
+        return np.stack([chain, hit - matches.ptr[chain]], 1).tolist() if len(hit) else []
+    count = [0] * n_images
+    for match in matches:
+        for p in match[2:]:
+            if p != MARK:
+                if not 0 <= p[0] < n_images:
+                    raise IndexError("weak_images: an image index outside the project's %d images" % n_images)
+                count[p[0]] += 1
+    weak = set(i for i, n in enumerate(count) if 0 < n < min_features)
+    return [[c, j] for c, match in enumerate(matches) for j, p in enumerate(match[2:])
+            if p != MARK and p[0] in weak]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1312,6 +1312,86 @@ int iamx_chain_pair_angles(const int64_t *ptr, const int32_t *img, const int32_t
                            int64_t *total, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Surface-consistency and depth culls of chains (csrc/chain_surface.hip) -- the rules of the
+ * reference's scripts/4c-surface-outliers3.py and scripts/4c-by-depth.py.  All arithmetic is f64,
+ * every product and sum rounded on its own, sums left to right in the stated order; no
+ * floating-point atomics, so no result depends on the launch geometry or differs between runs.
+ * Pinned to tests/surface_cull_restatement.py.  All pointers DEV.  Null, size and range checks
+ * return IAMX_EINVAL without a GPU; n == 0 returns 0 without a launch.
+ *
+ * The observation table (built by match_culling.observation_table): the members of the looked-at
+ * chains whose image is in the group, image-major (a stable sort of the flattened member order by
+ * image index): img_ptr [n_images + 1] i64, uv [n_obs][2] f64 (stored, distorted pixels), ned
+ * [n_obs][3] f64 (the chain's position), chain [n_obs] i32.
+ *
+ * iamx_surface_knn_fit: per image with n observations (1 <= k, n_pos <= IAMX_SURFACE_MAX_K):
+ *   n < 3: used = 0, status _SKIPPED_SMALL for each of its observations.  Otherwise per query i:
+ *   d2[j] = du*du + dv*dv over the image's observations; the first min(k, n) in ascending (d2, j);
+ *   walked in that order with positives = 0: a neighbour with d2 > 0 first adds 1 to positives, and
+ *   positives > n_pos ends the walk in front of it; every other neighbour is used (the query itself
+ *   and every duplicate pixel included).  For the m used neighbours in walk order x = sqrt(d2),
+ *   y = sqrt((dx*dx + dy*dy) + dz*dz) of the two positions; xm = sum x / m, ym = sum y / m,
+ *   sxx = sum (x - xm)^2, sxy = sum (x - xm)(y - ym).  sxx == 0 (or NaN): status _SKIPPED_FLAT,
+ *   used = 0.  Otherwise a = sxy / sxx, b = ym - a*xm, fit = {a, b}, status _FITTED, used = m and
+ *   slot s gets tgt = chain[j], val = |(a*x + b) - y|.  Slots from `used` on get tgt = -1,
+ *   val = 0; a skipped query's fit is {0, 0}.  tgt [n_obs][k] i32, val [n_obs][k] f64, used
+ *   [n_obs] i32, fit [n_obs][2] f64, status [n_obs] i32.  n_obs * k must fit 31 bits.
+ *
+ * iamx_surface_chain_metric: per chain c < n_chains: sum[c] = the val of the slots with tgt == c
+ *   added in ascending (observation, slot) order, count[c] their number, metric[c] = sum / count
+ *   (0 when count is 0); a tgt outside [0, n_chains) addresses nobody.  counters [4] i64:
+ *   _N_SMALL / _N_FLAT (observations of that status), _N_UNCOUNTED (chains with looked[c] and
+ *   count 0), _N_LOOKED.  n_chains == 0: no launch; n_obs == 0: zeros are written.  work_off
+ *   [n_chains + 1] i64, work_order [n_obs * k] i32.
+ *
+ * iamx_chain_outlier_stats: over the chains with looked[c], n of them: average = sum metric / n,
+ *   stddev = sqrt(sum (average - metric)^2 / n), both sums by a fixed tree (tiles of
+ *   IAMX_CHAIN_STATS_TILE chains folded pairwise, the tiles folded by one workgroup); flag[c] =
+ *   |average - metric| >= factor*stddev with two_sided, metric > average + factor*stddev without;
+ *   stddev == 0 and n == 0 (average = stddev = 0) flag nothing.  stats [4] f64 (_AVERAGE, _STDDEV,
+ *   _N, _BAND = factor*stddev), flag [n_chains] u8, out_idx / out_metric [n_chains]: the flagged
+ *   chains in ascending order with their metric, n_flagged [1] i64.  work_part f64, work_cnt i32
+ *   [ceil(n_chains / tile)], work_off i64 [that + 1].
+ *
+ * iamx_chain_depths: depth[o] = sqrt((dx*dx + dy*dy) + dz*dz) of ned[o] - pos[image of o]; z
+ *   [n_images][3] = mean, population deviation and count of the image's depths (fixed tree; an
+ *   image without observations: zeros); chain_ptr [n_chains + 1] i64 / chain_obs [n_obs] i32: the
+ *   observations of each chain in member order; a chain with >= 2 of them: looked = 1, metric =
+ *   the mean over them, left to right, of |depth - z mean of the image|; any other: looked = 0,
+ *   metric = 0.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_SURFACE_MAX_K 32
+#define IAMX_SURFACE_FITTED 1
+#define IAMX_SURFACE_SKIPPED_SMALL 2
+#define IAMX_SURFACE_SKIPPED_FLAT 3
+#define IAMX_SURFACE_N_SMALL 0
+#define IAMX_SURFACE_N_FLAT 1
+#define IAMX_SURFACE_N_UNCOUNTED 2
+#define IAMX_SURFACE_N_LOOKED 3
+#define IAMX_SURFACE_N_COUNTERS 4
+#define IAMX_CHAIN_STATS_TILE 256
+#define IAMX_STATS_AVERAGE 0
+#define IAMX_STATS_STDDEV 1
+#define IAMX_STATS_N 2
+#define IAMX_STATS_BAND 3
+int iamx_surface_knn_fit(const int64_t *img_ptr, const double *uv, const double *ned,
+                         const int32_t *chain, int n_images, int64_t n_obs, int k, int n_pos,
+                         int32_t *tgt, double *val, int32_t *used, double *fit, int32_t *status,
+                         void *stream);
+int iamx_surface_chain_metric(const int32_t *tgt, const double *val, const int32_t *status,
+                              int64_t n_obs, int k, const uint8_t *looked, int64_t n_chains,
+                              double *sum, int32_t *count, double *metric, int64_t *counters,
+                              int64_t *work_off, int32_t *work_order, void *stream);
+int iamx_chain_outlier_stats(const double *metric, const uint8_t *looked, int64_t n_chains,
+                             double factor, int two_sided, double *stats, uint8_t *flag,
+                             int32_t *out_idx, double *out_metric, int64_t *n_flagged,
+                             double *work_part, int32_t *work_cnt, int64_t *work_off, void *stream);
+int iamx_chain_depths(const int64_t *img_ptr, const double *ned, int n_images, int64_t n_obs,
+                      const double *pos, const int64_t *chain_ptr, const int32_t *chain_obs,
+                      int64_t n_chains, double *depth, double *z, double *metric, uint8_t *looked,
+                      void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Orthomosaic raster (csrc/ortho_raster.hip): the textured surface grids of Step 5 composed
  * top-down into one raster of H x W pixels, row 0 north.  The rules (polygons, exact coverage,
  * texture coordinate, sample, the two composition modes) are stated once in
