@@ -1,0 +1,435 @@
+"""Dense surface: plane-sweep depth maps of a group's images and a DSM raster fused from them, the
+third stage beside the Step 5 map and the orthomosaic (the reference has no counterpart: its
+surface is the sparse chains' Delaunay triangulation).
+
+    views_from_project(proj, group_list, group_index, matches, scale)   the group's views
+    choose_neighbours(matches, group, poses, n=4)        per image, the images to sweep against
+    depth_range(matches, group, poses)                   per image, (z_near, z_far) from its chains
+    depth_maps(views, neighbours, ranges, planes=64, ...)   sweep every view, cross-check -> DepthMaps
+    fuse(views, depths, gsd)                             surviving points -> Surface (dsm, count)
+    save(surface, analysis_dir, points=None)             dense/dsm.npy, count.npy, dsm.wld, dense.json
+
+The kernels are csrc/dense_sweep.hip; tests/dense_restatement.py restates the rules below in numpy,
+operation by operation, and the device result is held to it bit for bit.
+
+THE RULES
+
+View: one image at the sweep scale.  G, a float32 grey plane h x w (the same size for every view of
+a call); K = (fx, fy, cx, cy) at that scale; dist, the five OpenCV coefficients (k1, k2, p1, p2, k3),
+unchanged by scale; R, NED -> camera, float64 3 x 3; C, the camera centre in NED; rays [h][w][2], the
+undistorted normalised coordinates (xn, yn) of the pixel centres (x, y integer), computed on the
+device by undistort.undistort_points.
+
+Geometry is float64, every product and sum rounded on its own, sums of three from the left.  Depth is
+the reference camera's z.  The planes are fronto-parallel and uniform in inverse depth:
+    step = (w_near - w_far) / (D - 1)   (0 for D = 1)      w_d = w_far + d step      z_d = 1 / w_d
+
+Warp of reference pixel q to neighbour n on plane d:
+    Xc = (xn z_d, yn z_d, z_d)
+    Xw_i = ((Rr[0][i] Xc_0 + Rr[1][i] Xc_1) + Rr[2][i] Xc_2) + Cr_i                 (Rr^T Xc + Cr)
+    D = Xw - Cn,  Xn_i = (Rn[i][0] D_0 + Rn[i][1] D_1) + Rn[i][2] D_2
+    x = Xn_0 / Xn_2, y = Xn_1 / Xn_2, and synth.project's expressions as Python reads them:
+    r2 = x x + y y;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+    xd = x rad + 2 p1 x y + p2 (r2 + 2 x x);  yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y
+    fx_ = fx xd + cx,  fy_ = fy yd + cy                                          (K of n)
+The sample is valid iff Xn_2 > 0 and 0 <= fx_ <= w - 1 and 0 <= fy_ <= h - 1 (comparisons that a NaN
+fails: anything not finite on the way is invalid).  Its value is bilinear in float32:
+    x0 = floor(fx_), x1 = min(x0 + 1, w - 1), tx = float32(fx_ - x0); y likewise
+    top = G[y0][x0] + (G[y0][x1] - G[y0][x0]) tx;  bot on row y1;  Wv = top + (bot - top) ty
+It depends on (q, d, n) only: every window that contains q sees the same value.
+
+Score of (p, d, n), float32, over the window of radius r (N = (2r+1)^2 pixels, row-major, every sum
+started at the first pixel and taken in that order): invalid when the window leaves the reference
+image or one of its warped samples is invalid.  With a the reference's and b the warped values,
+    ma = (sum a) / N, mb = (sum b) / N                          correctly rounded quotients
+    saa = sum (a - ma)^2, sbb = sum (b - mb)^2, sab = sum (a - ma)(b - mb)
+    invalid unless saa >= min_var N                             (float32 product; the texture gate)
+    den = float32(sqrt(float64(saa sbb)))                       the product rounded to float32 first
+    invalid when den == 0;  s = sab / den, invalid when it is NaN
+Aggregate: S_d(p) = (the float32 sum of the valid s in neighbour order) / their count, invalid
+without one.
+
+Winner: the largest S_d, the smallest d on a tie; best = -1 where every plane is invalid.  s_0 is
+its score, s_m and s_p those of planes best - 1 and best + 1 (NaN where the plane does not exist or
+is invalid).  In float32, when s_m and s_p are both valid and den = (s_m - 2 s_0) + s_p < 0:
+off = (0.5 (s_m - s_p)) / den clamped to +-0.5, else off = 0.  In float64
+    depth = float32(1 / (w_far + (best + off) step))
+A pixel is kept iff best >= 0 and s_0 >= min_score; depth is NaN where it is not.  Outputs: plane
+int32, score = s_0 (NaN for best = -1), depth, around = (s_m, s_0, s_p).  A NaN is 0x7fc00000.
+
+Consistency (dense_check), float64.  A pixel of view i with a depth z becomes the NED point
+Ri^T (xn z, yn z, z) + Ci (expressions as above).  For each neighbour j it is projected into j
+(as above, with j's K): z' = its depth there, (u, v) its pixel; the neighbour agrees iff z' > 0,
+rint(u) and rint(v) (half to even) lie inside the image, j's depth map has a depth z_j there and
+|z' - z_j| <= eps z'.  The pixel survives with at least min(min_agree, neighbours of i) agreeing
+neighbours; a view without neighbours keeps nothing.
+
+Fusion (dense_splat).  The raster frame follows ortho.raster_frame over the surviving points' ENU
+bounds (host): x0 = floor(min east / gsd) gsd, y1 = ceil(max north / gsd) gsd,
+W = max(1, ceil((max east - x0) / gsd)), H likewise; a point exactly on the east or south bound
+falls outside the last cell and is dropped, as every point outside the frame is.  A point lands in
+cell (floor((y1 - north) / gsd), floor((east - x0) / gsd)).  Each cell holds an int32 count and an
+int64 sum of rint(up 1024), both kept by integer atomics only: the result does not depend on
+scheduling.  dsm = float32(sum / 1024 / count) in float64, NaN where count == 0.
+
+The grey plane of a project's frame (views_from_project): the decoded BGR frame through
+kernels.resize_area at the sweep scale (cv2's INTER_AREA), then the integer luma
+Y = (29 B + 150 G + 77 R + 128) >> 8, as float32.  K is scaled with the pixel-centre convention:
+sx = w / width, fx' = fx sx, cx' = (cx + 0.5) sx - 0.5, y likewise.
+"""
+import json
+import os
+from math import ceil, floor
+
+import numpy as np
+
+from . import _deps
+from ._deps import getNode
+
+NEIGHBOUR_RATIO = (0.05, 0.6)          # baseline over median chain depth
+RANGE_MARGIN = 0.1
+MAX_SIDE = 1 << 20
+
+
+class View(object):
+    """One image at the sweep scale (THE RULES).  G and rays numpy or device tensors."""
+    __slots__ = ('G', 'K', 'dist', 'R', 'C', 'rays', 'name')
+
+    def __init__(self, G, K, dist, R, C, rays=None, name=None):
+        self.G = G
+        self.K = np.asarray(K, np.float64).reshape(4)
+        self.dist = np.asarray(dist, np.float64).reshape(5)
+        self.R = np.asarray(R, np.float64).reshape(3, 3)
+        self.C = np.asarray(C, np.float64).reshape(3)
+        self.rays = rays
+        self.name = name
+
+
+class DepthMaps(object):
+    """depth_maps()'s result, device tensors: plane int32 / score float32 / depth float32 [V, h, w]
+    (the sweep's), keep uint8 [V, h, w] (kept and consistent), ned float64 [V, h, w, 3]."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class Surface(object):
+    """dsm float32 [H, W] (NaN: empty), count int32 [H, W] (device tensors); x0 = west side of
+    column 0, y1 = north side of row 0, gsd metres per cell (local ENU about ned_reference)."""
+
+    def __init__(self, dsm, count, x0, y1, gsd):
+        self.dsm, self.count, self.x0, self.y1, self.gsd = dsm, count, float(x0), float(y1), float(gsd)
+
+    @property
+    def shape(self):
+        return tuple(self.dsm.shape)
+
+
+# ---------------------------------------------------------------------------------------------
+# views
+# ---------------------------------------------------------------------------------------------
+def pixel_rays(K, dist, h, w):
+    """rays [h, w, 2] float64 (device): undistort.undistort_points at the pixel centres, (u - cx) / fx"""
+    import torch
+    from . import kernels, undistort
+    K = np.asarray(K, np.float64).reshape(4)
+    u, v = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
+    und = undistort.undistort_points(np.stack([u, v], 2).reshape(-1, 2), K, dist).astype(np.float64)
+    rays = np.stack([(und[:, 0] - K[2]) / K[0], (und[:, 1] - K[3]) / K[1]], 1).reshape(h, w, 2)
+    out = kernels._dev(rays, torch.float64)
+    torch.cuda.current_stream().synchronize()
+    return out
+
+
+def scaled_K(K, width, height, w, h):
+    """(fx, fy, cx, cy) of a width x height camera for its w x h image, pixel centres kept"""
+    K = np.asarray(K, np.float64)
+    fx, fy, cx, cy = (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else K.reshape(4)
+    sx, sy = w / float(width), h / float(height)
+    return np.array([fx * sx, fy * sy, (cx + 0.5) * sx - 0.5, (cy + 0.5) * sy - 0.5])
+
+
+def grey_plane(frame, scale):
+    """device BGR uint8 [H, W, 3] -> float32 [h, w]: kernels.resize_area, then the integer luma"""
+    import torch
+    from . import kernels
+    small = kernels.resize_area(frame, scale, scale) if scale != 1.0 else frame
+    s = small.to(torch.int32)
+    return ((29 * s[:, :, 0] + 150 * s[:, :, 1] + 77 * s[:, :, 2] + 128) >> 8).to(torch.float32).contiguous()
+
+
+def image_pose(image):
+    """(R NED -> camera, C) of an image's optimised pose"""
+    cam2body = image.get_cam2body() if hasattr(image, 'get_cam2body') else \
+        np.array([[0, 0, 1], [1, 0, 0], [0, 1, 0]], dtype=float)
+    R = np.linalg.inv(cam2body).dot(np.asarray(image.get_body2ned(opt=True), np.float64).T)
+    return R, np.asarray(image.get_camera_pose(opt=True)[0], np.float64)
+
+
+def group_indices(proj, group_list, group_index):
+    """the project indices of the group's images, in group order"""
+    if not 0 <= group_index < len(group_list):
+        raise IndexError("group %d of %d" % (group_index, len(group_list)))
+    index = {im.name: i for i, im in enumerate(proj.image_list)}
+    return [index[name] for name in group_list[group_index] if name in index]
+
+
+def views_from_project(proj, group_list, group_index, matches, scale, frames=None):
+    """The group's views at `scale` of the camera's size: optimised K, distortion and poses, the grey
+    planes from the decoded frames (histogram.frame_pass, in group order; frames=: ready device BGR
+    tensors instead).  -> (views, group) with group the images' project indices.  matches is not read
+    here: it rides along to choose_neighbours and depth_range."""
+    from . import histogram
+    camera = _deps.camera()
+    K = np.asarray(camera.get_K(optimized=True), np.float64)
+    dist = np.array(camera.get_dist_coeffs(optimized=True), np.float64).ravel()[:5]
+    width, height = camera.get_image_params()
+    group = group_indices(proj, group_list, group_index)
+    images = [proj.image_list[i] for i in group]
+    planes = []
+
+    def on_frames(batch):
+        for frame in batch:
+            planes.append(grey_plane(frame, scale))
+
+    if frames is not None:
+        on_frames(list(frames))
+    else:
+        histogram.frame_pass(images, want_hist=False, on_frames=on_frames)
+    if len(planes) != len(images):
+        raise RuntimeError("%d of %d frames arrived" % (len(planes), len(images)))
+    if not planes:
+        return [], group
+    h, w = planes[0].shape
+    Ks = scaled_K(K, width, height, w, h)
+    rays = pixel_rays(Ks, dist, h, w)
+    views = []
+    for im, G in zip(images, planes):
+        R, C = image_pose(im)
+        views.append(View(G, Ks, dist, R, C, rays=rays, name=im.name))
+    return views, group
+
+
+# ---------------------------------------------------------------------------------------------
+# neighbours and depth ranges from the sparse chains (host)
+# ---------------------------------------------------------------------------------------------
+def _observations(matches, group):
+    """the members of the positioned chains that lie in the group -> (chain number, position in
+    group, chain NED [n_obs, 3]), one row per (chain, image), an image counted once per chain"""
+    pos_of = {int(g): k for k, g in enumerate(group)}
+    chain, member, ned = [], [], []
+    for c, m in enumerate(matches):
+        if m[0] is None:
+            continue
+        seen = set()
+        for p in m[2:]:
+            k = pos_of.get(int(p[0]))
+            if k is not None and k not in seen:
+                seen.add(k)
+                chain.append(c)
+                member.append(k)
+                ned.append(m[0])
+    return (np.array(chain, np.int64), np.array(member, np.int64),
+            np.array(ned, np.float64).reshape(-1, 3))
+
+
+def _camera_depth(R, C, X):
+    """z of R (X - C), elementwise (no BLAS: the order of the sum is part of the result)"""
+    d = X - C
+    return (R[2, 0] * d[:, 0] + R[2, 1] * d[:, 1]) + R[2, 2] * d[:, 2]
+
+
+def choose_neighbours(matches, group, poses, n=4):
+    """Per image of the group (project indices; poses[k] = (R, C) of group[k]) the other images
+    ranked by the number of positioned chains they share with it (more first, the earlier image on a
+    tie), kept only where baseline / (median depth of the shared chains in the image's camera) lies in
+    NEIGHBOUR_RATIO, at most n.  -> a list of positions in the group per image."""
+    V = len(group)
+    if len(poses) != V:
+        raise ValueError("one pose per image of the group")
+    if n < 1:
+        raise ValueError("n is at least 1")
+    chain, member, ned = _observations(matches, group)
+    out = [[] for _ in range(V)]
+    if len(chain) == 0:
+        return out
+    # every ordered pair (i, j), i != j, of members of one chain
+    order = np.argsort(chain, kind='stable')
+    chain, member, ned = chain[order], member[order], ned[order]
+    start = np.nonzero(np.r_[True, chain[1:] != chain[:-1]])[0]
+    length = np.diff(np.r_[start, len(chain)])
+    first = np.repeat(start, length)                         # per observation: its chain's first row
+    size = np.repeat(length, length)
+    a = np.repeat(np.arange(len(chain)), size)               # observation a ...
+    b = np.repeat(first, size) + (np.arange(len(a)) - np.repeat(np.cumsum(size) - size, size))   # ... with each b
+    sel = a != b
+    a, b = a[sel], b[sel]
+    i, j = member[a], member[b]
+    depth = np.empty(len(a))
+    for k in range(V):
+        s = i == k
+        if s.any():
+            depth[s] = _camera_depth(poses[k][0], poses[k][1], ned[a[s]])
+    key = i * V + j
+    order = np.lexsort((depth, key))
+    key, depth = key[order], depth[order]
+    start = np.nonzero(np.r_[True, key[1:] != key[:-1]])[0]
+    count = np.diff(np.r_[start, len(key)])
+    lo, hi = start + (count - 1) // 2, start + count // 2
+    median = 0.5 * (depth[lo] + depth[hi])
+    pi, pj = key[start] // V, key[start] % V
+    Cs = np.array([p[1] for p in poses], np.float64).reshape(V, 3)
+    d = Cs[pi] - Cs[pj]
+    baseline = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio = baseline / median
+    ok = (median > 0) & (ratio >= NEIGHBOUR_RATIO[0]) & (ratio <= NEIGHBOUR_RATIO[1])
+    for k in range(V):
+        s = np.nonzero(ok & (pi == k))[0]
+        rank = s[np.lexsort((pj[s], -count[s]))]
+        out[k] = [int(x) for x in pj[rank][:n]]
+    return out
+
+
+def depth_range(matches, group, poses):
+    """Per image of the group (z_near, z_far): the camera depths of the positioned chains it observes,
+    those in front of it, (1 - RANGE_MARGIN) min and (1 + RANGE_MARGIN) max; None without one."""
+    V = len(group)
+    if len(poses) != V:
+        raise ValueError("one pose per image of the group")
+    chain, member, ned = _observations(matches, group)
+    out = [None] * V
+    for k in range(V):
+        s = member == k
+        if not s.any():
+            continue
+        z = _camera_depth(poses[k][0], poses[k][1], ned[s])
+        z = z[z > 0]
+        if len(z):
+            out[k] = ((1.0 - RANGE_MARGIN) * float(z.min()), (1.0 + RANGE_MARGIN) * float(z.max()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# depth maps and fusion (device)
+# ---------------------------------------------------------------------------------------------
+def depth_maps(views, neighbours, ranges, planes=64, radius=3, min_var=4.0, min_score=0.6, eps=0.01,
+               min_agree=2, check=True):
+    """Sweep every view against its neighbours (positions in `views`) over its range (z_near, z_far),
+    then the consistency rule over all maps (check=False: every kept pixel survives).  A view without
+    neighbours or without a range gets an empty map.  -> DepthMaps"""
+    import torch
+    from . import kernels
+    views = list(views)
+    V = len(views)
+    if V == 0:
+        raise ValueError("no views")
+    if len(neighbours) != V or len(ranges) != V:
+        raise ValueError("one neighbour list and one range per view")
+    kernels.dense_neighbour_table(neighbours, V)          # (checked before any device call)
+    h, w = kernels._dense_size(views)
+    for r in ranges:
+        if r is not None and not (0.0 < float(r[0]) < float(r[1]) < float('inf')):
+            raise ValueError("a range is 0 < z_near < z_far, got %r" % (r,))
+    dev = kernels.require_gpu()
+    plane = torch.full((V, h, w), -1, dtype=torch.int32, device=dev)
+    score = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
+    depth = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
+    around = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    for i, v in enumerate(views):
+        if ranges[i] is None or len(neighbours[i]) == 0:
+            continue
+        kernels.dense_sweep(v, [views[j] for j in neighbours[i]], 1.0 / float(ranges[i][1]), 1.0 / float(ranges[i][0]),
+                            planes, radius=radius, min_var=min_var, min_score=min_score,
+                            out=(plane[i], score[i], depth[i], around))
+    keep, ned = kernels.dense_check(depth, views, neighbours, eps=eps, min_agree=min_agree)
+    if not check:
+        keep = torch.isfinite(depth).to(torch.uint8)
+    return DepthMaps(plane=plane, score=score, depth=depth, keep=keep, ned=ned)
+
+
+def frame_of(east_min, east_max, north_min, north_max, gsd):
+    """ortho.raster_frame's frame for ENU bounds -> (x0, y1, W, H)"""
+    gsd = float(gsd)
+    if not (gsd > 0.0 and np.isfinite(gsd)):
+        raise ValueError("gsd must be a positive number of metres per cell")
+    x0 = floor(east_min / gsd) * gsd
+    y1 = ceil(north_max / gsd) * gsd
+    W = max(1, int(ceil((east_max - x0) / gsd)))
+    H = max(1, int(ceil((y1 - north_min) / gsd)))
+    if W > MAX_SIDE or H > MAX_SIDE:
+        raise ValueError("a %d x %d cell raster: a side above 2^20 cells is refused (gsd %g m)" % (W, H, gsd))
+    return x0, y1, W, H
+
+
+def fuse(views, depths, gsd):
+    """The surviving points of depth_maps()'s result into a DSM at `gsd` metres per cell.  -> Surface"""
+    import torch
+    from . import kernels
+    keep = depths.keep.reshape(-1).bool()
+    if not bool(keep.any()):
+        raise ValueError("no pixel survived: nothing to fuse")
+    pts = depths.ned.reshape(-1, 3)[keep]
+    lo, hi = pts.amin(dim=0).cpu().numpy(), pts.amax(dim=0).cpu().numpy()
+    x0, y1, W, H = frame_of(float(lo[1]), float(hi[1]), float(lo[0]), float(hi[0]), gsd)
+    count, _total, dsm = kernels.dense_splat(depths.ned, depths.keep, x0, y1, gsd, W, H)
+    return Surface(dsm, count, x0, y1, gsd)
+
+
+def surface_points(views, depths):
+    """the surviving points -> (xyz float32 [n, 3] east, north, up; intensity uint8 [n]) on the host"""
+    import torch
+    keep = depths.keep.bool()
+    ned = depths.ned[keep].cpu().numpy()
+    G = torch.stack([v.G if isinstance(v.G, torch.Tensor) else torch.from_numpy(np.asarray(v.G)).to(keep.device)
+                     for v in views])
+    grey = G[keep].clamp(0, 255).to(torch.uint8).cpu().numpy()
+    return np.stack([ned[:, 1], ned[:, 0], -ned[:, 2]], 1).astype(np.float32), grey
+
+
+def ply_bytes(xyz, intensity):
+    """binary little-endian PLY: x, y, z float32 and intensity uchar per vertex"""
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    intensity = np.asarray(intensity, np.uint8).reshape(-1)
+    if len(intensity) != len(xyz):
+        raise ValueError("one intensity per point")
+    rec = np.empty(len(xyz), dtype=[('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('i', 'u1')])
+    rec['x'], rec['y'], rec['z'], rec['i'] = xyz[:, 0], xyz[:, 1], xyz[:, 2], intensity
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+            "property float z\nproperty uchar intensity\nend_header\n" % len(xyz))
+    return head.encode('ascii') + rec.tobytes()
+
+
+def save(surface, analysis_dir, points=None):
+    """<analysis_dir>/dense/dsm.npy (float32, NaN: empty), count.npy (int32), dsm.wld (the world file
+    of the raster, local ENU metres, pixel-centre convention), dense.json; points = (xyz, intensity):
+    points.ply as well.  -> the json's dict"""
+    import io
+    from . import ortho, panda3d
+    out_dir = os.path.join(analysis_dir, 'dense')
+    os.makedirs(out_dir, exist_ok=True)
+    H, W = surface.shape
+    count = surface.count.cpu().numpy()
+
+    def npy(a):
+        buf = io.BytesIO()
+        np.save(buf, a)
+        return buf.getvalue()
+
+    panda3d._write_atomic(os.path.join(out_dir, 'dsm.npy'), npy(surface.dsm.cpu().numpy()))
+    panda3d._write_atomic(os.path.join(out_dir, 'count.npy'), npy(count))
+    panda3d._write_atomic(os.path.join(out_dir, 'dsm.wld'),
+                          ortho.world_file_text(surface.gsd, surface.x0, surface.y1).encode())
+    ref_node = getNode("/config/ned_reference", True)
+    info = {'ned_reference': {k: ref_node.getFloat(k) for k in ('lat_deg', 'lon_deg', 'alt_m')},
+            'units': 'local ENU metres about ned_reference; dsm is metres up', 'gsd': surface.gsd,
+            'width': W, 'height': H, 'cells_filled': int((count > 0).sum()), 'points_fused': int(count.sum()),
+            'bounds': {'west': surface.x0, 'east': surface.x0 + W * surface.gsd, 'north': surface.y1,
+                       'south': surface.y1 - H * surface.gsd},
+            'files': {'dsm': 'dsm.npy', 'count': 'count.npy', 'world_file': 'dsm.wld'}}
+    if points is not None:
+        panda3d._write_atomic(os.path.join(out_dir, 'points.ply'), ply_bytes(*points))
+        info['files']['points'] = 'points.ply'
+        info['points'] = int(len(points[0]))
+    panda3d._write_atomic(os.path.join(out_dir, 'dense.json'), (json.dumps(info, indent=2) + "\n").encode())
+    return info

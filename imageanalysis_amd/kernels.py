@@ -2324,3 +2324,152 @@ def chain_depths(img_ptr, ned, pos, chain_ptr, chain_obs):
                                   _ptr(chain_obs), n_chains, _ptr(depth), _ptr(z), _ptr(metric),
                                   _ptr(looked), stream_ptr()), 'iamx_chain_depths')
     return depth[:n_obs], z[:n_images], metric[:n_chains], looked[:n_chains]
+
+
+# --------------------------------------------------------------------------------------
+# dense surface (csrc/dense_sweep.hip; the rules: dense.py)
+# --------------------------------------------------------------------------------------
+DENSE_TILE = (32, 16)                    # a workgroup's reference pixels, (width, height)
+DENSE_MAX_RADIUS, DENSE_MAX_PLANES, DENSE_MAX_NEIGHBOURS, DENSE_MAX_SIDE = 7, 4096, 16, 16384
+
+
+def dense_camera(view):
+    """the 21 doubles of a view: R (row-major), C, fx, fy, cx, cy, k1, k2, p1, p2, k3"""
+    R = np.asarray(view.R, np.float64).reshape(9)
+    C = np.asarray(view.C, np.float64).reshape(3)
+    K = np.asarray(view.K, np.float64).reshape(4)
+    d = np.asarray(view.dist, np.float64).reshape(5)
+    return np.concatenate([R, C, K, d])
+
+
+def _dense_size(views):
+    shapes = [tuple(v.G.shape) for v in views]
+    if any(len(s) != 2 or s[0] < 1 or s[1] < 1 for s in shapes):
+        raise ValueError("a view's grey plane is [h, w]")
+    if any(s != shapes[0] for s in shapes):
+        raise ValueError("the views of a call have one size, got %s" % sorted(set(shapes)))
+    h, w = shapes[0]
+    if h > DENSE_MAX_SIDE or w > DENSE_MAX_SIDE:
+        raise ValueError("a view side above %d pixels" % DENSE_MAX_SIDE)
+    return h, w
+
+
+def _dense_out(out, specs, dev):
+    """the outputs: fresh, or the caller's (checked: shape, dtype, device, contiguous)"""
+    if out is None:
+        return [torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in specs]
+    out = list(out)
+    if len(out) != len(specs):
+        raise ValueError("%d output tensors wanted" % len(specs))
+    for t, (shape, dtype) in zip(out, specs):
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("an output tensor is a contiguous device %s of shape %r" % (dtype, tuple(shape)))
+    return out
+
+
+def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, min_score=0.6, out=None):
+    """The plane sweep of one reference view (dense.py, THE RULES), one launch.  ref and the
+    neighbours are views (G [h, w] float32, K, dist, R, C; the reference also rays [h, w, 2]), numpy
+    or device.  -> device plane int32 [h, w], score float32 [h, w], depth float32 [h, w] (NaN where
+    not kept), around float32 [h, w, 3].  out: those four, allocated by the caller."""
+    neighbours = list(neighbours)
+    planes, radius = int(planes), int(radius)
+    if not 1 <= planes <= DENSE_MAX_PLANES:
+        raise ValueError("planes is 1 to %d, got %d" % (DENSE_MAX_PLANES, planes))
+    if not 1 <= radius <= DENSE_MAX_RADIUS:
+        raise ValueError("radius is 1 to %d, got %d" % (DENSE_MAX_RADIUS, radius))
+    if not 1 <= len(neighbours) <= DENSE_MAX_NEIGHBOURS:
+        raise ValueError("1 to %d neighbours, got %d" % (DENSE_MAX_NEIGHBOURS, len(neighbours)))
+    h, w = _dense_size([ref] + neighbours)
+    w_far, w_near = float(w_far), float(w_near)
+    if not (w_far > 0.0 and w_near > w_far and math.isfinite(w_near)):
+        raise ValueError("inverse depths with 0 < w_far < w_near wanted, got %r and %r" % (w_far, w_near))
+    if ref.rays is None or tuple(ref.rays.shape) != (h, w, 2):
+        raise ValueError("the reference view carries rays [h, w, 2]")
+    dev = require_gpu()
+    G = _dev(ref.G, torch.float32)
+    rays = _dev(ref.rays, F64)
+    planes_n = [_dev(v.G, torch.float32) for v in neighbours]
+    if all(p.data_ptr() == planes_n[0].data_ptr() + 4 * h * w * k for k, p in enumerate(planes_n)):
+        N = planes_n[0]                                    # (consecutive in one buffer already: read in place)
+    else:
+        N = torch.stack(planes_n).contiguous()
+    pose = _dev(dense_camera(ref)[:12], F64)
+    cams = _dev(np.stack([dense_camera(v) for v in neighbours]), F64)
+    plane, score, depth, around = _dense_out(out, [((h, w), I32), ((h, w), torch.float32), ((h, w), torch.float32),
+                                                   ((h, w, 3), torch.float32)], dev)
+    check(lib().iamx_dense_sweep(_ptr(G), _ptr(rays), _ptr(N), _ptr(pose), _ptr(cams), w, h, len(neighbours),
+                                 planes, w_far, w_near, radius, float(min_var), float(min_score), _ptr(plane),
+                                 _ptr(score), _ptr(depth), _ptr(around), stream_ptr()), 'iamx_dense_sweep')
+    torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
+    return plane, score, depth, around
+
+
+def dense_neighbour_table(neighbours, n_views):
+    """lists of view numbers -> int32 [V, M], -1 padded (host)"""
+    if len(neighbours) != n_views:
+        raise ValueError("one neighbour list per view")
+    M = max([len(n) for n in neighbours] + [1])
+    if M > DENSE_MAX_NEIGHBOURS:
+        raise ValueError("at most %d neighbours per view" % DENSE_MAX_NEIGHBOURS)
+    tab = -np.ones((n_views, M), np.int32)
+    for i, n in enumerate(neighbours):
+        n = [int(j) for j in n]
+        if any(not 0 <= j < n_views or j == i for j in n):
+            raise ValueError("view %d: a neighbour is another view of the call" % i)
+        tab[i, :len(n)] = n
+    return tab
+
+
+def dense_check(depths, views, neighbours, eps=0.01, min_agree=2, out=None):
+    """The consistency rule over stacked depth maps: depths float32 [V, h, w] (NaN: not kept), the V
+    views (each with rays), neighbours a list of view numbers per view.  -> device keep uint8
+    [V, h, w], ned float64 [V, h, w, 3]."""
+    views = list(views)
+    V = len(views)
+    tab = dense_neighbour_table(neighbours, V)
+    if not (float(eps) >= 0.0 and int(min_agree) >= 1):
+        raise ValueError("eps >= 0 and min_agree >= 1 wanted")
+    if V == 0:
+        raise ValueError("no views")
+    h, w = _dense_size(views)
+    if tuple(depths.shape) != (V, h, w):
+        raise ValueError("depths is [V, h, w] = %r" % ((V, h, w),))
+    for v in views:
+        if v.rays is None or tuple(v.rays.shape) != (h, w, 2):
+            raise ValueError("every view carries rays [h, w, 2]")
+    dev = require_gpu()
+    D = _dev(depths, torch.float32)
+    rays = torch.stack([_dev(v.rays, F64) for v in views]).contiguous()
+    cams = _dev(np.stack([dense_camera(v) for v in views]), F64)
+    nb = _dev(tab, I32)
+    keep, ned = _dense_out(out, [((V, h, w), U8), ((V, h, w, 3), F64)], dev)
+    check(lib().iamx_dense_check(_ptr(D), _ptr(rays), _ptr(cams), _ptr(nb), V, int(tab.shape[1]), w, h, float(eps),
+                                 int(min_agree), _ptr(keep), _ptr(ned), stream_ptr()), 'iamx_dense_check')
+    torch.cuda.current_stream().synchronize()
+    return keep, ned
+
+
+def dense_splat(ned, keep, x0, y1, gsd, W, H, out=None):
+    """The fusion rule: NED points [..., 3] (numpy or device) with keep [...] (or None: all) into the
+    raster frame.  -> device count int32 [H, W], sum int64 [H, W] of rint(up 1024), dsm float32
+    [H, W].  out: those three; count and sum are zeroed here."""
+    W, H, gsd = int(W), int(H), float(gsd)
+    if not (W >= 1 and H >= 1 and gsd > 0.0 and math.isfinite(gsd) and math.isfinite(x0) and math.isfinite(y1)):
+        raise ValueError("a raster frame of at least one cell at a positive gsd wanted")
+    dev = require_gpu()
+    P = _dev(ned, F64).reshape(-1, 3)
+    n = int(P.shape[0])
+    Kp = None
+    if keep is not None:
+        Kp = _dev(keep, U8).reshape(-1)
+        if int(Kp.shape[0]) != n:
+            raise ValueError("one keep flag per point")
+    count, total, dsm = _dense_out(out, [((H, W), I32), ((H, W), I64), ((H, W), torch.float32)], dev)
+    count.zero_()
+    total.zero_()
+    check(lib().iamx_dense_splat(_ptr(P), _ptr(Kp), n, float(x0), float(y1), gsd, W, H, _ptr(count), _ptr(total),
+                                 stream_ptr()), 'iamx_dense_splat')
+    check(lib().iamx_dense_resolve(_ptr(count), _ptr(total), W, H, _ptr(dsm), stream_ptr()), 'iamx_dense_resolve')
+    torch.cuda.current_stream().synchronize()
+    return count, total, dsm

@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""A dense surface beside the Step 5 map and the orthomosaic (no counterpart in the reference, whose
+surface is the sparse chains' triangulation): plane-sweep depth maps of one group's images against
+their best neighbours, cross-checked between views and fused into a height raster on the device
+(imageanalysis_amd/dense.py), written as <analysis_dir>/dense/dsm.npy, count.npy, dsm.wld and
+dense.json, with --ply the surviving points as dense/points.ply.
+Run from the reference's scripts/ directory: python <repo>/imageanalysis_amd/scripts/5d-dense-surface.py PROJECT
+"""
+import argparse
+import os
+import pickle
+import time
+
+from lib import groups, project
+
+from imageanalysis_amd import dense
+
+ap = argparse.ArgumentParser(description='Dense depth maps and a DSM raster of one group.')
+ap.add_argument('project', help='project directory')
+ap.add_argument('--group', type=int, default=0, help='group index')
+ap.add_argument('--scale', type=float, default=0.125, help='sweep scale of the frames')
+ap.add_argument('--planes', type=int, default=64, help='depth hypotheses per image, uniform in inverse depth')
+ap.add_argument('--neighbors', type=int, default=4, help='images to sweep each image against')
+ap.add_argument('--radius', type=int, default=3, help='correlation window radius, 1 .. 7')
+ap.add_argument('--min-score', type=float, default=0.6, help='least mean correlation of a kept pixel')
+ap.add_argument('--gsd', type=float, default=0.0, help='metres per cell (default: the sweep pixel\'s footprint at the median depth)')
+ap.add_argument('--ply', action='store_true', help='write the surviving points as dense/points.ply')
+args = ap.parse_args()
+
+proj = project.ProjectMgr(args.project)
+proj.load_images_info()
+group_list = groups.load(proj.analysis_dir)
+print('Group sizes:', " ".join(str(len(g)) for g in group_list))
+with open(os.path.join(proj.analysis_dir, "matches_grouped"), "rb") as f:
+    matches = pickle.load(f)
+
+t0 = time.perf_counter()
+views, group = dense.views_from_project(proj, group_list, args.group, matches, args.scale)
+if not views:
+    raise SystemExit("group %d has no images" % args.group)
+poses = [(v.R, v.C) for v in views]
+neighbours = dense.choose_neighbours(matches, group, poses, n=args.neighbors)
+ranges = dense.depth_range(matches, group, poses)
+swept = sum(1 for n, r in zip(neighbours, ranges) if n and r is not None)
+print('Views: %d of %d x %d pixels, %d with neighbours and a depth range' % (len(views), views[0].G.shape[1],
+                                                                            views[0].G.shape[0], swept))
+maps = dense.depth_maps(views, neighbours, ranges, planes=args.planes, radius=args.radius, min_score=args.min_score)
+gsd = args.gsd
+if gsd <= 0.0:
+    mids = sorted(0.5 * (r[0] + r[1]) for r in ranges if r is not None)
+    if not mids:
+        raise SystemExit("no image of group %d observes a positioned chain" % args.group)
+    gsd = mids[len(mids) // 2] / float(views[0].K[0])
+surface = dense.fuse(views, maps, gsd)
+info = dense.save(surface, proj.analysis_dir, points=dense.surface_points(views, maps) if args.ply else None)
+print('DSM: %d x %d cells at %.3f m, %d of them filled by %d points, %.1f s'
+      % (info['width'], info['height'], gsd, info['cells_filled'], info['points_fused'], time.perf_counter() - t0))
+print('Wrote %s to %s/dense' % (', '.join(sorted(info['files'].values())), proj.analysis_dir))

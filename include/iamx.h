@@ -1779,6 +1779,51 @@ int iamx_brute_select(const int32_t *pairs, const int64_t *kp_off, const int32_t
                       int64_t *out_off, int32_t *out_rows, int64_t out_cap, int32_t *chosen,
                       int32_t *stats, int32_t *fit_cnt, int32_t *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Dense surface (csrc/dense_sweep.hip) -- plane-sweep depth maps, their cross-view check and
+ * the DSM splat.  The rules are stated in imageanalysis_amd/dense.py ("THE RULES") and restated in
+ * numpy by tests/dense_restatement.py; the device follows them bit for bit.  All pointers DEV.
+ *
+ * A camera is IAMX_DENSE_CAM_DOUBLES doubles: R[9] (NED -> camera, row-major), C[3] (centre, NED),
+ * fx, fy, cx, cy at the sweep scale, k1, k2, p1, p2, k3.  rays [h][w][2] are a view's undistorted
+ * normalised coordinates (xn, yn) at its pixel centres.
+ *
+ * iamx_dense_sweep, one launch per reference image: ref [h][w] float32 grey, nbr [num_nbr][h][w],
+ *   ref_pose [12] = R, C of the reference, nbr_cam [num_nbr][21].  planes 1..IAMX_DENSE_MAX_PLANES
+ *   uniform in inverse depth from w_far to w_near, radius 1..IAMX_DENSE_MAX_RADIUS, the texture
+ *   gate min_var, the keep threshold min_score.  -> plane [h][w] (-1: every plane invalid), score
+ *   [h][w] (the winner's; NaN), depth [h][w] (NaN where not kept), around [h][w][3] = the scores at
+ *   plane - 1, plane, plane + 1 (NaN where there is none or it is invalid).  Every pixel is written.
+ *   A workgroup owns IAMX_DENSE_TILE_W x IAMX_DENSE_TILE_H pixels.
+ * iamx_dense_check, one thread per pixel of depth [V][h][w]: nbr [V][max_nbr] view numbers, -1 for
+ *   none.  -> keep [V][h][w] 0 / 1, ned [V][h][w][3] the pixel's NED point (NaN where depth is).
+ * iamx_dense_splat: ned [N][3], keep [N] or null (all); the points with keep != 0 inside the frame
+ *   (x0 = west side of column 0, y1 = north side of row 0, gsd) add 1 to count [H][W] and
+ *   rint(up 1024) to sum [H][W] by integer atomics; the caller zeroes both.  A point whose
+ *   |rint(up 1024)| is above 1e15 or NaN is dropped.
+ * iamx_dense_resolve: dsm [H][W] = float32(sum / 1024 / count), NaN where count == 0.
+ * A size or a parameter out of range, a null pointer: IAMX_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_DENSE_TILE_W 32
+#define IAMX_DENSE_TILE_H 16
+#define IAMX_DENSE_MAX_RADIUS 7
+#define IAMX_DENSE_MAX_PLANES 4096
+#define IAMX_DENSE_MAX_NEIGHBOURS 16
+#define IAMX_DENSE_MAX_SIDE 16384
+#define IAMX_DENSE_MAX_RASTER 1048576
+#define IAMX_DENSE_CAM_DOUBLES 21
+int iamx_dense_sweep(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
+                     const double *nbr_cam, int width, int height, int num_nbr, int planes,
+                     double w_far, double w_near, int radius, float min_var, float min_score,
+                     int32_t *plane, float *score, float *depth, float *around, void *stream);
+int iamx_dense_check(const float *depth, const double *rays, const double *cams, const int32_t *nbr,
+                     int num_views, int max_nbr, int width, int height, double eps, int min_agree,
+                     uint8_t *keep, double *ned, void *stream);
+int iamx_dense_splat(const double *ned, const uint8_t *keep, int64_t num_points, double x0, double y1,
+                     double gsd, int width, int height, int32_t *count, int64_t *sum, void *stream);
+int iamx_dense_resolve(const int32_t *count, const int64_t *sum, int width, int height, float *dsm,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
