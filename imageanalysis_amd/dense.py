@@ -8,9 +8,12 @@ surface is the sparse chains' Delaunay triangulation).
     depth_maps(views, neighbours, ranges, planes=64, ...)   sweep every view, cross-check -> DepthMaps
     fuse(views, depths, gsd)                             surviving points -> Surface (dsm, count)
     save(surface, analysis_dir, points=None)             dense/dsm.npy, count.npy, dsm.wld, dense.json
+    load(analysis_dir)                                   the inverse of save -> Surface
+    fill(surface, rounds=8)                              holes closed from their rims -> (Surface, round_of)
 
 The kernels are csrc/dense_sweep.hip; tests/dense_restatement.py restates the rules below in numpy,
-operation by operation, and the device result is held to it bit for bit.
+operation by operation, and the device result is held to it bit for bit (fill: csrc/ortho_dsm.hip's
+iamx_dense_fill, restated by tests/ortho_dense_restatement.py).
 
 THE RULES
 
@@ -71,6 +74,15 @@ falls outside the last cell and is dropped, as every point outside the frame is.
 cell (floor((y1 - north) / gsd), floor((east - x0) / gsd)).  Each cell holds an int32 count and an
 int64 sum of rint(up 1024), both kept by integer atomics only: the result does not depend on
 scheduling.  dsm = float32(sum / 1024 / count) in float64, NaN where count == 0.
+
+Fill (dense_fill) makes the fused DSM hole-free enough to drape frames over.  Round k = 1 .. rounds
+reads the raster as round k - 1 left it (ping-pong, nothing is updated in place).  A NaN cell with at
+least one finite value among its 8 neighbours becomes the float32 sum of those values divided by
+their count: the neighbours are taken in row-major order, cells outside the raster do not exist, the
+sum starts at the first finite neighbour, and the quotient is computed in float64 and rounded once
+(the correctly rounded float32 quotient).  Finite cells never change.  round_of, uint8 [H, W], is 0
+for a measured cell, k for a cell filled in round k and 255 for a cell still empty.  rounds is
+0 .. 254 (0: nothing is filled); an all-NaN raster is a ValueError; count is carried over unchanged.
 
 The grey plane of a project's frame (views_from_project): the decoded BGR frame through
 kernels.resize_area at the sweep scale (cv2's INTER_AREA), then the integer luma
@@ -433,3 +445,45 @@ def save(surface, analysis_dir, points=None):
         info['points'] = int(len(points[0]))
     panda3d._write_atomic(os.path.join(out_dir, 'dense.json'), (json.dumps(info, indent=2) + "\n").encode())
     return info
+
+
+def load(analysis_dir, device=None):
+    """<analysis_dir>/dense/dsm.npy, count.npy and dense.json back into a Surface, the inverse of
+    save().  The tensors go to the current HIP device; device=: somewhere else ('cpu': no device
+    is needed)."""
+    import torch
+    out_dir = os.path.join(analysis_dir, 'dense')
+    with open(os.path.join(out_dir, 'dense.json')) as f:
+        info = json.load(f)
+    files = info.get('files', {})
+    dsm = np.load(os.path.join(out_dir, files.get('dsm', 'dsm.npy')))
+    count = np.load(os.path.join(out_dir, files.get('count', 'count.npy')))
+    if dsm.ndim != 2 or dsm.dtype != np.float32 or count.shape != dsm.shape or count.dtype != np.int32:
+        raise ValueError("%s: dsm.npy is float32 [H, W] and count.npy int32 of the same shape" % out_dir)
+    if dsm.shape != (info['height'], info['width']):
+        raise ValueError("%s: dsm.npy is %d x %d cells, dense.json says %d x %d"
+                         % (out_dir, dsm.shape[1], dsm.shape[0], info['width'], info['height']))
+    if device is None:
+        from . import kernels
+        d, c = kernels._dev(dsm, torch.float32), kernels._dev(count, torch.int32)
+        torch.cuda.current_stream().synchronize()
+    else:
+        d, c = torch.from_numpy(dsm).to(device), torch.from_numpy(count).to(device)
+    return Surface(d, c, info['bounds']['west'], info['bounds']['north'], info['gsd'])
+
+
+def fill(surface, rounds=8):
+    """The fill rule (THE RULES) on a Surface.  -> (Surface with the filled dsm and the same count,
+    round_of uint8 [H, W]: 0 measured, k filled in round k, 255 still empty)"""
+    import torch
+    from . import kernels
+    rounds = int(rounds)
+    if not 0 <= rounds <= 254:
+        raise ValueError("rounds is 0 to 254, got %d" % rounds)
+    dsm = surface.dsm if isinstance(surface.dsm, torch.Tensor) else torch.from_numpy(np.asarray(surface.dsm, np.float32))
+    if dsm.dim() != 2 or dsm.numel() == 0:
+        raise ValueError("a DSM is [H, W]")
+    if not bool(torch.isfinite(dsm).any()):
+        raise ValueError("the DSM has no measured cell: nothing to fill from")
+    filled, round_of = kernels.dense_fill(dsm, rounds)
+    return Surface(filled, surface.count, surface.x0, surface.y1, surface.gsd), round_of

@@ -2473,3 +2473,55 @@ def dense_splat(ned, keep, x0, y1, gsd, W, H, out=None):
     check(lib().iamx_dense_resolve(_ptr(count), _ptr(total), W, H, _ptr(dsm), stream_ptr()), 'iamx_dense_resolve')
     torch.cuda.current_stream().synchronize()
     return count, total, dsm
+
+
+def dense_fill(dsm, rounds=8):
+    """The DSM hole fill (dense.py, THE RULES: fill), one launch per round and one to sort the cells:
+    dsm float32 [H, W] (numpy or device), NaN: empty.  -> device (filled float32 [H, W], round_of uint8
+    [H, W]: 0 measured, k filled in round k, 255 still empty)."""
+    rounds = int(rounds)
+    if not 0 <= rounds <= 254:
+        raise ValueError("rounds is 0 to 254, got %d" % rounds)
+    if len(dsm.shape) != 2 or dsm.shape[0] < 1 or dsm.shape[1] < 1:
+        raise ValueError("a DSM is [H, W]")
+    dev = require_gpu()
+    src = _dev(dsm, torch.float32)
+    H, W = int(src.shape[0]), int(src.shape[1])
+    z = [torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)]
+    r = [torch.empty((H, W), dtype=U8, device=dev) for _ in range(2)]
+    check(lib().iamx_dense_fill(_ptr(src), None, W, H, 0, _ptr(z[0]), _ptr(r[0]), stream_ptr()), 'iamx_dense_fill')
+    for k in range(1, rounds + 1):
+        a, b = (k - 1) & 1, k & 1
+        check(lib().iamx_dense_fill(_ptr(z[a]), _ptr(r[a]), W, H, k, _ptr(z[b]), _ptr(r[b]), stream_ptr()),
+              'iamx_dense_fill')
+    torch.cuda.current_stream().synchronize()              # (src may be a staging copy: it has been read)
+    return z[rounds & 1], r[rounds & 1]
+
+
+# --------------------------------------------------------------------------------------
+# true orthophoto (csrc/ortho_dsm.hip; the rules: ortho.py)
+# --------------------------------------------------------------------------------------
+ORTHO_DSM_PARAMS, ORTHO_DSM_MAX_UPSAMPLE = 26, 8
+
+
+def ortho_dsm_params(x0, y1, gsd, bias, zmax, K, dist, R, C):
+    """the 26 host doubles of iamx_ortho_dsm_image: the DSM's frame, bias, zmax, then a dense camera
+    (R row-major, C, fx, fy, cx, cy at the frame's size, k1, k2, p1, p2, k3)"""
+    return np.concatenate([[float(x0), float(y1), float(gsd), float(bias), float(zmax)],
+                           np.asarray(R, np.float64).reshape(9), np.asarray(C, np.float64).reshape(3),
+                           np.asarray(K, np.float64).reshape(4), np.asarray(dist, np.float64).reshape(5)])
+
+
+def ortho_dsm_image(mode, dsm, ss, params, frame, image_index, box, acc, index, count, bgr):
+    """One image of a true orthophoto into the accumulators (ortho.py, THE TRUE-ORTHO RULES), one
+    launch: mode 0 best / 1 feather, dsm device float32 [H, W], ss the upsample, params
+    ortho_dsm_params(), frame device uint8 [h, w, 3], box (c0, r0, c1, r1) in mosaic pixels; acc,
+    index (None in mode feather), count, bgr as iamx_ortho_clear left them or earlier images did."""
+    params = np.ascontiguousarray(params, np.float64)
+    if params.shape != (ORTHO_DSM_PARAMS,):
+        raise ValueError("%d parameters wanted" % ORTHO_DSM_PARAMS)
+    c0, r0, c1, r1 = (int(v) for v in box)
+    check(lib().iamx_ortho_dsm_image(int(mode), _ptr(dsm), int(dsm.shape[0]), int(dsm.shape[1]), int(ss),
+                                     params.ctypes.data_as(_lib.c_void_p), _ptr(frame), int(frame.shape[0]),
+                                     int(frame.shape[1]), int(image_index), c0, r0, c1, r1, _ptr(acc), _ptr(index),
+                                     _ptr(count), _ptr(bgr), stream_ptr()), 'iamx_ortho_dsm_image')

@@ -5,7 +5,8 @@ centre) written as one georeferenced image, on a machine without a display.
     raster_frame(grids, gsd)                       origin, size, snapped vertices (host)
     compose(grids, uvs, frames, width, height, gsd, mode, bands=)   the rasteriser on ready arrays
     render(proj, group_list, group_index, gsd, ...)           grids, frames and filters of a project
-    save(mosaic, analysis_dir, tile, fmt)          tiles, world files, ortho.json
+    save(mosaic, analysis_dir, tile, fmt, subdir)  tiles, world files, ortho.json
+    compose_dense(...), render_dense(...)          the true orthophoto over the dense DSM (last section)
 
 The rasteriser is csrc/ortho_raster.hip; tests/ortho_restatement.py (mode multiband:
 tests/ortho_multiband_restatement.py) restates the rules below in numpy, operation by operation,
@@ -97,6 +98,73 @@ pixel), index 4, count 2, bgr 3; on top the larger of the ownership metric (8 pe
 freed before the first frame) and the layer pyramid of the image with the largest pixel box (16 per
 pixel of its regions).  The collapse works in place.  An image costs a layer launch, L - 1 reduces
 and L accumulates over its regions; the collapse runs once over every level.
+
+THE TRUE-ORTHO RULES
+
+    compose_dense(surface, cameras, frames, mode, upsample, bias)   the drape on ready arrays
+    render_dense(proj, group_list, group_index, surface, ...)       poses, frames and filters of a project
+
+A true orthophoto over the dense DSM (dense.py; 5e-true-ortho.py): every mosaic pixel is placed at
+its DSM height, projected into the frames through the full camera model and coloured only from the
+frames that see it.  The kernel is csrc/ortho_dsm.hip; tests/ortho_dense_restatement.py restates
+what follows and the device is held to it bit for bit.  Everything is float64, every product and sum
+rounded on its own, sums of three from the left.
+
+Inputs.  The surface: Z = float64(dsm) [H][W] with x0, y1, gsd (dense.Surface; fill it first, a NaN
+cell is a hole).  The settings: an integer upsample ss, 1 .. 8; bias >= 0, finite, metres; zmax, the
+largest finite Z.  Per image k: a BGR uint8 frame h_k x w_k, at least 2 x 2;
+K_k = dense.scaled_K(K, width, height, w_k, h_k); dist[5]; R (NED -> camera); C (NED).
+
+Mosaic.  H_o = H ss, W_o = W ss, g = gsd / ss (a side above 2^20 pixels is refused).  Row 0 is north;
+pixel (r, c) lies at e = x0 + (c + 0.5) g, n = y1 - (r + 0.5) g.
+
+Height.  gx = min(max((c + 0.5) / ss - 0.5, 0), W - 1), xa = floor(gx), xb = min(xa + 1, W - 1),
+tx = gx - xa; y likewise.  top = Z[ya][xa] + (Z[ya][xb] - Z[ya][xa]) tx, and Z[ya][xa] alone when
+tx == 0 (the tap of weight zero is not read: a hole beside the pixel does not reach it); bot on row
+yb; h = top + (bot - top) ty, and top alone when ty == 0.  Where h is NaN the pixel is uncovered for
+every image.  P = (n, e, -h).
+
+Cover.  dense.py's warp from D = Xw - Cn onward with Xw = P: Xn, x, y, r2, rad, xd, yd, then fx_, fy_
+with K_k.  Image k covers the pixel iff Xn_2 > 0, 0 <= fx_ <= w_k - 1, 0 <= fy_ <= h_k - 1 (a NaN
+fails) and dh = (-C_2) - h > 0.
+
+Visibility, in DSM cell units: px = (c + 0.5) / ss, py = (r + 0.5) / ss; qx = (C_1 - x0) / gsd,
+qy = (y1 - C_0) / gsd; dx = qx - px, dy = qy - py, L = max(|dx|, |dy|).  For i = 1, 2, ... while
+i <= L and i <= max(H, W):
+    t = i / L,  x = px + dx t,  y = py + dy t
+    the cell is (floor(y), floor(x)); outside the raster: visible, stop
+    hr = h + dh t;  hr > zmax: visible, stop
+    Z[cell] > hr + bias: occluded, stop                      (false for a NaN)
+When the loop runs out, or L < 1, the pixel is visible.  A step moves one cell along the longer
+axis, so the bound max(H, W) is never what ends a march.
+
+Sample: the bilinear formula above at (fx_, fy_) in the frame, per channel.
+
+Composition, images in group order, one stream-ordered launch per image, no atomics; the
+accumulators are those of best and feather above (iamx_ortho_clear and iamx_ortho_resolve are reused):
+  best      m = (D_0 D_0 + D_1 D_1) / (dh dh), the squared tangent off nadir; the smallest m wins,
+            the earlier image on a tie.  bgr = floor(sample + 0.5); index int32, -1 where
+            uncovered; count uint16, the images that cover AND see the pixel, saturating.
+  feather   d = min(min(fx_, (w_k - 1) - fx_), min(fy_, (h_k - 1) - fy_)),
+            w = max(d / (0.5 min(w_k - 1, h_k - 1)), 2^-20); accumulated and resolved as feather above.
+  multiband with a dense surface is a ValueError: its pyramid kernels want an owner pass and a layer
+            pass from this kernel (a later change).
+
+Work box per image (host, float64; work_box()): the undistorted rays (undistort.undistort_points) of
+the frame's four corners and of every 32nd border pixel are cut with the horizontal planes at the
+smallest and the largest finite DSM height.  If a ray does not descend (or the camera is not above
+the higher plane, or a hit is not finite) the box is the whole mosaic.  Otherwise it is the bounds
+of the hits in mosaic pixels, floor of the smallest and ceil of the largest, grown on every side by
+BOX_MARGIN = 2 pixels plus BOX_GROW = 1/64 of the box's longer side (the bow of a distorted border
+between two samples, the float32 of the undistortion and the rounding of h), then cut to the mosaic.
+It assumes a distortion model that is monotonic over the frame's cone.  The restatement computes
+every image over the whole mosaic; equality checks the box.
+
+Departures, none of them measured on real frames.  Occluders are the DSM's cells at their nearest-cell
+heights while the point's own height is bilinear: on a slope steeper than bias / gsd per cell a
+point can be hidden by the cell it stands in or the next one, which is what bias is for.  bias=None
+means 1.0 gsd; no real DSM has been measured against that default.  Memory: the mosaic's
+accumulators as above (17 or 37 bytes per pixel) plus the DSM.
 """
 import ctypes
 import json
@@ -141,11 +209,13 @@ class RasterFrame(object):
 class Mosaic(object):
     """device bgr uint8 [H,W,3], index int32 [H,W] (None in mode feather), count uint16 [H,W];
     x0, y1, gsd; mode; names (the group's images, `index` counts into them); bands (multiband: the
-    levels used, L; else None)"""
-    __slots__ = ('bgr', 'index', 'count', 'x0', 'y1', 'gsd', 'mode', 'names', 'bands')
+    levels used, L; else None); a true orthophoto also carries surface = 'dense', upsample and bias
+    (None on every other mosaic)"""
+    __slots__ = ('bgr', 'index', 'count', 'x0', 'y1', 'gsd', 'mode', 'names', 'bands', 'surface', 'upsample', 'bias')
 
     def __init__(self, **kw):
         self.bands = None
+        self.surface = self.upsample = self.bias = None
         for k, v in kw.items():
             setattr(self, k, v)
 
@@ -605,23 +675,276 @@ def render(proj, group_list, group_index, gsd, mode='best', prefilter=True, hist
     return mosaic
 
 
+# ---------------------------------------------------------------------------------------------
+# true orthophoto over the dense DSM (THE TRUE-ORTHO RULES)
+# ---------------------------------------------------------------------------------------------
+DENSE_MODES = ('best', 'feather')
+MAX_UPSAMPLE = 8
+BOX_STRIDE = 32                # every 32nd border pixel, and the corners
+BOX_MARGIN = 2.0               # mosaic pixels
+BOX_GROW = 1.0 / 64.0          # of the box's longer side
+
+# the last render_dense(): images, frames shrunk, seconds
+render_dense_stats = {'images': 0, 'prefiltered': 0, 'seconds': 0.0, 'frames_per_s': 0.0}
+
+
+def border_pixels(w, h):
+    """(x, y) of the frame's corners and every 32nd pixel of its border -> int64 [n][2]"""
+    xs = sorted(set(range(0, w, BOX_STRIDE)) | {w - 1})
+    ys = sorted(set(range(0, h, BOX_STRIDE)) | {h - 1})
+    pts = [(x, y) for y in (0, h - 1) for x in xs] + [(x, y) for x in (0, w - 1) for y in ys]
+    return np.array(sorted(set(pts)), np.int64)
+
+
+def work_box(K, dist, R, C, w, h, z_lo, z_hi, x0, y1, g, Ho, Wo, rays=None):
+    """The work box of one image (THE TRUE-ORTHO RULES): K = (fx, fy, cx, cy) at the frame's size
+    w x h, z_lo and z_hi the smallest and the largest finite DSM height, g the mosaic's pixel size.
+    rays: the undistorted normalised coordinates [n][2] of border_pixels(w, h) (default:
+    undistort.undistort_points, on the device).  -> inclusive (c0, r0, c1, r1) in mosaic pixels"""
+    K = np.asarray(K, np.float64).reshape(4)
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    C = np.asarray(C, np.float64).reshape(3)
+    whole = (0, 0, Wo - 1, Ho - 1)
+    if rays is None:
+        from . import undistort
+        und = undistort.undistort_points(border_pixels(w, h).astype(np.float32), K, dist).astype(np.float64)
+        rays = np.stack([(und[:, 0] - K[2]) / K[0], (und[:, 1] - K[3]) / K[1]], 1)
+    rays = np.asarray(rays, np.float64).reshape(-1, 2)
+    d = rays[:, :1] * R[0] + rays[:, 1:] * R[1] + R[2]             # R^T (xn, yn, 1), NED
+    if not (np.isfinite(d).all() and (d[:, 2] > 0).all() and -C[2] > z_hi):
+        return whole
+    cols, rows = [], []
+    for z in (z_lo, z_hi):
+        t = (-z - C[2]) / d[:, 2]
+        cols.append((C[1] + t * d[:, 1] - x0) / g)
+        rows.append((y1 - (C[0] + t * d[:, 0])) / g)
+    cols, rows = np.concatenate(cols), np.concatenate(rows)
+    if not (np.isfinite(cols).all() and np.isfinite(rows).all()):
+        return whole
+    lo_c, hi_c, lo_r, hi_r = floor(cols.min()), ceil(cols.max()), floor(rows.min()), ceil(rows.max())
+    grow = BOX_MARGIN + BOX_GROW * max(hi_c - lo_c, hi_r - lo_r)
+    clip = lambda v, n: int(min(max(v, -1.0), float(n)))          # (before int(): a far hit stays a small number)
+    return (max(clip(lo_c - grow, Wo), 0), max(clip(lo_r - grow, Ho), 0),
+            min(clip(ceil(hi_c + grow), Wo), Wo - 1), min(clip(ceil(hi_r + grow), Ho), Ho - 1))
+
+
+def _camera_of(cam):
+    """a (K, width, height, dist, R, C) tuple or a dense.View-like object (its K is at its plane's
+    size) -> (K, width, height, dist [5], R [3, 3], C [3])"""
+    if hasattr(cam, 'K') and hasattr(cam, 'R'):
+        G = getattr(cam, 'G', None)
+        if G is None or len(G.shape) < 2:
+            raise ValueError("a view given as a camera carries its plane G [h, w]: its size is the camera's")
+        cam = (cam.K, int(G.shape[1]), int(G.shape[0]), cam.dist, cam.R, cam.C)
+    if len(cam) != 6:
+        raise ValueError("a camera is (K, width, height, dist, R, C)")
+    K, width, height, dist, R, C = cam
+    dist, R, C = (np.asarray(dist, np.float64).reshape(5), np.asarray(R, np.float64).reshape(3, 3),
+                  np.asarray(C, np.float64).reshape(3))
+    if not (float(width) >= 1 and float(height) >= 1 and np.isfinite(np.asarray(K, np.float64)).all()
+            and np.isfinite(dist).all() and np.isfinite(R).all() and np.isfinite(C).all()):
+        raise ValueError("a camera is finite and at least 1 x 1 pixel")
+    return np.asarray(K, np.float64), float(width), float(height), dist, R, C
+
+
+def _check_dense_frame(frame):
+    shape = tuple(getattr(frame, 'shape', ()))
+    if len(shape) != 3 or shape[2] != 3 or shape[0] < 2 or shape[1] < 2:
+        raise ValueError("a frame is uint8 [h, w, 3], at least 2 x 2 (got %r)" % (shape,))
+
+
+def surface_heights(dsm):
+    """(the smallest, the largest, the mean) finite height of a device DSM, as floats"""
+    import torch
+    finite = dsm[torch.isfinite(dsm)]
+    if finite.numel() == 0:
+        raise ValueError("the DSM has no finite cell: nothing to drape over")
+    return float(finite.min()), float(finite.max()), float(finite.double().mean())
+
+
+class _DenseComposer(object):
+    """the accumulators of one true orthophoto and the DSM on the device; add(k, camera, frame)
+    drapes image k (call it in group order), finish() -> Mosaic"""
+
+    def __init__(self, surface, mode, upsample, bias, names=None):
+        import torch
+        from . import kernels
+        from ._lib import check, lib, require_gpu, stream_ptr
+        if mode == 'multiband':
+            raise ValueError("mode multiband over a dense surface is not built: use 'best' or 'feather'")
+        if mode not in DENSE_MODES:
+            raise ValueError("mode must be 'best' or 'feather'")
+        if isinstance(upsample, bool) or int(upsample) != upsample or not 1 <= int(upsample) <= MAX_UPSAMPLE:
+            raise ValueError("upsample is an integer 1 .. %d (got %r)" % (MAX_UPSAMPLE, upsample))
+        gsd = float(surface.gsd)
+        if not (gsd > 0.0 and np.isfinite(gsd) and np.isfinite(surface.x0) and np.isfinite(surface.y1)):
+            raise ValueError("the surface's frame must be finite, gsd positive")
+        bias = 1.0 * gsd if bias is None else float(bias)
+        if not (bias >= 0.0 and np.isfinite(bias)):
+            raise ValueError("bias is a finite number of metres, at least 0 (got %r)" % bias)
+        if len(surface.dsm.shape) != 2 or min(surface.dsm.shape) < 1:
+            raise ValueError("a DSM is [H, W]")
+        self.mode, self.ss, self.bias, self.names = mode, int(upsample), bias, list(names) if names is not None else None
+        H, W = (int(v) for v in surface.dsm.shape)
+        self.Ho, self.Wo, self.g = H * self.ss, W * self.ss, gsd / self.ss
+        if self.Ho > MAX_SIDE or self.Wo > MAX_SIDE:
+            raise ValueError("a %d x %d pixel mosaic: a side above 2^20 pixels is refused" % (self.Wo, self.Ho))
+        self.x0, self.y1, self.gsd = float(surface.x0), float(surface.y1), gsd
+        dev = self.dev = require_gpu()
+        need = self.Wo * self.Ho * BYTES_PER_PIXEL[mode]
+        free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+        if need > free:
+            raise MemoryError("a %d x %d pixel mosaic (mode %s) needs %.2f GB of accumulators, %.2f GB of device "
+                              "memory are free: use a smaller upsample (band splitting is not implemented)"
+                              % (self.Wo, self.Ho, mode, need / 1e9, free / 1e9))
+        self.dsm = kernels._dev(surface.dsm, torch.float32)
+        self.z_lo, self.z_hi, self.z_mean = surface_heights(self.dsm)
+        n = (self.Ho, self.Wo)
+        self._p, self._kernels = kernels._ptr, kernels
+        self._call = (lib(), check, stream_ptr)
+        self.acc = torch.empty(n if mode == 'best' else n + (4,), dtype=torch.float64, device=dev)
+        self.index = torch.empty(n, dtype=torch.int32, device=dev) if mode == 'best' else None
+        self.count = torch.empty(n, dtype=torch.uint16, device=dev)
+        self.bgr = torch.empty(n + (3,), dtype=torch.uint8, device=dev)
+        L, p = self._call[0], self._p
+        check(L.iamx_ortho_clear(MODES[mode], self.Ho, self.Wo, p(self.acc), p(self.index), p(self.count), p(self.bgr),
+                                 stream_ptr()), 'iamx_ortho_clear')
+
+    def box(self, K, dist, R, C, w, h):
+        return work_box(K, dist, R, C, w, h, self.z_lo, self.z_hi, self.x0, self.y1, self.g, self.Ho, self.Wo)
+
+    def add(self, k, camera, frame):
+        from . import dense
+        K, width, height, dist, R, C = _camera_of(camera)
+        _check_dense_frame(frame)
+        frame = self._kernels._dev(frame, self._kernels.U8)
+        h, w = int(frame.shape[0]), int(frame.shape[1])
+        Ks = dense.scaled_K(K, width, height, w, h)
+        params = self._kernels.ortho_dsm_params(self.x0, self.y1, self.gsd, self.bias, self.z_hi, Ks, dist, R, C)
+        self._kernels.ortho_dsm_image(MODES[self.mode], self.dsm, self.ss, params, frame, k,
+                                      self.box(Ks, dist, R, C, w, h), self.acc, self.index, self.count, self.bgr)
+
+    def finish(self):
+        L, check, stream_ptr = self._call
+        p = self._p
+        if self.mode == 'feather':
+            check(L.iamx_ortho_resolve(self.Ho, self.Wo, p(self.acc), p(self.count), p(self.bgr), stream_ptr()),
+                  'iamx_ortho_resolve')
+        return Mosaic(bgr=self.bgr, index=self.index, count=self.count, x0=self.x0, y1=self.y1, gsd=self.g,
+                      mode=self.mode, names=self.names, surface='dense', upsample=self.ss, bias=self.bias)
+
+
+def compose_dense(surface, cameras, frames, mode='best', upsample=1, bias=None, names=None):
+    """The true orthophoto on ready arrays (THE TRUE-ORTHO RULES): surface a dense.Surface (filled:
+    dense.fill), cameras a list of (K at camera size, width, height, dist, R NED -> camera, C NED) or
+    of dense.View-like objects, frames one BGR uint8 [h, w, 3] per camera (device tensors or numpy),
+    of any size at least 2 x 2; upsample: mosaic pixels per DSM cell and side, 1 .. 8; bias: metres a
+    DSM cell must stand above the ray to hide the point, None: 1.0 * surface.gsd -- a default no real
+    DSM has been measured against.  -> Mosaic (gsd: the mosaic's, surface.gsd / upsample)"""
+    cameras, frames = list(cameras), list(frames)
+    if len(frames) != len(cameras):
+        raise ValueError("%d frames for %d cameras" % (len(frames), len(cameras)))
+    if mode not in MODES:
+        raise ValueError("mode must be 'best' or 'feather'")
+    for cam, frame in zip(cameras, frames):                # (every ValueError before any device call)
+        _camera_of(cam)
+        _check_dense_frame(frame)
+    comp = _DenseComposer(surface, mode, upsample, bias, names)
+    for k, (cam, frame) in enumerate(zip(cameras, frames)):
+        comp.add(k, cam, frame)
+    return comp.finish()
+
+
+def dense_prefilter_factor(K, C, z_mean, g):
+    """f = min(1, native / g), native = (-C_2 - mean finite dsm) / sqrt(fx fy) at camera size: the
+    metres one frame pixel spans on the mean surface over the mosaic's pixel size"""
+    K = np.asarray(K, np.float64)
+    fx, fy = (K[0, 0], K[1, 1]) if K.shape == (3, 3) else K.reshape(4)[:2]
+    native = (-float(C[2]) - float(z_mean)) / sqrt(fx * fy)
+    return min(1.0, native / float(g))
+
+
+def _colour_frame(frame, name, histogram, mask):
+    """prepare_frame's colour step: histogram.lookup_tables and the vignette mask through kernels.colour_lut"""
+    from . import histogram as _histogram, kernels
+    lut = _histogram.lookup_tables(name) if histogram else None
+    if histogram and lut is None:
+        _log("histogram: no neighbour template for", name, "(image left as it is)")
+    if lut is None and mask is None:
+        return frame
+    if mask is not None and tuple(mask.shape) != tuple(frame.shape):
+        raise ValueError("%s: the frame is %d x %d, the vignette mask %d x %d"
+                         % (name, frame.shape[1], frame.shape[0], mask.shape[1], mask.shape[0]))
+    return kernels.colour_lut(frame, lut if lut is not None else _IDENTITY_LUT, mask)
+
+
+def render_dense(proj, group_list, group_index, surface, mode='best', upsample=1, bias=None, prefilter=True,
+                 histogram=False, vignette=False, frames=None):
+    """The true orthophoto of one group over `surface` (dense.load, then dense.fill): poses from
+    dense.image_pose, the optimised K and distortion as dense.views_from_project takes them, the
+    frames decoded by histogram.frame_pass in group order (frames=: ready device tensors instead),
+    the colour tables as prepare_frame applies them, and kernels.resize_area by
+    dense_prefilter_factor() when that is below 0.75.  -> Mosaic"""
+    from . import dense, histogram as _histogram, kernels
+    t0 = time.perf_counter()
+    camera = _deps.camera()
+    K = np.asarray(camera.get_K(optimized=True), np.float64)
+    dist = np.array(camera.get_dist_coeffs(optimized=True), np.float64).ravel()[:5]
+    width, height = camera.get_image_params()
+    group = dense.group_indices(proj, group_list, group_index)
+    images = [proj.image_list[i] for i in group]
+    names = [im.name for im in images]
+    comp = _DenseComposer(surface, mode, upsample, bias, names)
+    mask = _vignette_mask(proj.analysis_dir) if vignette else None
+    state = {'k': 0, 'shrunk': 0}
+
+    def on_frames(batch):
+        for frame in batch:
+            k = state['k']
+            frame = _colour_frame(_check_frame(frame), names[k], histogram, mask)
+            R, C = dense.image_pose(images[k])
+            if prefilter:
+                f = dense_prefilter_factor(K, C, comp.z_mean, comp.g)
+                if f < PREFILTER_BELOW and round(frame.shape[0] * f) >= 2 and round(frame.shape[1] * f) >= 2:
+                    frame = kernels.resize_area(frame, f, f)
+                    state['shrunk'] += 1
+            comp.add(k, (K, width, height, dist, R, C), frame)
+            state['k'] = k + 1
+
+    if frames is not None:
+        frames = list(frames)
+        if len(frames) != len(images):
+            raise ValueError("%d frames for the group's %d images" % (len(frames), len(images)))
+        on_frames(frames)
+    else:
+        _histogram.frame_pass(images, want_hist=False, on_frames=on_frames)
+    if state['k'] != len(images):
+        raise RuntimeError("%d of %d frames arrived" % (state['k'], len(images)))
+    mosaic = comp.finish()
+    dt = time.perf_counter() - t0
+    render_dense_stats.update(images=len(images), prefiltered=state['shrunk'], seconds=dt,
+                              frames_per_s=len(images) / dt if dt > 0 else 0.0)
+    return mosaic
+
+
 def world_file_text(gsd, west, north):
     """the six lines of a world file for a north-up tile whose upper-left CORNER is (west, north)"""
     vals = (gsd, 0.0, 0.0, -gsd, west + 0.5 * gsd, north - 0.5 * gsd)
     return "".join("%r\n" % float(v) for v in vals)
 
 
-def save(mosaic, analysis_dir, tile=4096, fmt='jpg'):
-    """<analysis_dir>/ortho/tile_<row>_<col>.<fmt> through Pillow (jpg: panda3d.encode_jpeg's
+def save(mosaic, analysis_dir, tile=4096, fmt='jpg', subdir='ortho'):
+    """<analysis_dir>/<subdir>/tile_<row>_<col>.<fmt> through Pillow (jpg: panda3d.encode_jpeg's
     settings), a world file per tile (local ENU metres, the pixel-centre convention) and ortho.json:
-    /config/ned_reference, gsd, bounds, mode (multiband: and bands), per-tile bounds, the image names.  -> the json's dict"""
+    /config/ned_reference, gsd, bounds, mode (multiband: and bands; a true orthophoto: and surface,
+    upsample, bias), per-tile bounds, the image names.  -> the json's dict"""
     from PIL import Image as PILImage
     from . import panda3d
     tile = int(tile)
     if tile < 1:
         raise ValueError("tile must be at least 1 pixel")
     fmt = fmt.lower().lstrip('.')
-    out_dir = os.path.join(analysis_dir, 'ortho')
+    out_dir = os.path.join(analysis_dir, subdir)
     os.makedirs(out_dir, exist_ok=True)
     H, W = mosaic.shape
     gsd, x0, y1 = float(mosaic.gsd), float(mosaic.x0), float(mosaic.y1)
@@ -655,5 +978,9 @@ def save(mosaic, analysis_dir, tile=4096, fmt='jpg'):
             'tiles': tiles, 'images': list(mosaic.names) if mosaic.names is not None else []}
     if mosaic.mode == 'multiband':
         info['bands'] = int(mosaic.bands)
+    if getattr(mosaic, 'surface', None) is not None:
+        info['surface'] = mosaic.surface
+        info['upsample'] = int(mosaic.upsample)
+        info['bias'] = float(mosaic.bias)
     panda3d._write_atomic(os.path.join(out_dir, 'ortho.json'), json.dumps(info, indent=1).encode())
     return info

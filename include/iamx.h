@@ -1824,6 +1824,41 @@ int iamx_dense_splat(const double *ned, const uint8_t *keep, int64_t num_points,
 int iamx_dense_resolve(const int32_t *count, const int64_t *sum, int width, int height, float *dsm,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * True orthophoto (csrc/ortho_dsm.hip): a group's frames draped over the dense DSM, every mosaic
+ * pixel placed at its DSM height, projected through the full camera model and coloured only from
+ * the frames that see it.  The rules are stated in imageanalysis_amd/ortho.py ("THE TRUE-ORTHO
+ * RULES") and the fill in imageanalysis_amd/dense.py; both are restated in numpy by
+ * tests/ortho_dense_restatement.py and the device follows them bit for bit.  All pointers DEV
+ * unless noted; null, size and range checks need no GPU.
+ *
+ * iamx_ortho_dsm_image, one image per launch, stream ordered -- the images of a group are composed
+ *   in the order of the calls.  dsm [H][W] f32 (NaN: a hole); ss: the mosaic is H ss x W ss pixels,
+ *   1 <= ss <= IAMX_ORTHO_DSM_MAX_UPSAMPLE, a side at most 2^20; params HOST f64
+ *   [IAMX_ORTHO_DSM_PARAMS] = x0, y1, gsd (the DSM's frame), bias, zmax (the largest finite height),
+ *   R[9] (NED -> camera, row-major), C[3] (NED), fx, fy, cx, cy at the frame's size, k1, k2, p1, p2,
+ *   k3, all finite; frame u8 [h_s][w_s][3], at least 2 x 2; image_index: what `index` receives;
+ *   c0, r0, c1, r1: the inclusive work box in mosaic pixels (c1 < c0 or r1 < r0: nothing is launched
+ *   and the call succeeds).  mode, acc, index, count and bgr are iamx_ortho_raster_image's, over the
+ *   mosaic: iamx_ortho_clear starts them and iamx_ortho_resolve finishes mode feather.
+ * iamx_dense_fill, one round of the DSM hole fill per launch: round 0 copies src to dst and writes
+ *   round_dst = 0 for a finite cell, 255 for an empty one (round_src is not read and may be NULL);
+ *   round k = 1 .. 254 gives an empty cell with a finite value among its 8 neighbours of src their
+ *   float32 sum in row-major order over their count (the quotient in float64, rounded once) and
+ *   round_dst = k; every other cell and its round are copied.  src and dst are different rasters
+ *   [height][width] f32, round_src and round_dst [height][width] u8.
+ * A size or a parameter out of range, a null pointer, a box that leaves the mosaic: IAMX_EINVAL
+ * without a launch.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_ORTHO_DSM_PARAMS 26
+#define IAMX_ORTHO_DSM_MAX_UPSAMPLE 8
+int iamx_ortho_dsm_image(int mode, const float *dsm, int H, int W, int ss, const double *params,
+                         const uint8_t *frame, int h_s, int w_s, int image_index, int c0, int r0,
+                         int c1, int r1, double *acc, int32_t *index, uint16_t *count, uint8_t *bgr,
+                         void *stream);
+int iamx_dense_fill(const float *src, const uint8_t *round_src, int width, int height, int round,
+                    float *dst, uint8_t *round_dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
