@@ -22,6 +22,12 @@
 // of the reference window do not depend on the step and are computed once.  The running winner and
 // the scores before and after it stay in registers.  No atomics.
 //
+// sweep_kernel<R, true> (iamx_dense_sweep_volume) is the same kernel with the emission compiled in: each
+// aggregate score also leaves as the uint8 cost of dense.py's SEMI-GLOBAL RULES, volume [h][w][planes],
+// for csrc/dense_sgm.hip.  A thread gathers four planes of a pixel into one dword store where planes is a
+// multiple of 4 and stores bytes otherwise.  sweep_kernel<R, false> never reads its volume argument and
+// compiles to the instructions of the kernel before the emission existed.
+//
 // check_kernel: one thread per pixel of every depth map.  splat_kernel: one thread per point,
 // integer atomics only (a 32-bit count and a 64-bit sum of rint(up 1024) per cell), so the result
 // does not depend on scheduling.  resolve_kernel: sum / 1024 / count.
@@ -150,8 +156,19 @@ __device__ __forceinline__ void write_pixel(const SweepArgs &A, int g, const Win
     A.around[3 * (int64_t)g + 2] = W.sp;
 }
 
-template <int R>
-__global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A)
+// the cost of SEMI-GLOBAL RULES: uint8, 255 for an invalid score, the clamp after the rounding
+__device__ __forceinline__ uint32_t cost_of(float S)
+{
+    if (!(S == S)) return 255u;
+    float c = rintf((1.0f - S) * 127.0f);
+    c = c < 0.0f ? 0.0f : (c > 254.0f ? 254.0f : c);
+    return (uint32_t)c;
+}
+
+// VOL: the costs of the thread's two pixels go to volume [h][w][planes] as well, four planes to a
+// dword store where planes is a multiple of 4 (pixel g's row then starts on a dword), bytes otherwise
+template <int R, bool VOL>
+__global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__restrict__ volume)
 {
     constexpr int K = 2 * R + 1;                         // window side
     constexpr int TW = TILE_W + 2 * R, TH = TILE_H + 2 * R;
@@ -237,6 +254,10 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A)
     W1.init();
     const double wmax = (double)(w - 1), hmax = (double)(h - 1);
     const int64_t plane_px = (int64_t)w * h;
+    const bool in0 = px < w && py < h, in1 = px + 1 < w && py < h;
+    const bool packed = (A.planes & 3) == 0;
+    uint8_t *__restrict__ vol0 = VOL ? volume + ((int64_t)py * w + px) * A.planes : nullptr;
+    uint32_t pk0 = 0, pk1 = 0;
     int buf = 0;
     for (int d = 0; d < A.planes; ++d) {
         const double z = 1.0 / (A.w_far + (double)d * A.step);
@@ -313,8 +334,25 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A)
             }
             buf ^= 1;
         }
-        W0.step(d, cnt0 > 0 ? sum0 / (float)cnt0 : qnan());
-        W1.step(d, cnt1 > 0 ? sum1 / (float)cnt1 : qnan());
+        const float S0 = cnt0 > 0 ? sum0 / (float)cnt0 : qnan();
+        W0.step(d, S0);
+        const float S1 = cnt1 > 0 ? sum1 / (float)cnt1 : qnan();
+        W1.step(d, S1);
+        if constexpr (VOL) {
+            const uint32_t c0 = cost_of(S0), c1 = cost_of(S1);
+            if (packed) {
+                pk0 |= c0 << (8 * (d & 3));
+                pk1 |= c1 << (8 * (d & 3));
+                if ((d & 3) == 3) {
+                    if (in0) *reinterpret_cast<uint32_t *>(vol0 + (d - 3)) = pk0;
+                    if (in1) *reinterpret_cast<uint32_t *>(vol0 + A.planes + (d - 3)) = pk1;
+                    pk0 = pk1 = 0;
+                }
+            } else {
+                if (in0) vol0[d] = (uint8_t)c0;
+                if (in1) vol0[A.planes + d] = (uint8_t)c1;
+            }
+        }
     }
     if (py < h) {
         if (px < w) write_pixel(A, py * w + px, W0);
@@ -323,10 +361,14 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A)
 }
 
 template <int R>
-int launch_sweep(const SweepArgs &A, void *stream)
+int launch_sweep(const SweepArgs &A, uint8_t *volume, void *stream)
 {
     const dim3 grid((A.w + TILE_W - 1) / TILE_W, (A.h + TILE_H - 1) / TILE_H);
-    hipLaunchKernelGGL(sweep_kernel<R>, grid, dim3(THREADS), 0, iamx::as_stream(stream), A);
+    if (volume) {
+        hipLaunchKernelGGL((sweep_kernel<R, true>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, volume);
+        return iamx::check_launch("iamx_dense_sweep_volume");
+    }
+    hipLaunchKernelGGL((sweep_kernel<R, false>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, (uint8_t *)nullptr);
     return iamx::check_launch("iamx_dense_sweep");
 }
 
@@ -410,10 +452,10 @@ __global__ __launch_bounds__(THREADS) void resolve_kernel(const int32_t *__restr
 
 }  // namespace
 
-extern "C" int iamx_dense_sweep(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
+static int dense_sweep_entry(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
                                 const double *nbr_cam, int width, int height, int num_nbr, int planes,
                                 double w_far, double w_near, int radius, float min_var, float min_score,
-                                int32_t *plane, float *score, float *depth, float *around, void *stream)
+                                int32_t *plane, float *score, float *depth, float *around, uint8_t *volume, void *stream)
 {
     IAMX_REQUIRE(planes >= 1 && planes <= IAMX_DENSE_MAX_PLANES, "planes out of range");
     IAMX_REQUIRE(radius >= 1 && radius <= IAMX_DENSE_MAX_RADIUS, "radius out of range");
@@ -432,14 +474,36 @@ extern "C" int iamx_dense_sweep(const float *ref, const double *rays, const floa
     A.min_score = min_score;
     A.plane = plane; A.score = score; A.depth = depth; A.around = around;
     switch (radius) {
-        case 1: return launch_sweep<1>(A, stream);
-        case 2: return launch_sweep<2>(A, stream);
-        case 3: return launch_sweep<3>(A, stream);
-        case 4: return launch_sweep<4>(A, stream);
-        case 5: return launch_sweep<5>(A, stream);
-        case 6: return launch_sweep<6>(A, stream);
-        default: return launch_sweep<7>(A, stream);
+        case 1: return launch_sweep<1>(A, volume, stream);
+        case 2: return launch_sweep<2>(A, volume, stream);
+        case 3: return launch_sweep<3>(A, volume, stream);
+        case 4: return launch_sweep<4>(A, volume, stream);
+        case 5: return launch_sweep<5>(A, volume, stream);
+        case 6: return launch_sweep<6>(A, volume, stream);
+        default: return launch_sweep<7>(A, volume, stream);
     }
+}
+
+extern "C" int iamx_dense_sweep(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
+                                const double *nbr_cam, int width, int height, int num_nbr, int planes,
+                                double w_far, double w_near, int radius, float min_var, float min_score,
+                                int32_t *plane, float *score, float *depth, float *around, void *stream)
+{
+    return dense_sweep_entry(ref, rays, nbr, ref_pose, nbr_cam, width, height, num_nbr, planes, w_far, w_near, radius,
+                             min_var, min_score, plane, score, depth, around, nullptr, stream);
+}
+
+extern "C" int iamx_dense_sweep_volume(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
+                                       const double *nbr_cam, int width, int height, int num_nbr, int planes,
+                                       double w_far, double w_near, int radius, float min_var, float min_score,
+                                       int32_t *plane, float *score, float *depth, float *around, uint8_t *volume,
+                                       void *stream)
+{
+    IAMX_REQUIRE(planes >= 2 && planes <= IAMX_DENSE_SGM_MAX_PLANES, "planes out of range for a cost volume");
+    IAMX_REQUIRE(volume, "null pointer");
+    IAMX_REQUIRE(((uintptr_t)volume & 3) == 0, "the volume is aligned to 4 bytes");
+    return dense_sweep_entry(ref, rays, nbr, ref_pose, nbr_cam, width, height, num_nbr, planes, w_far, w_near, radius,
+                             min_var, min_score, plane, score, depth, around, volume, stream);
 }
 
 extern "C" int iamx_dense_check(const float *depth, const double *rays, const double *cams, const int32_t *nbr,

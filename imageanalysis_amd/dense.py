@@ -6,6 +6,7 @@ surface is the sparse chains' Delaunay triangulation).
     choose_neighbours(matches, group, poses, n=4)        per image, the images to sweep against
     depth_range(matches, group, poses)                   per image, (z_near, z_far) from its chains
     depth_maps(views, neighbours, ranges, planes=64, ...)   sweep every view, cross-check -> DepthMaps
+                                                         (regularize='sgm': SEMI-GLOBAL RULES)
     fuse(views, depths, gsd)                             surviving points -> Surface (dsm, count)
     save(surface, analysis_dir, points=None)             dense/dsm.npy, count.npy, dsm.wld, dense.json
     load(analysis_dir)                                   the inverse of save -> Surface
@@ -60,6 +61,39 @@ off = (0.5 (s_m - s_p)) / den clamped to +-0.5, else off = 0.  In float64
 A pixel is kept iff best >= 0 and s_0 >= min_score; depth is NaN where it is not.  Outputs: plane
 int32, score = s_0 (NaN for best = -1), depth, around = (s_m, s_0, s_p).  A NaN is 0x7fc00000.
 
+SEMI-GLOBAL RULES (depth_maps(regularize='sgm'); kernels: csrc/dense_sgm.hip and the emission in
+csrc/dense_sweep.hip; restated by tests/dense_sgm_restatement.py).  Between the aggregate scores and
+the winner stands a semi-global aggregation (Hirschmueller) of the cost volume; everything but the two
+float32 operations of the select is integer arithmetic, so the result does not depend on scheduling.
+
+Cost.  S_d(p) is the aggregate score above, float32, invalid where it is above.  C(p, d) is uint8:
+255 where S_d(p) is invalid, otherwise clamp(rint((1.0f - S) 127.0f), 0, 254) -- each float32 operation
+rounded on its own, rint half to even, the clamp after the rounding.  The volume is [h][w][planes],
+planes contiguous.  The mode takes 2 <= planes <= 64 (IAMX_DENSE_SGM_MAX_PLANES: one plane per lane
+of a wave); anything else is a ValueError before any device call.
+
+Working cost.  C'(p, d) = C(p, d) if C < 255, else c_invalid, a parameter in 0 .. 254 that defaults
+to 127, which is score 0.
+
+Paths.  The directions (dx, dy) in this order: (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1) (-1,1);
+paths = 4 takes the first four, paths = 8 all, no other value is allowed.  For direction r and pixel p:
+if p - r lies outside the image, L_r(p, d) = C'(p, d); otherwise, with m = min_k L_r(p - r, k),
+    L_r(p, d) = C'(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + P1, L_r(p-r, d+1) + P1, m + P2) - m
+where planes d +- 1 outside [0, planes) do not exist.  0 <= P1 <= P2 <= 255.  Hence
+L_r <= 254 + P2 <= 509 and T(p, d) = sum_r L_r(p, d) <= 4072 fits a uint16.
+
+Select.  best = argmin_d T(p, d), the smallest d on a tie: always >= 0, also where every raw cost is
+255 (a propagated plane).  With T_0 = T(p, best), T_m and T_p at best -+ 1: if 0 < best < planes - 1
+and the integer den = (T_m - 2 T_0) + T_p > 0, off = float32(T_m - T_p) / float32(2 den), one float32
+division, clamped to +-0.5; otherwise off = 0.  In float64, as in the sweep,
+    depth = float32(1 / (w_far + (best + off) step))
+A pixel is kept iff its RAW cost satisfies C(p, best) <= q(min_score), q the cost formula above
+evaluated on the host in float32; a raw cost of 255 is therefore never kept -- smoothness may move a
+winner, it may not invent a measurement.  depth is NaN where the pixel is not kept.  Outputs: plane
+int32, cost uint8 (the raw C(p, best)), total uint16 (T_0; carried as int16 bits in torch), depth
+float32.  dense_check and everything behind it consume depth unchanged.  The volume and the total of a
+depth_maps call take 3 h w planes bytes, allocated once and reused for every view.
+
 Consistency (dense_check), float64.  A pixel of view i with a depth z becomes the NED point
 Ri^T (xn z, yn z, z) + Ci (expressions as above).  For each neighbour j it is projected into j
 (as above, with j's K): z' = its depth there, (u, v) its pixel; the neighbour agrees iff z' > 0,
@@ -101,6 +135,8 @@ from ._deps import getNode
 NEIGHBOUR_RATIO = (0.05, 0.6)          # baseline over median chain depth
 RANGE_MARGIN = 0.1
 MAX_SIDE = 1 << 20
+REGULARIZE = ('none', 'sgm')
+SGM_P1, SGM_P2 = 16, 128                 # the defaults of p1 / p2 (the table they come from)
 
 
 class View(object):
@@ -119,7 +155,10 @@ class View(object):
 
 class DepthMaps(object):
     """depth_maps()'s result, device tensors: plane int32 / score float32 / depth float32 [V, h, w]
-    (the sweep's), keep uint8 [V, h, w] (kept and consistent), ned float64 [V, h, w, 3]."""
+    (the sweep's), keep uint8 [V, h, w] (kept and consistent), ned float64 [V, h, w, 3].
+    regularize='sgm': plane and depth are the select's, score stays the sweep's winner's, and cost
+    uint8 / total int16 [V, h, w] (the raw cost and the summed path cost at the selected plane; 255 and
+    0 for a view that was not swept) come with them."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -325,11 +364,34 @@ def depth_range(matches, group, poses):
 # ---------------------------------------------------------------------------------------------
 # depth maps and fusion (device)
 # ---------------------------------------------------------------------------------------------
+def sgm_max_cost(min_score):
+    """q(min_score) of SEMI-GLOBAL RULES: the cost formula in float32 on the host"""
+    s = np.float32(min_score)
+    if np.isnan(s):
+        raise ValueError("min_score is a number")
+    c = np.rint((np.float32(1.0) - s) * np.float32(127.0))
+    return int(min(max(c, np.float32(0.0)), np.float32(254.0)))
+
+
+def sgm_parameters(planes, regularize='none', p1=None, p2=None, paths=8, c_invalid=127):
+    """the mode and its parameters checked on the host (ValueError) -> None for 'none', else
+    (planes, paths, p1, p2, c_invalid) with the defaults filled in"""
+    from . import kernels
+    if regularize not in REGULARIZE:
+        raise ValueError("regularize is one of %s, got %r" % (', '.join(REGULARIZE), regularize))
+    if regularize == 'none':
+        return None
+    return kernels.dense_sgm_check(planes, paths, SGM_P1 if p1 is None else p1, SGM_P2 if p2 is None else p2, c_invalid)
+
+
 def depth_maps(views, neighbours, ranges, planes=64, radius=3, min_var=4.0, min_score=0.6, eps=0.01,
-               min_agree=2, check=True):
+               min_agree=2, check=True, regularize='none', p1=None, p2=None, paths=8, c_invalid=127):
     """Sweep every view against its neighbours (positions in `views`) over its range (z_near, z_far),
     then the consistency rule over all maps (check=False: every kept pixel survives).  A view without
-    neighbours or without a range gets an empty map.  -> DepthMaps"""
+    neighbours or without a range gets an empty map.  regularize='sgm': SEMI-GLOBAL RULES stand between
+    the sweep and the winner (p1 / p2 default to SGM_P1 / SGM_P2, paths 4 or 8, 2 to 64 planes); the
+    cost volume and the total, 3 h w planes bytes, are allocated once and reused for every view.
+    -> DepthMaps"""
     import torch
     from . import kernels
     views = list(views)
@@ -338,6 +400,7 @@ def depth_maps(views, neighbours, ranges, planes=64, radius=3, min_var=4.0, min_
         raise ValueError("no views")
     if len(neighbours) != V or len(ranges) != V:
         raise ValueError("one neighbour list and one range per view")
+    sgm = sgm_parameters(planes, regularize, p1, p2, paths, c_invalid)
     kernels.dense_neighbour_table(neighbours, V)          # (checked before any device call)
     h, w = kernels._dense_size(views)
     for r in ranges:
@@ -348,16 +411,34 @@ def depth_maps(views, neighbours, ranges, planes=64, radius=3, min_var=4.0, min_
     score = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
     depth = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
     around = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    more = {}
+    if sgm is not None:
+        planes, paths, p1, p2, c_invalid = sgm
+        max_cost = sgm_max_cost(min_score)
+        volume = torch.empty((h, w, planes), dtype=torch.uint8, device=dev)
+        total = torch.empty((h, w, planes), dtype=torch.int16, device=dev)
+        wta_plane = torch.empty((h, w), dtype=torch.int32, device=dev)
+        wta_depth = torch.empty((h, w), dtype=torch.float32, device=dev)
+        more = dict(cost=torch.full((V, h, w), 255, dtype=torch.uint8, device=dev),
+                    total=torch.zeros((V, h, w), dtype=torch.int16, device=dev))
     for i, v in enumerate(views):
         if ranges[i] is None or len(neighbours[i]) == 0:
             continue
-        kernels.dense_sweep(v, [views[j] for j in neighbours[i]], 1.0 / float(ranges[i][1]), 1.0 / float(ranges[i][0]),
-                            planes, radius=radius, min_var=min_var, min_score=min_score,
-                            out=(plane[i], score[i], depth[i], around))
+        w_far, w_near = 1.0 / float(ranges[i][1]), 1.0 / float(ranges[i][0])
+        if sgm is None:
+            kernels.dense_sweep(v, [views[j] for j in neighbours[i]], w_far, w_near, planes, radius=radius,
+                                min_var=min_var, min_score=min_score, out=(plane[i], score[i], depth[i], around))
+            continue
+        kernels.dense_sweep(v, [views[j] for j in neighbours[i]], w_far, w_near, planes, radius=radius,
+                            min_var=min_var, min_score=min_score, out=(wta_plane, score[i], wta_depth, around),
+                            volume=volume)
+        kernels.dense_sgm_paths(volume, paths, p1, p2, c_invalid, out=(total,))
+        kernels.dense_sgm_select(total, volume, w_far, w_near, max_cost,
+                                 out=(plane[i], more['cost'][i], more['total'][i], depth[i]))
     keep, ned = kernels.dense_check(depth, views, neighbours, eps=eps, min_agree=min_agree)
     if not check:
         keep = torch.isfinite(depth).to(torch.uint8)
-    return DepthMaps(plane=plane, score=score, depth=depth, keep=keep, ned=ned)
+    return DepthMaps(plane=plane, score=score, depth=depth, keep=keep, ned=ned, **more)
 
 
 def frame_of(east_min, east_max, north_min, north_max, gsd):
@@ -412,10 +493,11 @@ def ply_bytes(xyz, intensity):
     return head.encode('ascii') + rec.tobytes()
 
 
-def save(surface, analysis_dir, points=None):
+def save(surface, analysis_dir, points=None, extra=None):
     """<analysis_dir>/dense/dsm.npy (float32, NaN: empty), count.npy (int32), dsm.wld (the world file
     of the raster, local ENU metres, pixel-centre convention), dense.json; points = (xyz, intensity):
-    points.ply as well.  -> the json's dict"""
+    points.ply as well; extra: a dict of further entries of dense.json (the semi-global mode's
+    parameters), appended after the others.  -> the json's dict"""
     import io
     from . import ortho, panda3d
     out_dir = os.path.join(analysis_dir, 'dense')
@@ -443,6 +525,8 @@ def save(surface, analysis_dir, points=None):
         panda3d._write_atomic(os.path.join(out_dir, 'points.ply'), ply_bytes(*points))
         info['files']['points'] = 'points.ply'
         info['points'] = int(len(points[0]))
+    if extra:
+        info.update(extra)
     panda3d._write_atomic(os.path.join(out_dir, 'dense.json'), (json.dumps(info, indent=2) + "\n").encode())
     return info
 

@@ -11,6 +11,7 @@ from . import _lib
 from ._lib import check, lib, require_gpu, stream_ptr
 
 I8, I32, I64, F64, U8 = torch.int8, torch.int32, torch.int64, torch.float64, torch.uint8
+I16 = torch.int16                        # the bits of a uint16 total of the semi-global mode (at most 4072)
 
 
 def _ptr(t):
@@ -2331,6 +2332,8 @@ def chain_depths(img_ptr, ned, pos, chain_ptr, chain_obs):
 # --------------------------------------------------------------------------------------
 DENSE_TILE = (32, 16)                    # a workgroup's reference pixels, (width, height)
 DENSE_MAX_RADIUS, DENSE_MAX_PLANES, DENSE_MAX_NEIGHBOURS, DENSE_MAX_SIDE = 7, 4096, 16, 16384
+DENSE_SGM_MAX_PLANES = 64                # semi-global mode: one plane per lane of a wave
+DENSE_SGM_DIRECTIONS = ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1))   # (dx, dy)
 
 
 def dense_camera(view):
@@ -2367,15 +2370,19 @@ def _dense_out(out, specs, dev):
     return out
 
 
-def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, min_score=0.6, out=None):
+def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, min_score=0.6, out=None, volume=None):
     """The plane sweep of one reference view (dense.py, THE RULES), one launch.  ref and the
     neighbours are views (G [h, w] float32, K, dist, R, C; the reference also rays [h, w, 2]), numpy
     or device.  -> device plane int32 [h, w], score float32 [h, w], depth float32 [h, w] (NaN where
-    not kept), around float32 [h, w, 3].  out: those four, allocated by the caller."""
+    not kept), around float32 [h, w, 3].  out: those four, allocated by the caller.  volume: a
+    contiguous device uint8 [h, w, planes] that receives the costs of SEMI-GLOBAL RULES beside them
+    (2 to 64 planes then)."""
     neighbours = list(neighbours)
     planes, radius = int(planes), int(radius)
     if not 1 <= planes <= DENSE_MAX_PLANES:
         raise ValueError("planes is 1 to %d, got %d" % (DENSE_MAX_PLANES, planes))
+    if volume is not None:
+        _dense_sgm_planes(planes)
     if not 1 <= radius <= DENSE_MAX_RADIUS:
         raise ValueError("radius is 1 to %d, got %d" % (DENSE_MAX_RADIUS, radius))
     if not 1 <= len(neighbours) <= DENSE_MAX_NEIGHBOURS:
@@ -2398,11 +2405,92 @@ def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, m
     cams = _dev(np.stack([dense_camera(v) for v in neighbours]), F64)
     plane, score, depth, around = _dense_out(out, [((h, w), I32), ((h, w), torch.float32), ((h, w), torch.float32),
                                                    ((h, w, 3), torch.float32)], dev)
-    check(lib().iamx_dense_sweep(_ptr(G), _ptr(rays), _ptr(N), _ptr(pose), _ptr(cams), w, h, len(neighbours),
-                                 planes, w_far, w_near, radius, float(min_var), float(min_score), _ptr(plane),
-                                 _ptr(score), _ptr(depth), _ptr(around), stream_ptr()), 'iamx_dense_sweep')
+    args = (_ptr(G), _ptr(rays), _ptr(N), _ptr(pose), _ptr(cams), w, h, len(neighbours), planes, w_far, w_near, radius,
+            float(min_var), float(min_score), _ptr(plane), _ptr(score), _ptr(depth), _ptr(around))
+    if volume is None:
+        check(lib().iamx_dense_sweep(*(args + (stream_ptr(),))), 'iamx_dense_sweep')
+    else:
+        volume, = _dense_out([volume], [((h, w, planes), U8)], dev)
+        check(lib().iamx_dense_sweep_volume(*(args + (_ptr(volume), stream_ptr()))), 'iamx_dense_sweep_volume')
     torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
     return plane, score, depth, around
+
+
+def _dense_sgm_planes(planes):
+    if not 2 <= planes <= DENSE_SGM_MAX_PLANES:
+        raise ValueError("semi-global mode takes 2 to %d planes, got %d" % (DENSE_SGM_MAX_PLANES, planes))
+
+
+def dense_sgm_check(planes, paths, p1, p2, c_invalid):
+    """the parameters of SEMI-GLOBAL RULES, checked on the host -> them as ints"""
+    planes, paths, p1, p2, c_invalid = int(planes), int(paths), int(p1), int(p2), int(c_invalid)
+    _dense_sgm_planes(planes)
+    if paths not in (4, 8):
+        raise ValueError("paths is 4 or 8, got %d" % paths)
+    if not 0 <= p1 <= p2 <= 255:
+        raise ValueError("0 <= P1 <= P2 <= 255 wanted, got %d and %d" % (p1, p2))
+    if not 0 <= c_invalid <= 254:
+        raise ValueError("c_invalid is 0 to 254, got %d" % c_invalid)
+    return planes, paths, p1, p2, c_invalid
+
+
+def _dense_volume(volume):
+    """a cost volume (numpy or device) -> device uint8 [h, w, planes], its sizes"""
+    if len(volume.shape) != 3 or min(volume.shape) < 1:
+        raise ValueError("a cost volume is [h, w, planes]")
+    h, w, planes = (int(x) for x in volume.shape)
+    _dense_sgm_planes(planes)
+    if h > DENSE_MAX_SIDE or w > DENSE_MAX_SIDE:
+        raise ValueError("a view side above %d pixels" % DENSE_MAX_SIDE)
+    return h, w, planes
+
+
+def dense_sgm_paths(volume, paths=8, p1=16, p2=128, c_invalid=127, out=None, direction=None):
+    """The path costs of SEMI-GLOBAL RULES summed over the first `paths` directions, one launch per
+    direction: volume uint8 [h, w, planes] (numpy or device).  -> device total [h, w, planes], the uint16 sums as
+    torch.int16 (they are at most 4072).
+    out: (total,), allocated by the caller; whatever it holds is overwritten.  direction = 0 .. 7: that
+    direction's L_r alone, one launch."""
+    h, w, planes = _dense_volume(volume)
+    planes, paths, p1, p2, c_invalid = dense_sgm_check(planes, paths, p1, p2, c_invalid)
+    if direction is not None and not 0 <= int(direction) < 8:
+        raise ValueError("direction is 0 to 7")
+    dev = require_gpu()
+    vol = _dev(volume, U8)
+    total, = _dense_out(out, [((h, w, planes), I16)], dev)
+    if direction is None:
+        check(lib().iamx_dense_sgm_paths(_ptr(vol), w, h, planes, paths, p1, p2, c_invalid, _ptr(total), stream_ptr()),
+              'iamx_dense_sgm_paths')
+    else:
+        check(lib().iamx_dense_sgm_direction(_ptr(vol), w, h, planes, int(direction), 0, p1, p2, c_invalid, _ptr(total),
+                                             stream_ptr()), 'iamx_dense_sgm_direction')
+    torch.cuda.current_stream().synchronize()
+    return total
+
+
+def dense_sgm_select(total, volume, w_far, w_near, max_cost, out=None):
+    """The select of SEMI-GLOBAL RULES: total (int16 bits of the uint16 sums) and volume uint8 [h, w, planes] (numpy or device),
+    the planes uniform in inverse depth from w_far to w_near, max_cost = q(min_score).  -> device plane
+    int32, cost uint8, total at the winner int16, depth float32 (NaN where not kept), all [h, w].
+    out: those four."""
+    h, w, planes = _dense_volume(volume)
+    if tuple(total.shape) != (h, w, planes):
+        raise ValueError("total has the volume's shape %r" % ((h, w, planes),))
+    w_far, w_near, max_cost = float(w_far), float(w_near), int(max_cost)
+    if not (w_far > 0.0 and w_near > w_far and math.isfinite(w_near)):
+        raise ValueError("inverse depths with 0 < w_far < w_near wanted, got %r and %r" % (w_far, w_near))
+    if not 0 <= max_cost <= 254:
+        raise ValueError("max_cost is 0 to 254, got %d" % max_cost)
+    dev = require_gpu()
+    vol = _dev(volume, U8)
+    tot = _dev(total, I16)
+    plane, cost, tot0, depth = _dense_out(out, [((h, w), I32), ((h, w), U8), ((h, w), I16),
+                                                ((h, w), torch.float32)], dev)
+    step = (w_near - w_far) / (planes - 1)
+    check(lib().iamx_dense_sgm_select(_ptr(tot), _ptr(vol), w, h, planes, w_far, step, max_cost, _ptr(plane), _ptr(cost),
+                                      _ptr(tot0), _ptr(depth), stream_ptr()), 'iamx_dense_sgm_select')
+    torch.cuda.current_stream().synchronize()
+    return plane, cost, tot0, depth
 
 
 def dense_neighbour_table(neighbours, n_views):

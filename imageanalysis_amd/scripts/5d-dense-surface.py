@@ -3,7 +3,8 @@
 surface is the sparse chains' triangulation): plane-sweep depth maps of one group's images against
 their best neighbours, cross-checked between views and fused into a height raster on the device
 (imageanalysis_amd/dense.py), written as <analysis_dir>/dense/dsm.npy, count.npy, dsm.wld and
-dense.json, with --ply the surviving points as dense/points.ply.
+dense.json, with --ply the surviving points as dense/points.ply.  --regularize sgm puts the semi-global
+aggregation of dense.py's SEMI-GLOBAL RULES between the cost volume and the winner (2 to 64 planes).
 Run from the reference's scripts/ directory: python <repo>/imageanalysis_amd/scripts/5d-dense-surface.py PROJECT
 """
 import argparse
@@ -25,7 +26,15 @@ ap.add_argument('--radius', type=int, default=3, help='correlation window radius
 ap.add_argument('--min-score', type=float, default=0.6, help='least mean correlation of a kept pixel')
 ap.add_argument('--gsd', type=float, default=0.0, help='metres per cell (default: the sweep pixel\'s footprint at the median depth)')
 ap.add_argument('--ply', action='store_true', help='write the surviving points as dense/points.ply')
+ap.add_argument('--regularize', choices=dense.REGULARIZE, default='none', help='none: winner-take-all; sgm: semi-global aggregation')
+ap.add_argument('--p1', type=int, default=dense.SGM_P1, help='sgm: penalty of a change by one plane')
+ap.add_argument('--p2', type=int, default=dense.SGM_P2, help='sgm: penalty of a larger change, P1 <= P2 <= 255')
+ap.add_argument('--paths', type=int, choices=(4, 8), default=8, help='sgm: directions aggregated')
 args = ap.parse_args()
+try:
+    sgm = dense.sgm_parameters(args.planes, args.regularize, args.p1, args.p2, args.paths)
+except ValueError as e:
+    ap.error(str(e))
 
 proj = project.ProjectMgr(args.project)
 proj.load_images_info()
@@ -44,7 +53,8 @@ ranges = dense.depth_range(matches, group, poses)
 swept = sum(1 for n, r in zip(neighbours, ranges) if n and r is not None)
 print('Views: %d of %d x %d pixels, %d with neighbours and a depth range' % (len(views), views[0].G.shape[1],
                                                                             views[0].G.shape[0], swept))
-maps = dense.depth_maps(views, neighbours, ranges, planes=args.planes, radius=args.radius, min_score=args.min_score)
+mode = {} if sgm is None else dict(regularize=args.regularize, p1=sgm[2], p2=sgm[3], paths=sgm[1])
+maps = dense.depth_maps(views, neighbours, ranges, planes=args.planes, radius=args.radius, min_score=args.min_score, **mode)
 gsd = args.gsd
 if gsd <= 0.0:
     mids = sorted(0.5 * (r[0] + r[1]) for r in ranges if r is not None)
@@ -52,7 +62,8 @@ if gsd <= 0.0:
         raise SystemExit("no image of group %d observes a positioned chain" % args.group)
     gsd = mids[len(mids) // 2] / float(views[0].K[0])
 surface = dense.fuse(views, maps, gsd)
-info = dense.save(surface, proj.analysis_dir, points=dense.surface_points(views, maps) if args.ply else None)
+info = dense.save(surface, proj.analysis_dir, points=dense.surface_points(views, maps) if args.ply else None,
+                  extra=mode)
 print('DSM: %d x %d cells at %.3f m, %d of them filled by %d points, %.1f s'
       % (info['width'], info['height'], gsd, info['cells_filled'], info['points_fused'], time.perf_counter() - t0))
 print('Wrote %s to %s/dense' % (', '.join(sorted(info['files'].values())), proj.analysis_dir))

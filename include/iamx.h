@@ -1825,6 +1825,45 @@ int iamx_dense_resolve(const int32_t *count, const int64_t *sum, int width, int 
                        void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Dense surface, semi-global aggregation (csrc/dense_sgm.hip, the emission in csrc/dense_sweep.hip):
+ * the layer between the sweep's cost volume and the winner.  The rules are stated in
+ * imageanalysis_amd/dense.py ("SEMI-GLOBAL RULES") and restated in numpy by
+ * tests/dense_sgm_restatement.py; the device follows them bit for bit.  All pointers DEV.
+ *
+ * volume [h][w][planes] uint8, planes contiguous: the cost C of (pixel, plane), 255 where the sweep's
+ * aggregate score is invalid, else clamp(rint((1 - S) 127), 0, 254).  total [h][w][planes] uint16:
+ * the sum T of the directions' path costs, at most 8 (254 + 255) = 4072.  2 <= planes <=
+ * IAMX_DENSE_SGM_MAX_PLANES (one plane per lane of a wave).
+ *
+ * iamx_dense_sweep_volume: iamx_dense_sweep with the same arguments and the same four outputs, and
+ *   volume written beside them (every pixel, every plane); volume is aligned to 4 bytes.
+ * iamx_dense_sgm_direction, one launch: the path costs L_r of direction 0 .. 7 (in the rules' order:
+ *   (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1) (-1,1) as (dx, dy)), one wave per path; accumulate
+ *   0: total = L_r (every element is written), else total += L_r.  0 <= p1 <= p2 <= 255, c_invalid
+ *   0 .. 254 stands in for a cost of 255.
+ * iamx_dense_sgm_paths: the first `paths` (4 or 8) directions, stream ordered, the first one storing
+ *   and the others adding: total needs no zeroing by the caller and nothing of its old content stays.
+ * iamx_dense_sgm_select, one wave per pixel: plane [h][w] = argmin_d T (the smallest d on a tie, never
+ *   -1), cost [h][w] = the raw C there, tot0 [h][w] = T there, depth [h][w] = the sub-plane depth
+ *   where cost <= max_cost (0 .. 254), NaN elsewhere; step = (w_near - w_far) / (planes - 1) > 0.
+ * A size or a parameter out of range, a null pointer: IAMX_EINVAL without a launch.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_DENSE_SGM_MAX_PLANES 64
+int iamx_dense_sweep_volume(const float *ref, const double *rays, const float *nbr,
+                            const double *ref_pose, const double *nbr_cam, int width, int height,
+                            int num_nbr, int planes, double w_far, double w_near, int radius,
+                            float min_var, float min_score, int32_t *plane, float *score, float *depth,
+                            float *around, uint8_t *volume, void *stream);
+int iamx_dense_sgm_direction(const uint8_t *volume, int width, int height, int planes, int direction,
+                             int accumulate, int p1, int p2, int c_invalid, uint16_t *total,
+                             void *stream);
+int iamx_dense_sgm_paths(const uint8_t *volume, int width, int height, int planes, int paths, int p1,
+                         int p2, int c_invalid, uint16_t *total, void *stream);
+int iamx_dense_sgm_select(const uint16_t *total, const uint8_t *volume, int width, int height,
+                          int planes, double w_far, double step, int max_cost, int32_t *plane,
+                          uint8_t *cost, uint16_t *tot0, float *depth, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * True orthophoto (csrc/ortho_dsm.hip): a group's frames draped over the dense DSM, every mosaic
  * pixel placed at its DSM height, projected through the full camera model and coloured only from
  * the frames that see it.  The rules are stated in imageanalysis_amd/ortho.py ("THE TRUE-ORTHO
