@@ -28,10 +28,20 @@
 // multiple of 4 and stores bytes otherwise.  sweep_kernel<R, false> never reads its volume argument and
 // compiles to the instructions of the kernel before the emission existed.
 //
+// sweep_kernel<R, false, true> (iamx_dense_sweep_guided) is the same kernel again with the plane loop's
+// bounds read from a table (dense.py's REFINEMENT RULES): the workgroup of tile (bx, by) walks the planes
+// first <= d < first + count of entry by tiles_x + bx, out of planes_total global planes.  Every lane loads
+// the same two ints, so the bounds, and with them every barrier, are uniform in the workgroup; a window of
+// no planes runs the loop zero times and the workgroup writes its empty pixels at the end like any other.
+// The plane index, the depths, the winner and the parabola are the global d's; a winner on a rim of its
+// window that is not a rim of the plane set loses its depth (the window-edge rule).  No volume in this form.
+//
 // check_kernel: one thread per pixel of every depth map.  splat_kernel: one thread per point,
 // integer atomics only (a 32-bit count and a 64-bit sum of rint(up 1024) per cell), so the result
 // does not depend on scheduling.  resolve_kernel: sum / 1024 / count.
 #include <math.h>
+
+#include <vector>
 
 #include "iamx_common.h"
 
@@ -135,7 +145,8 @@ struct Winner {
     }
 };
 
-__device__ __forceinline__ void write_pixel(const SweepArgs &A, int g, const Winner &W)
+// clipped: the winner stands on a rim of its tile's window that is not a rim of the plane set (the guided form)
+__device__ __forceinline__ void write_pixel(const SweepArgs &A, int g, const Winner &W, bool clipped = false)
 {
     float off = 0.0f;
     if (W.best >= 0 && W.sm == W.sm && W.sp == W.sp) {
@@ -146,7 +157,7 @@ __device__ __forceinline__ void write_pixel(const SweepArgs &A, int g, const Win
         }
     }
     float depth = qnan();
-    if (W.best >= 0 && W.s0 >= A.min_score)
+    if (W.best >= 0 && W.s0 >= A.min_score && !clipped)
         depth = (float)(1.0 / (A.w_far + ((double)W.best + (double)off) * A.step));
     A.plane[g] = W.best;
     A.score[g] = W.s0;
@@ -167,9 +178,13 @@ __device__ __forceinline__ uint32_t cost_of(float S)
 
 // VOL: the costs of the thread's two pixels go to volume [h][w][planes] as well, four planes to a
 // dword store where planes is a multiple of 4 (pixel g's row then starts on a dword), bytes otherwise
-template <int R, bool VOL>
-__global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__restrict__ volume)
+// GUIDED: the planes walked are the tile's window of `windows` [tiles_y][tiles_x][2] = (first, count),
+// A.planes is the size of the global plane set, and the window-edge rule applies
+template <int R, bool VOL, bool GUIDED = false>
+__global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__restrict__ volume,
+                                                        const int32_t *__restrict__ windows)
 {
+    static_assert(!(VOL && GUIDED), "the guided form emits no volume");
     constexpr int K = 2 * R + 1;                         // window side
     constexpr int TW = TILE_W + 2 * R, TH = TILE_H + 2 * R;
     constexpr int NPOS = (TW * TH + THREADS - 1) / THREADS;
@@ -259,7 +274,13 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__
     uint8_t *__restrict__ vol0 = VOL ? volume + ((int64_t)py * w + px) * A.planes : nullptr;
     uint32_t pk0 = 0, pk1 = 0;
     int buf = 0;
-    for (int d = 0; d < A.planes; ++d) {
+    int d_first = 0, d_end = A.planes;
+    if constexpr (GUIDED) {
+        const int32_t *__restrict__ e = windows + 2 * ((int64_t)blockIdx.y * gridDim.x + blockIdx.x);
+        d_first = e[0];
+        d_end = d_first + e[1];
+    }
+    for (int d = d_first; d < d_end; ++d) {
         const double z = 1.0 / (A.w_far + (double)d * A.step);
         float sum0 = 0.0f, sum1 = 0.0f;
         int cnt0 = 0, cnt1 = 0;
@@ -354,6 +375,14 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__
             }
         }
     }
+    if constexpr (GUIDED) {
+        const int lo = d_first > 0 ? d_first : -2, hi = d_end < A.planes ? d_end - 1 : -2;   // (-2: a rim of the set)
+        if (py < h) {
+            if (px < w) write_pixel(A, py * w + px, W0, W0.best == lo || W0.best == hi);
+            if (px + 1 < w) write_pixel(A, py * w + px + 1, W1, W1.best == lo || W1.best == hi);
+        }
+        return;
+    }
     if (py < h) {
         if (px < w) write_pixel(A, py * w + px, W0);
         if (px + 1 < w) write_pixel(A, py * w + px + 1, W1);
@@ -361,14 +390,21 @@ __global__ __launch_bounds__(THREADS) void sweep_kernel(SweepArgs A, uint8_t *__
 }
 
 template <int R>
-int launch_sweep(const SweepArgs &A, uint8_t *volume, void *stream)
+int launch_sweep(const SweepArgs &A, uint8_t *volume, const int32_t *windows, void *stream)
 {
     const dim3 grid((A.w + TILE_W - 1) / TILE_W, (A.h + TILE_H - 1) / TILE_H);
+    if (windows) {
+        hipLaunchKernelGGL((sweep_kernel<R, false, true>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A,
+                           (uint8_t *)nullptr, windows);
+        return iamx::check_launch("iamx_dense_sweep_guided");
+    }
     if (volume) {
-        hipLaunchKernelGGL((sweep_kernel<R, true>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, volume);
+        hipLaunchKernelGGL((sweep_kernel<R, true>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, volume,
+                           (const int32_t *)nullptr);
         return iamx::check_launch("iamx_dense_sweep_volume");
     }
-    hipLaunchKernelGGL((sweep_kernel<R, false>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, (uint8_t *)nullptr);
+    hipLaunchKernelGGL((sweep_kernel<R, false>), grid, dim3(THREADS), 0, iamx::as_stream(stream), A, (uint8_t *)nullptr,
+                       (const int32_t *)nullptr);
     return iamx::check_launch("iamx_dense_sweep");
 }
 
@@ -455,15 +491,36 @@ __global__ __launch_bounds__(THREADS) void resolve_kernel(const int32_t *__restr
 static int dense_sweep_entry(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
                                 const double *nbr_cam, int width, int height, int num_nbr, int planes,
                                 double w_far, double w_near, int radius, float min_var, float min_score,
-                                int32_t *plane, float *score, float *depth, float *around, uint8_t *volume, void *stream)
+                                int32_t *plane, float *score, float *depth, float *around, uint8_t *volume,
+                                const int32_t *windows, void *stream)
 {
-    IAMX_REQUIRE(planes >= 1 && planes <= IAMX_DENSE_MAX_PLANES, "planes out of range");
+    if (windows)
+        IAMX_REQUIRE(planes >= 2 && planes <= IAMX_DENSE_GUIDED_MAX_PLANES, "planes_total out of range");
+    else
+        IAMX_REQUIRE(planes >= 1 && planes <= IAMX_DENSE_MAX_PLANES, "planes out of range");
     IAMX_REQUIRE(radius >= 1 && radius <= IAMX_DENSE_MAX_RADIUS, "radius out of range");
     IAMX_REQUIRE(num_nbr >= 1 && num_nbr <= IAMX_DENSE_MAX_NEIGHBOURS, "neighbour count out of range");
     IAMX_REQUIRE(width >= 1 && height >= 1 && width <= IAMX_DENSE_MAX_SIDE && height <= IAMX_DENSE_MAX_SIDE,
                  "image size out of range");
     IAMX_REQUIRE(w_far > 0.0 && w_near > w_far && w_near < INFINITY, "0 < w_far < w_near wanted");
     IAMX_REQUIRE(ref && rays && nbr && ref_pose && nbr_cam && plane && score && depth && around, "null pointer");
+    if (windows) {
+        // the table is small (8 bytes per tile): read it back and refuse an entry outside the plane set
+        const size_t tiles = (size_t)((width + TILE_W - 1) / TILE_W) * (size_t)((height + TILE_H - 1) / TILE_H);
+        std::vector<int32_t> tab(2 * tiles);
+        hipStream_t s = iamx::as_stream(stream);
+        if (hipMemcpyAsync(tab.data(), windows, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipGetLastError();
+            return iamx::fail(IAMX_ELAUNCH, "%s: the window table could not be read", "iamx_dense_sweep_guided");
+        }
+        for (size_t t = 0; t < tiles; ++t) {
+            const int64_t first = tab[2 * t], count = tab[2 * t + 1];
+            if (first < 0 || count < 0 || first + count > planes)
+                return iamx::fail(IAMX_EINVAL, "%s: window %zu = (%d, %d) leaves the %d planes", "iamx_dense_sweep_guided",
+                                  t, (int)first, (int)count, planes);
+        }
+    }
     SweepArgs A;
     A.ref = ref; A.rays = rays; A.nbr = nbr; A.ref_pose = ref_pose; A.nbr_cam = nbr_cam;
     A.w = width; A.h = height; A.n = num_nbr; A.planes = planes;
@@ -474,13 +531,13 @@ static int dense_sweep_entry(const float *ref, const double *rays, const float *
     A.min_score = min_score;
     A.plane = plane; A.score = score; A.depth = depth; A.around = around;
     switch (radius) {
-        case 1: return launch_sweep<1>(A, volume, stream);
-        case 2: return launch_sweep<2>(A, volume, stream);
-        case 3: return launch_sweep<3>(A, volume, stream);
-        case 4: return launch_sweep<4>(A, volume, stream);
-        case 5: return launch_sweep<5>(A, volume, stream);
-        case 6: return launch_sweep<6>(A, volume, stream);
-        default: return launch_sweep<7>(A, volume, stream);
+        case 1: return launch_sweep<1>(A, volume, windows, stream);
+        case 2: return launch_sweep<2>(A, volume, windows, stream);
+        case 3: return launch_sweep<3>(A, volume, windows, stream);
+        case 4: return launch_sweep<4>(A, volume, windows, stream);
+        case 5: return launch_sweep<5>(A, volume, windows, stream);
+        case 6: return launch_sweep<6>(A, volume, windows, stream);
+        default: return launch_sweep<7>(A, volume, windows, stream);
     }
 }
 
@@ -490,7 +547,18 @@ extern "C" int iamx_dense_sweep(const float *ref, const double *rays, const floa
                                 int32_t *plane, float *score, float *depth, float *around, void *stream)
 {
     return dense_sweep_entry(ref, rays, nbr, ref_pose, nbr_cam, width, height, num_nbr, planes, w_far, w_near, radius,
-                             min_var, min_score, plane, score, depth, around, nullptr, stream);
+                             min_var, min_score, plane, score, depth, around, nullptr, nullptr, stream);
+}
+
+extern "C" int iamx_dense_sweep_guided(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
+                                       const double *nbr_cam, int width, int height, int num_nbr, int planes_total,
+                                       double w_far, double w_near, int radius, float min_var, float min_score,
+                                       const int32_t *windows, int32_t *plane, float *score, float *depth, float *around,
+                                       void *stream)
+{
+    IAMX_REQUIRE(windows, "null pointer");
+    return dense_sweep_entry(ref, rays, nbr, ref_pose, nbr_cam, width, height, num_nbr, planes_total, w_far, w_near,
+                             radius, min_var, min_score, plane, score, depth, around, nullptr, windows, stream);
 }
 
 extern "C" int iamx_dense_sweep_volume(const float *ref, const double *rays, const float *nbr, const double *ref_pose,
@@ -503,7 +571,7 @@ extern "C" int iamx_dense_sweep_volume(const float *ref, const double *rays, con
     IAMX_REQUIRE(volume, "null pointer");
     IAMX_REQUIRE(((uintptr_t)volume & 3) == 0, "the volume is aligned to 4 bytes");
     return dense_sweep_entry(ref, rays, nbr, ref_pose, nbr_cam, width, height, num_nbr, planes, w_far, w_near, radius,
-                             min_var, min_score, plane, score, depth, around, volume, stream);
+                             min_var, min_score, plane, score, depth, around, volume, nullptr, stream);
 }
 
 extern "C" int iamx_dense_check(const float *depth, const double *rays, const double *cams, const int32_t *nbr,

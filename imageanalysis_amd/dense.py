@@ -7,6 +7,9 @@ surface is the sparse chains' Delaunay triangulation).
     depth_range(matches, group, poses)                   per image, (z_near, z_far) from its chains
     depth_maps(views, neighbours, ranges, planes=64, ...)   sweep every view, cross-check -> DepthMaps
                                                          (regularize='sgm': SEMI-GLOBAL RULES)
+    refine_planes(planes, ratio)                         the size T of the next level's plane set
+    refine(views, neighbours, ranges, coarse, planes, ratio=4, ...)   one finer level, swept only around
+                                                         the coarse depths -> DepthMaps (REFINEMENT RULES)
     fuse(views, depths, gsd)                             surviving points -> Surface (dsm, count)
     save(surface, analysis_dir, points=None)             dense/dsm.npy, count.npy, dsm.wld, dense.json
     load(analysis_dir)                                   the inverse of save -> Surface
@@ -93,6 +96,48 @@ winner, it may not invent a measurement.  depth is NaN where the pixel is not ke
 int32, cost uint8 (the raw C(p, best)), total uint16 (T_0; carried as int16 bits in torch), depth
 float32.  dense_check and everything behind it consume depth unchanged.  The volume and the total of a
 depth_maps call take 3 h w planes bytes, allocated once and reused for every view.
+
+REFINEMENT RULES (refine(); kernels: csrc/dense_refine.hip and the guided form of csrc/dense_sweep.hip;
+restated by tests/dense_refine_restatement.py).  A coarse level's depth map says where the surface is; the
+fine level sweeps, per tile, a window of a larger plane set around it.
+
+Fine plane set.  For a view with range (w_far, w_near), T planes uniform in inverse depth:
+    step_f = (w_near - w_far) / (T - 1)      z_d = 1 / (w_far + (double)d step_f)     (the sweep's expression)
+refine_planes(planes, ratio) = (planes - 1) ratio + 1, so coarse plane k is fine plane k ratio.
+2 <= T <= IAMX_DENSE_GUIDED_MAX_PLANES = 65536 (IAMX_DENSE_MAX_PLANES, the plain sweep's, stays 4096).
+
+Window table.  int32 [tiles_y][tiles_x][2] = (first, count) over the sweep's 32 x 16 tiles in row-major
+order, tiles_x = ceil(w / 32), tiles_y = ceil(h / 16).  An entry has 0 <= first, 0 <= count and
+first + count <= T; anything else is a ValueError on the host and an error of the C entry, without a launch.
+
+Guided sweep.  For pixel p of tile t, S_d(p) is THE RULES' aggregate for first_t <= d < first_t + count_t;
+every other plane is not swept: its score is invalid.  Winner, tie rule, around = (s_m, s_0, s_p) and the
+float32 offset are THE RULES' with the global d, so s_m is NaN at best = first_t, s_p is NaN at the window's
+last plane, and off = 0 there.  depth = float32(1 / (w_far + (best + off) step_f)) in float64.  A pixel is
+kept iff best >= 0, s_0 >= min_score, and (the window-edge rule) neither best = first_t with first_t > 0
+nor best = first_t + count_t - 1 with first_t + count_t < T: a winner on a rim of its window that is not a
+rim of the plane set may be a clipped peak.  plane, score and around are written for every pixel regardless;
+a tile with count = 0 writes plane = -1 and NaN everywhere.  With every entry (0, T) and T <= 4096 the four
+outputs are the plain sweep's with planes = T, bit for bit.
+
+Guide.  From the coarse depth map Dc [hc][wc] float32 (NaN: none), the fine size (h, w), (w_far, w_near, T),
+the radius r and pad >= 0.  For tile (tx, ty), in integers:
+    fine columns    x0 = max(32 tx - r, 0), x1 = min(32 tx + 31 + r, w - 1)        rows: 16 and h
+    coarse columns  c0 = max(((2 x0 + 1) wc) div (2 w) - 1, 0)
+                    c1 = min(((2 x1 + 1) wc) div (2 w) + 1, wc - 1)                 rows: hc and h
+(the coarse pixel under the fine pixel's centre, one more either side; the size ratio need not be 2).  Over
+the entries of that box that are finite and > 0, in float64 with every operation rounded on its own:
+    wv = 1.0 / (double)Dc,  wmin = min wv,  wmax = max wv         (order-free: no reduction order to fix)
+    lo = floor((wmin - w_far) / step_f) - pad,  hi = ceil((wmax - w_far) / step_f) + pad
+both clamped into [0, T - 1] (floor and ceil are whole numbers; the pad and the clamp are exact in whatever
+arithmetic holds them, so a depth far outside the range lands on an end of the set).  The window is
+(lo, hi - lo + 1), and (0, 0) for a box without such an entry.  pad defaults to ratio: one coarse step.
+
+refine.  The guide depth of view i is coarse.depth[i] where coarse.keep[i] != 0 and NaN elsewhere -- the
+coarse level's consistency check decides what may guide.  The coarse level may be semi-global; the fine
+level is winner-take-all inside its windows.  dense_check runs over the fine maps as above.  A view
+without a range or neighbours gets an empty map, and so does one whose coarse map kept nothing (every
+window is (0, 0)).  Levels chain: a refine()'s result is the `coarse` of the next with planes = T.
 
 Consistency (dense_check), float64.  A pixel of view i with a depth z becomes the NED point
 Ri^T (xn z, yn z, z) + Ci (expressions as above).  For each neighbour j it is projected into j
@@ -439,6 +484,78 @@ def depth_maps(views, neighbours, ranges, planes=64, radius=3, min_var=4.0, min_
     if not check:
         keep = torch.isfinite(depth).to(torch.uint8)
     return DepthMaps(plane=plane, score=score, depth=depth, keep=keep, ned=ned, **more)
+
+
+def refine_planes(planes, ratio):
+    """T of REFINEMENT RULES: the size of the fine plane set whose plane k ratio is coarse plane k"""
+    from . import kernels
+    planes, ratio = int(planes), int(ratio)
+    if planes < 2:
+        raise ValueError("a level that is refined has at least 2 planes, got %d" % planes)
+    if ratio < 1:
+        raise ValueError("ratio is at least 1, got %d" % ratio)
+    total = (planes - 1) * ratio + 1
+    if total > kernels.DENSE_GUIDED_MAX_PLANES:
+        raise ValueError("(%d - 1) %d + 1 = %d planes, above %d" % (planes, ratio, total, kernels.DENSE_GUIDED_MAX_PLANES))
+    return total
+
+
+def refine(views, neighbours, ranges, coarse, planes, ratio=4, pad=None, radius=3, min_var=4.0, min_score=0.6,
+           eps=0.01, min_agree=2, check=True):
+    """One finer level (REFINEMENT RULES).  views: the fine views, the cameras of the coarse call in its
+    order at any larger size; coarse: that call's DepthMaps (depth_maps(), with regularize='sgm' or
+    without, or an earlier refine()); planes: its plane count.  Per view the guide turns the coarse
+    depths that survived (coarse.keep) into a window per tile of the T = refine_planes(planes, ratio)
+    fine planes (pad: planes added either side, default ratio), the guided sweep walks them winner-take-all,
+    and the consistency rule runs over the fine maps.  A view without neighbours or a range gets an empty
+    map, and so does one whose coarse map kept nothing.  -> DepthMaps with plane (indices in the T planes),
+    score, depth, keep, ned, windows int32 [V, tiles_y, tiles_x, 2] and total = T; a valid `coarse`
+    of the next level with planes = T."""
+    import torch
+    from . import kernels
+    views = list(views)
+    V = len(views)
+    if V == 0:
+        raise ValueError("no views")
+    if len(neighbours) != V or len(ranges) != V:
+        raise ValueError("one neighbour list and one range per view")
+    total = refine_planes(planes, ratio)
+    pad = int(ratio) if pad is None else int(pad)
+    if not 0 <= pad <= kernels.DENSE_GUIDED_MAX_PLANES:
+        raise ValueError("pad is 0 to %d planes, got %d" % (kernels.DENSE_GUIDED_MAX_PLANES, pad))
+    if not 1 <= int(radius) <= kernels.DENSE_MAX_RADIUS:
+        raise ValueError("radius is 1 to %d, got %d" % (kernels.DENSE_MAX_RADIUS, radius))
+    c_shape, k_shape = tuple(coarse.depth.shape), tuple(coarse.keep.shape)
+    if len(c_shape) != 3 or k_shape != c_shape:
+        raise ValueError("the coarse level carries depth and keep [V, hc, wc]")
+    if c_shape[0] != V:
+        raise ValueError("the coarse level has %d views, the fine one %d" % (c_shape[0], V))
+    kernels.dense_neighbour_table(neighbours, V)          # (checked before any device call)
+    h, w = kernels._dense_size(views)
+    for r in ranges:
+        if r is not None and not (0.0 < float(r[0]) < float(r[1]) < float('inf')):
+            raise ValueError("a range is 0 < z_near < z_far, got %r" % (r,))
+    dev = kernels.require_gpu()
+    c_depth = kernels._dev(coarse.depth, torch.float32)
+    c_keep = kernels._dev(coarse.keep, torch.uint8)
+    plane = torch.full((V, h, w), -1, dtype=torch.int32, device=dev)
+    score = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
+    depth = torch.full((V, h, w), float('nan'), dtype=torch.float32, device=dev)
+    around = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    windows = torch.zeros((V,) + kernels.dense_tiles(h, w) + (2,), dtype=torch.int32, device=dev)
+    nan = torch.full(c_shape[1:], float('nan'), dtype=torch.float32, device=dev)
+    for i, v in enumerate(views):
+        if ranges[i] is None or len(neighbours[i]) == 0:
+            continue
+        w_far, w_near = 1.0 / float(ranges[i][1]), 1.0 / float(ranges[i][0])
+        kernels.dense_guide(torch.where(c_keep[i] != 0, c_depth[i], nan), (h, w), w_far, w_near, total, radius=radius,
+                            pad=pad, out=windows[i])
+        kernels.dense_sweep_guided(v, [views[j] for j in neighbours[i]], w_far, w_near, total, windows[i], radius=radius,
+                                   min_var=min_var, min_score=min_score, out=(plane[i], score[i], depth[i], around))
+    keep, ned = kernels.dense_check(depth, views, neighbours, eps=eps, min_agree=min_agree)
+    if not check:
+        keep = torch.isfinite(depth).to(torch.uint8)
+    return DepthMaps(plane=plane, score=score, depth=depth, keep=keep, ned=ned, windows=windows, total=total)
 
 
 def frame_of(east_min, east_max, north_min, north_max, gsd):

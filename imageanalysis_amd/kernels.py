@@ -2333,6 +2333,7 @@ def chain_depths(img_ptr, ned, pos, chain_ptr, chain_obs):
 DENSE_TILE = (32, 16)                    # a workgroup's reference pixels, (width, height)
 DENSE_MAX_RADIUS, DENSE_MAX_PLANES, DENSE_MAX_NEIGHBOURS, DENSE_MAX_SIDE = 7, 4096, 16, 16384
 DENSE_SGM_MAX_PLANES = 64                # semi-global mode: one plane per lane of a wave
+DENSE_GUIDED_MAX_PLANES = 65536          # the guided sweep's whole plane set (a tile walks a window of it)
 DENSE_SGM_DIRECTIONS = ((1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, -1), (1, -1), (-1, 1))   # (dx, dy)
 
 
@@ -2370,19 +2371,9 @@ def _dense_out(out, specs, dev):
     return out
 
 
-def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, min_score=0.6, out=None, volume=None):
-    """The plane sweep of one reference view (dense.py, THE RULES), one launch.  ref and the
-    neighbours are views (G [h, w] float32, K, dist, R, C; the reference also rays [h, w, 2]), numpy
-    or device.  -> device plane int32 [h, w], score float32 [h, w], depth float32 [h, w] (NaN where
-    not kept), around float32 [h, w, 3].  out: those four, allocated by the caller.  volume: a
-    contiguous device uint8 [h, w, planes] that receives the costs of SEMI-GLOBAL RULES beside them
-    (2 to 64 planes then)."""
-    neighbours = list(neighbours)
-    planes, radius = int(planes), int(radius)
-    if not 1 <= planes <= DENSE_MAX_PLANES:
-        raise ValueError("planes is 1 to %d, got %d" % (DENSE_MAX_PLANES, planes))
-    if volume is not None:
-        _dense_sgm_planes(planes)
+def _dense_sweep_check(ref, neighbours, w_far, w_near, radius):
+    """the arguments that every form of the sweep shares, on the host -> (h, w, w_far, w_near, radius)"""
+    radius = int(radius)
     if not 1 <= radius <= DENSE_MAX_RADIUS:
         raise ValueError("radius is 1 to %d, got %d" % (DENSE_MAX_RADIUS, radius))
     if not 1 <= len(neighbours) <= DENSE_MAX_NEIGHBOURS:
@@ -2393,7 +2384,11 @@ def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, m
         raise ValueError("inverse depths with 0 < w_far < w_near wanted, got %r and %r" % (w_far, w_near))
     if ref.rays is None or tuple(ref.rays.shape) != (h, w, 2):
         raise ValueError("the reference view carries rays [h, w, 2]")
-    dev = require_gpu()
+    return h, w, w_far, w_near, radius
+
+
+def _dense_sweep_upload(ref, neighbours, h, w):
+    """-> the reference's grey plane and rays, the neighbours' planes [n, h, w], its pose, their cameras"""
     G = _dev(ref.G, torch.float32)
     rays = _dev(ref.rays, F64)
     planes_n = [_dev(v.G, torch.float32) for v in neighbours]
@@ -2403,6 +2398,25 @@ def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, m
         N = torch.stack(planes_n).contiguous()
     pose = _dev(dense_camera(ref)[:12], F64)
     cams = _dev(np.stack([dense_camera(v) for v in neighbours]), F64)
+    return G, rays, N, pose, cams
+
+
+def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, min_score=0.6, out=None, volume=None):
+    """The plane sweep of one reference view (dense.py, THE RULES), one launch.  ref and the
+    neighbours are views (G [h, w] float32, K, dist, R, C; the reference also rays [h, w, 2]), numpy
+    or device.  -> device plane int32 [h, w], score float32 [h, w], depth float32 [h, w] (NaN where
+    not kept), around float32 [h, w, 3].  out: those four, allocated by the caller.  volume: a
+    contiguous device uint8 [h, w, planes] that receives the costs of SEMI-GLOBAL RULES beside them
+    (2 to 64 planes then)."""
+    neighbours = list(neighbours)
+    planes = int(planes)
+    if not 1 <= planes <= DENSE_MAX_PLANES:
+        raise ValueError("planes is 1 to %d, got %d" % (DENSE_MAX_PLANES, planes))
+    if volume is not None:
+        _dense_sgm_planes(planes)
+    h, w, w_far, w_near, radius = _dense_sweep_check(ref, neighbours, w_far, w_near, radius)
+    dev = require_gpu()
+    G, rays, N, pose, cams = _dense_sweep_upload(ref, neighbours, h, w)
     plane, score, depth, around = _dense_out(out, [((h, w), I32), ((h, w), torch.float32), ((h, w), torch.float32),
                                                    ((h, w, 3), torch.float32)], dev)
     args = (_ptr(G), _ptr(rays), _ptr(N), _ptr(pose), _ptr(cams), w, h, len(neighbours), planes, w_far, w_near, radius,
@@ -2412,6 +2426,86 @@ def dense_sweep(ref, neighbours, w_far, w_near, planes, radius=3, min_var=4.0, m
     else:
         volume, = _dense_out([volume], [((h, w, planes), U8)], dev)
         check(lib().iamx_dense_sweep_volume(*(args + (_ptr(volume), stream_ptr()))), 'iamx_dense_sweep_volume')
+    torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
+    return plane, score, depth, around
+
+
+def _dense_total(total):
+    total = int(total)
+    if not 2 <= total <= DENSE_GUIDED_MAX_PLANES:
+        raise ValueError("the fine plane set has 2 to %d planes, got %d" % (DENSE_GUIDED_MAX_PLANES, total))
+    return total
+
+
+def dense_tiles(h, w):
+    """(tiles_y, tiles_x) of the sweep's tiles over an h x w image"""
+    return (int(h) + DENSE_TILE[1] - 1) // DENSE_TILE[1], (int(w) + DENSE_TILE[0] - 1) // DENSE_TILE[0]
+
+
+def dense_windows_check(windows, h, w, total):
+    """A window table of an h x w image (dense.py, REFINEMENT RULES): int32 [tiles_y, tiles_x, 2] =
+    (first, count), numpy or a tensor, every entry inside the `total` planes; anything else is a
+    ValueError.  A device table is read back for it.  -> the table as it came"""
+    shape = dense_tiles(h, w) + (2,)
+    if isinstance(windows, torch.Tensor):
+        if windows.dtype != I32 or tuple(windows.shape) != shape:
+            raise ValueError("the window table is int32 of shape %r" % (shape,))
+        tab = windows.cpu().numpy()
+    else:
+        tab = np.asarray(windows)
+        if tab.dtype != np.int32 or tab.shape != shape:
+            raise ValueError("the window table is int32 of shape %r" % (shape,))
+    first, count = tab[..., 0].astype(np.int64), tab[..., 1].astype(np.int64)
+    if (first < 0).any() or (count < 0).any() or (first + count > total).any():
+        raise ValueError("a window has 0 <= first, 0 <= count and first + count <= %d" % total)
+    return windows
+
+
+def dense_guide(coarse_depth, fine_hw, w_far, w_near, total, radius=3, pad=0, out=None):
+    """The window table of a fine level from a coarse depth map (dense.py, REFINEMENT RULES: Guide), one
+    launch.  coarse_depth float32 [hc, wc], NaN where there is none, numpy or device; fine_hw = (h, w) of
+    the fine views; total the size of the fine plane set.  -> device int32 [tiles_y, tiles_x, 2] =
+    (first, count).  out: that tensor, allocated by the caller."""
+    total, radius, pad = _dense_total(total), int(radius), int(pad)
+    h, w = int(fine_hw[0]), int(fine_hw[1])
+    shape = tuple(coarse_depth.shape)
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("a coarse depth map is [hc, wc]")
+    if not (1 <= h <= DENSE_MAX_SIDE and 1 <= w <= DENSE_MAX_SIDE and max(shape) <= DENSE_MAX_SIDE):
+        raise ValueError("a side of 1 to %d pixels wanted" % DENSE_MAX_SIDE)
+    if not 1 <= radius <= DENSE_MAX_RADIUS:
+        raise ValueError("radius is 1 to %d, got %d" % (DENSE_MAX_RADIUS, radius))
+    if not 0 <= pad <= DENSE_GUIDED_MAX_PLANES:
+        raise ValueError("pad is 0 to %d planes, got %d" % (DENSE_GUIDED_MAX_PLANES, pad))
+    w_far, w_near = float(w_far), float(w_near)
+    if not (w_far > 0.0 and w_near > w_far and math.isfinite(w_near)):
+        raise ValueError("inverse depths with 0 < w_far < w_near wanted, got %r and %r" % (w_far, w_near))
+    dev = require_gpu()
+    D = _dev(coarse_depth, torch.float32)
+    windows, = _dense_out(None if out is None else [out], [(dense_tiles(h, w) + (2,), I32)], dev)
+    check(lib().iamx_dense_guide(_ptr(D), shape[1], shape[0], w, h, w_far, w_near, total, radius, pad, _ptr(windows),
+                                 stream_ptr()), 'iamx_dense_guide')
+    torch.cuda.current_stream().synchronize()
+    return windows
+
+
+def dense_sweep_guided(ref, neighbours, w_far, w_near, total, windows, radius=3, min_var=4.0, min_score=0.6, out=None):
+    """The plane sweep of one reference view over per-tile windows of `total` planes (dense.py,
+    REFINEMENT RULES: Guided sweep), one launch.  The views as in dense_sweep; windows int32
+    [tiles_y, tiles_x, 2] = (first, count), numpy or device.  -> device plane int32 [h, w] (the index in
+    the whole set), score, depth float32 [h, w], around float32 [h, w, 3].  out: those four."""
+    neighbours = list(neighbours)
+    total = _dense_total(total)
+    h, w, w_far, w_near, radius = _dense_sweep_check(ref, neighbours, w_far, w_near, radius)
+    dense_windows_check(windows, h, w, total)
+    dev = require_gpu()
+    G, rays, N, pose, cams = _dense_sweep_upload(ref, neighbours, h, w)
+    tab = _dev(windows, I32)
+    plane, score, depth, around = _dense_out(out, [((h, w), I32), ((h, w), torch.float32), ((h, w), torch.float32),
+                                                   ((h, w, 3), torch.float32)], dev)
+    check(lib().iamx_dense_sweep_guided(_ptr(G), _ptr(rays), _ptr(N), _ptr(pose), _ptr(cams), w, h, len(neighbours), total,
+                                        w_far, w_near, radius, float(min_var), float(min_score), _ptr(tab), _ptr(plane),
+                                        _ptr(score), _ptr(depth), _ptr(around), stream_ptr()), 'iamx_dense_sweep_guided')
     torch.cuda.current_stream().synchronize()              # (the uploads' staging copies have been read)
     return plane, score, depth, around
 

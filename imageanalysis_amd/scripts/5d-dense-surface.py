@@ -5,6 +5,9 @@ their best neighbours, cross-checked between views and fused into a height raste
 (imageanalysis_amd/dense.py), written as <analysis_dir>/dense/dsm.npy, count.npy, dsm.wld and
 dense.json, with --ply the surviving points as dense/points.ply.  --regularize sgm puts the semi-global
 aggregation of dense.py's SEMI-GLOBAL RULES between the cost volume and the winner (2 to 64 planes).
+--refine LEVELS goes coarse to fine (dense.py's REFINEMENT RULES): the sweep above runs at
+scale / 2^LEVELS, and each level after it doubles the scale and sweeps, per tile, only a window of
+--refine-ratio times finer planes around the depths of the level before; --scale stays the final scale.
 Run from the reference's scripts/ directory: python <repo>/imageanalysis_amd/scripts/5d-dense-surface.py PROJECT
 """
 import argparse
@@ -30,9 +33,17 @@ ap.add_argument('--regularize', choices=dense.REGULARIZE, default='none', help='
 ap.add_argument('--p1', type=int, default=dense.SGM_P1, help='sgm: penalty of a change by one plane')
 ap.add_argument('--p2', type=int, default=dense.SGM_P2, help='sgm: penalty of a larger change, P1 <= P2 <= 255')
 ap.add_argument('--paths', type=int, choices=(4, 8), default=8, help='sgm: directions aggregated')
+ap.add_argument('--refine', type=int, default=0, metavar='LEVELS',
+                help='coarse to fine: sweep at scale / 2^LEVELS, then LEVELS guided levels up to --scale')
+ap.add_argument('--refine-ratio', type=int, default=4, metavar='R', help='refine: fine planes per coarse plane step')
 args = ap.parse_args()
 try:
     sgm = dense.sgm_parameters(args.planes, args.regularize, args.p1, args.p2, args.paths)
+    if not 0 <= args.refine <= 8:
+        raise ValueError("--refine is 0 to 8 levels, got %d" % args.refine)
+    planes_total = args.planes
+    for _ in range(args.refine):
+        planes_total = dense.refine_planes(planes_total, args.refine_ratio)
 except ValueError as e:
     ap.error(str(e))
 
@@ -44,7 +55,7 @@ with open(os.path.join(proj.analysis_dir, "matches_grouped"), "rb") as f:
     matches = pickle.load(f)
 
 t0 = time.perf_counter()
-views, group = dense.views_from_project(proj, group_list, args.group, matches, args.scale)
+views, group = dense.views_from_project(proj, group_list, args.group, matches, args.scale / 2 ** args.refine)
 if not views:
     raise SystemExit("group %d has no images" % args.group)
 poses = [(v.R, v.C) for v in views]
@@ -55,6 +66,17 @@ print('Views: %d of %d x %d pixels, %d with neighbours and a depth range' % (len
                                                                             views[0].G.shape[0], swept))
 mode = {} if sgm is None else dict(regularize=args.regularize, p1=sgm[2], p2=sgm[3], paths=sgm[1])
 maps = dense.depth_maps(views, neighbours, ranges, planes=args.planes, radius=args.radius, min_score=args.min_score, **mode)
+planes = args.planes
+for level in range(1, args.refine + 1):
+    views, _group = dense.views_from_project(proj, group_list, args.group, matches, args.scale / 2 ** (args.refine - level))
+    maps = dense.refine(views, neighbours, ranges, maps, planes, ratio=args.refine_ratio, radius=args.radius,
+                        min_score=args.min_score)
+    planes = maps.total
+    count = maps.windows[..., 1].float()
+    print('Level %d: %d x %d pixels, %d planes, %.1f of them walked per tile (most %d)'
+          % (level, views[0].G.shape[1], views[0].G.shape[0], planes, float(count.mean()), int(count.max())))
+if args.refine:
+    mode = dict(mode, refine=args.refine, ratio=args.refine_ratio, planes_total=planes)
 gsd = args.gsd
 if gsd <= 0.0:
     mids = sorted(0.5 * (r[0] + r[1]) for r in ranges if r is not None)

@@ -1864,6 +1864,42 @@ int iamx_dense_sgm_select(const uint16_t *total, const uint8_t *volume, int widt
                           uint8_t *cost, uint16_t *tot0, float *depth, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Dense surface, coarse to fine (csrc/dense_refine.hip, the guided form in csrc/dense_sweep.hip): a
+ * fine level sweeps, per tile, only a window of a larger set of planes around the depths that a
+ * coarse depth map found.  The rules are stated in imageanalysis_amd/dense.py ("REFINEMENT RULES")
+ * and restated in numpy by tests/dense_refine_restatement.py; the device follows them bit for bit.
+ * All pointers DEV.
+ *
+ * windows [tiles_y][tiles_x][2] int32 = (first, count) per IAMX_DENSE_TILE_W x IAMX_DENSE_TILE_H tile
+ * of the fine image, row-major, tiles_x = ceil(width / 32), tiles_y = ceil(height / 16); an entry
+ * has 0 <= first, 0 <= count, first + count <= planes_total.  2 <= planes_total <=
+ * IAMX_DENSE_GUIDED_MAX_PLANES planes uniform in inverse depth from w_far to w_near.
+ *
+ * iamx_dense_guide, one workgroup per tile: coarse_depth [hc][wc] float32 (NaN: none) -> windows.
+ *   The tile grown by `radius` fine pixels maps to a box of coarse pixels (one more either side); the
+ *   smallest and largest inverse depth of its finite positive entries, floor and ceil in fine plane
+ *   steps, `pad` (0 .. IAMX_DENSE_GUIDED_MAX_PLANES) planes more either side, clamped into the set;
+ *   (0, 0) for a box without an entry.  Every entry is written.
+ * iamx_dense_sweep_guided: iamx_dense_sweep with planes_total in place of planes, and the tile's
+ *   workgroup walking the planes of its window only; plane is the index in the whole set (-1 and NaN
+ *   scores for a tile with count 0), around holds NaN beyond the window, and a winner on a rim of
+ *   its window that is not a rim of the set has depth NaN.  The table is read back and checked before
+ *   the launch (the stream is synchronised once); with every entry (0, planes_total) and
+ *   planes_total <= IAMX_DENSE_MAX_PLANES the outputs are iamx_dense_sweep's.
+ * A size or a parameter out of range, a null pointer, an entry that leaves the set: IAMX_EINVAL
+ * without a launch.
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_DENSE_GUIDED_MAX_PLANES 65536
+int iamx_dense_guide(const float *coarse_depth, int wc, int hc, int width, int height, double w_far,
+                     double w_near, int planes_total, int radius, int pad, int32_t *windows,
+                     void *stream);
+int iamx_dense_sweep_guided(const float *ref, const double *rays, const float *nbr,
+                            const double *ref_pose, const double *nbr_cam, int width, int height,
+                            int num_nbr, int planes_total, double w_far, double w_near, int radius,
+                            float min_var, float min_score, const int32_t *windows, int32_t *plane,
+                            float *score, float *depth, float *around, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * True orthophoto (csrc/ortho_dsm.hip): a group's frames draped over the dense DSM, every mosaic
  * pixel placed at its DSM height, projected through the full camera model and coloured only from
  * the frames that see it.  The rules are stated in imageanalysis_amd/ortho.py ("THE TRUE-ORTHO
