@@ -333,7 +333,7 @@ struct SymArgs {
                                  //      whose minimum is <= v2 (NULL: not wanted) -- the only train rows
                                  //      that can be the query's best or second (narrow exact stage)
 #if defined(IAMX_T_STAMPS)
-    unsigned long long *stamps;  // [workgroups][waves][4]: segment sum, chunks, loop cycles, loop 100 MHz ticks --
+    unsigned long long *stamps;  // [workgroups][waves][4]: segment sum (knn2sym16_kernel: pair tails), chunks, loop cycles, loop 100 MHz ticks --
                                  //      a buffer of its own: nothing in the library reads it
 #endif
 };
@@ -1325,8 +1325,10 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
     int bimg_held = -1;              // the B image whose slice bq holds
     asm volatile("" : "+v"(u_end), "+v"(item_wgi), "+v"(bimg_held));
 #if defined(IAMX_T_STAMPS)
-    // (the diagnostic build stamps this kernel's whole chunk loop only: chunks, cycles, 100 MHz ticks)
-    unsigned long long stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0;
+    // (the diagnostic build stamps this kernel's whole chunk loop -- chunks, cycles, 100 MHz ticks -- and the
+    //  pair tail: the cycles from the end of a pair's chunk loop to the start of the item's next pair's, which
+    //  cover the last merge, the column epilogue, the barrier, the first two stages and the first operand reads)
+    unsigned long long stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0, stamp_tail = 0, stamp_c1 = 0;
 #endif
     // the table entries of the pair the loop runs next, read one pair ahead (see knn2sym_kernel)
     int nx_b = A.upairs[2 * u], nx_a = A.upairs[2 * u + 1];
@@ -1497,6 +1499,7 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
 #if defined(IAMX_T_STAMPS)
         const unsigned long long loop_c0 = __builtin_amdgcn_s_memtime(), loop_r0 = __builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0) alone
+        if (stamp_c1) stamp_tail += loop_c0 - stamp_c1;
 #endif
         for (int ch = 0; ch < nchunks; ++ch) {
             const int buf = ch & 1;
@@ -1595,9 +1598,10 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
             stamp_cycles += loop_c1 - loop_c0;
             stamp_ticks += __builtin_amdgcn_s_memrealtime() - loop_r0;
             stamp_chunks += (unsigned)nchunks;
+            stamp_c1 = loop_c1;
             if (A.stamps && lane == 0) {
                 unsigned long long *o = A.stamps + ((size_t)blockIdx.x * NW + wave) * 4;
-                o[0] = 0;
+                o[0] = stamp_tail;
                 o[1] = stamp_chunks;
                 o[2] = stamp_cycles;
                 o[3] = stamp_ticks;
@@ -1616,60 +1620,71 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
         // ---- column results: lane groups lg and lg ^ 2 hold the same group g = lg & 1 of train rows; merged,
         // a lane has form 2's 4 x 2 group minima of its 16 queries: the two smallest, and the groups whose
         // minimum is <= the second smallest (bit k + 4 g), 4 bits a query
+        // Both exchanges are swaps on the VALU (no LDS).  v_permlane32_swap on the registers of blocks j and
+        // j + 8 and one minimum leave block j + 8 h merged in half h = lane >> 5; of a lane's two smallest,
+        // v_permlane16_swap on the registers of blocks p and p + 4 leaves both sides of block p + 4 c in the
+        // DPP rows of parity c = lg & 1.  So lane (n, lg) ends with (v1, v2) of the FOUR CONSECUTIVE queries
+        // 16 rn + 4 lg + p, and every lane stores.
         if (wave_valid) {
-            unsigned ownpack[2] = {0, 0};
-            int v1s[QB], v2s[QB];
+            int mk[QB / 2][4], a1[QB / 2], a2[QB / 2];
 #pragma unroll
-            for (int qb = 0; qb < QB; ++qb) {
-                int mk[4];
+            for (int j = 0; j < QB / 2; ++j) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) mk[k] = min(m[qb][k], __shfl_xor(m[qb][k], 32));
-                const int lo01 = min(mk[0], mk[1]), hi01 = max(mk[0], mk[1]);
-                const int lo23 = min(mk[2], mk[3]), hi23 = max(mk[2], mk[3]);
-                const int a1 = min(lo01, lo23), a2 = min(max(lo01, lo23), min(hi01, hi23));
-                const int b1 = __shfl_xor(a1, 16), b2 = __shfl_xor(a2, 16);
-                const int v1 = min(a1, b1), v2 = min(max(a1, b1), min(a2, b2));
-                v1s[qb] = v1;
-                v2s[qb] = v2;
-                const unsigned own = (mk[0] <= v2 ? 1u : 0u) | (mk[1] <= v2 ? 2u : 0u) |
-                                     (mk[2] <= v2 ? 4u : 0u) | (mk[3] <= v2 ? 8u : 0u);
-                ownpack[qb >> 3] |= own << (4 * (qb & 7));
+                for (int k = 0; k < 4; ++k) {
+                    const v2u x = __builtin_amdgcn_permlane32_swap((unsigned)m[j][k], (unsigned)m[j + QB / 2][k], false, false);
+                    mk[j][k] = min((int)x[0], (int)x[1]);
+                }
+                const int lo01 = min(mk[j][0], mk[j][1]), hi01 = max(mk[j][0], mk[j][1]);
+                const int lo23 = min(mk[j][2], mk[j][3]), hi23 = max(mk[j][2], mk[j][3]);
+                a1[j] = min(lo01, lo23);
+                a2[j] = min(max(lo01, lo23), min(hi01, hi23));
             }
-            unsigned othpack[2] = {0, 0};
+            int v1s[4], v2s[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                // ([0]: the even row's side of its block p in the even rows, of the odd rows' block p + 4 in the odd rows)
+                const v2u x1 = __builtin_amdgcn_permlane16_swap((unsigned)a1[p], (unsigned)a1[p + 4], false, false);
+                const v2u x2 = __builtin_amdgcn_permlane16_swap((unsigned)a2[p], (unsigned)a2[p + 4], false, false);
+                v1s[p] = min((int)x1[0], (int)x1[1]);
+                v2s[p] = min(max((int)x1[0], (int)x1[1]), min((int)x2[0], (int)x2[1]));
+            }
+            const int row0 = q0 + QB * rn + 4 * lg;
+            unsigned maskw = 0;          // byte p = the nibble of group half 0 | the nibble of group half 1 << 4
             if (A.colmask) {
-                othpack[0] = (unsigned)__shfl_xor((int)ownpack[0], 16);
-                othpack[1] = (unsigned)__shfl_xor((int)ownpack[1], 16);
-            }
-            const int row0 = q0 + QB * rn;
-            if (lg == 0) {
+                // the second smallest of block j in every row: the even rows' v2s[p] is block p's, the odd rows' block p + 4's
+                unsigned ownpack = 0;
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb)
-                    if (row0 + qb < nb)
-                        *reinterpret_cast<v2i *>(A.col + 2 * (col_u + row0 + qb)) = v2i{v1s[qb], v2s[qb]};
-                if (A.colmask) {
-                    // byte qb = own nibble | other half's nibble << 4
-                    uint8_t *dst = A.colmask + col_u + row0;
-                    if (row0 + QB <= nb) {
-                        auto spread = [](unsigned nib4) {    // four nibbles -> the low nibbles of four bytes
-                            const unsigned x = (nib4 | (nib4 << 8)) & 0x00FF00FFu;
-                            return (x | (x << 4)) & 0x0F0F0F0Fu;
-                        };
-                        typedef unsigned v4u __attribute__((ext_vector_type(4)));
-                        v4u o;
+                for (int p = 0; p < 4; ++p) {
+                    const v2u w = __builtin_amdgcn_permlane16_swap((unsigned)v2s[p], (unsigned)v2s[p], false, false);
 #pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            o[2 * h] = spread(ownpack[h] & 0xFFFFu) | (spread(othpack[h] & 0xFFFFu) << 4);
-                            o[2 * h + 1] = spread(ownpack[h] >> 16) | (spread(othpack[h] >> 16) << 4);
-                        }
-                        *reinterpret_cast<v4u *>(dst) = o;
-                    } else {
-#pragma unroll
-                        for (int qb = 0; qb < QB; ++qb)
-                            if (row0 + qb < nb)
-                                dst[qb] = (uint8_t)(((ownpack[qb >> 3] >> (4 * (qb & 7))) & 15u) |
-                                                    (((othpack[qb >> 3] >> (4 * (qb & 7))) & 15u) << 4));
+                    for (int c = 0; c < 2; ++c) {
+                        const int j = p + 4 * c, v2 = (int)w[c];
+                        const unsigned own = (mk[j][0] <= v2 ? 1u : 0u) | (mk[j][1] <= v2 ? 2u : 0u) |
+                                             (mk[j][2] <= v2 ? 4u : 0u) | (mk[j][3] <= v2 ? 8u : 0u);
+                        ownpack |= own << (4 * j);
                     }
                 }
+                // ([0]: the even rows' words, group half 0, in both rows; [1]: the odd rows')
+                const v2u g = __builtin_amdgcn_permlane16_swap(ownpack, ownpack, false, false);
+                auto spread = [](unsigned nib4) {    // four nibbles -> the low nibbles of four bytes
+                    const unsigned x = (nib4 | (nib4 << 8)) & 0x00FF00FFu;
+                    return (x | (x << 4)) & 0x0F0F0F0Fu;
+                };
+                const int sh = 16 * (lg & 1);
+                maskw = spread((g[0] >> sh) & 0xFFFFu) | (spread((g[1] >> sh) & 0xFFFFu) << 4);
+            }
+            int32_t *const cdst = A.col + 2 * (col_u + row0);
+            if (row0 + 4 <= nb) {
+                *reinterpret_cast<v4i *>(cdst) = v4i{v1s[0], v2s[0], v1s[1], v2s[1]};
+                *reinterpret_cast<v4i *>(cdst + 4) = v4i{v1s[2], v2s[2], v1s[3], v2s[3]};
+                if (A.colmask) *reinterpret_cast<unsigned *>(A.colmask + col_u + row0) = maskw;
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    if (row0 + p < nb) {
+                        *reinterpret_cast<v2i *>(cdst + 2 * p) = v2i{v1s[p], v2s[p]};
+                        if (A.colmask) A.colmask[col_u + row0 + p] = (uint8_t)(maskw >> (8 * p));
+                    }
             }
         }
         if (++u == uniform32(u_end)) break;

@@ -10,7 +10,11 @@ Segments: 1..16 the steps of a chunk (step 12 = the barrier step, steps 12..16 c
 steps 4, 8, 12, 16 the last level of the row butterfly), 17 the barrier step's s_waitcnt (its vmcnt
 part: the stamp in front of it drains lgkmcnt itself), 18 the s_barrier behind it, 19 two stamps back to
 back (the stamp's own cost, subtracted from every other segment).  Every build also stamps the whole loop
-with s_memtime and s_memrealtime: the in-kernel clock.
+with s_memtime and s_memrealtime: the in-kernel clock.  The 16x16x64 item kernel (--loops) stamps its whole
+loop and its PAIR TAIL: the cycles from the end of a pair's chunk loop to the start of the item's next
+pair's (the last merge, the column epilogue, the barrier, the first two stages, the first operand reads).
+The tail's median is over every wave that ran chunks, waves past the end of the B image included (their tail
+has no column epilogue); the 4096-row store has none.
 
 Prints the median over waves of cycles per chunk and the share of the loop's cycles per chunk IN THE
 SAME BUILD.  Read the shares: a stamped build's fences forbid overlaps the shipped loop has, so its run
@@ -121,7 +125,7 @@ def startup_store():
     return 'items', args, c.n_items, (store, c)
 
 
-def measure(L, kernel, args, n_wg, seconds):
+def measure(L, kernel, args, n_wg, seconds, pair_chunks=0):
     launch = {'items': L.iamx_knn2sym_sweep_items, 'items16': L.iamx_knn2sym_sweep_items16}.get(kernel, L.iamx_knn2sym_sweep)
     buf = torch.zeros((n_wg, NW, 4), dtype=torch.int64, device='cuda')
     L.iamx_knn2sym_set_stamps(buf.data_ptr())
@@ -137,6 +141,10 @@ def measure(L, kernel, args, n_wg, seconds):
     seg = float(np.median(v[:, 0] / v[:, 1]))
     loop = float(np.median(v[:, 2] / v[:, 1]))
     ghz = float(np.median(v[:, 2] / v[:, 3])) * 0.1             # s_memrealtime ticks at 100 MHz
+    if pair_chunks:
+        # the 16x16x64 kernel's segment sum is its pair tails: the pairs of a wave's item but the last have one
+        tails = v[:, 1] / pair_chunks - 1
+        seg = float(np.median(v[tails > 0, 0] / tails[tails > 0]))
     return seg, loop, ghz
 
 
@@ -160,15 +168,19 @@ def main():
         return
     torch.cuda.set_device(0)
     if args.loops:
+        import sweep_startup as ss
         L = load(jobs[0][1])
         _kernel, a, n_wg, _keep = startup_store()
         print('device %s; 4096-row store, %d workgroups, %.1f s of back-to-back launches each; median over waves'
               % (torch.cuda.get_device_name(0), n_wg, args.seconds))
         for rep in range(3):
             for kernel in ('items', 'items16'):
-                _seg, loop, ghz = measure(L, kernel, a, n_wg, args.seconds)
+                pair_chunks = ss.ROWS // 128 if kernel == 'items16' else 0
+                tail, loop, ghz = measure(L, kernel, a, n_wg, args.seconds, pair_chunks)
                 print('  %-8s chunk loop %7.0f cycles a chunk, in-kernel clock %.3f GHz, %.3f us a chunk'
-                      % (kernel, loop, ghz, loop / ghz * 1e-3))
+                      % (kernel, loop, ghz, loop / ghz * 1e-3) +
+                      (', pair tail %.0f cycles (%.2f %% of a pair of %d chunks)'
+                       % (tail, 100.0 * tail / (tail + loop * pair_chunks), pair_chunks) if pair_chunks else ''))
         return
     stores = [('dense', ) + dense_store(), ('4096-row', ) + startup_store()]
     res = {}

@@ -1,5 +1,7 @@
 // Checks the lane/register mapping of the transposing half-wave minimum used by
-// imageanalysis_amd/csrc/match_knn2sym.hip (DPP bank masks, row_ror, v_permlane16_swap).
+// imageanalysis_amd/csrc/match_knn2sym.hip (DPP bank masks, row_ror, v_permlane16_swap), and of the two
+// swaps of knn2sym16_kernel's column epilogue: which lanes of which operand each element of
+// __builtin_amdgcn_permlane32_swap's and __builtin_amdgcn_permlane16_swap's result holds.
 // Build + run on the GPU box:  hipcc --offload-arch=gfx950 -O3 rowmin_check.hip -o rowmin_check && ./rowmin_check
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -47,8 +49,43 @@ __global__ void k(const int *in, int *out)
     out[threadIdx.x * 2 + 1] = m1;
 }
 
+// [lane][4]: permlane32_swap(a, b)[0], [1], permlane16_swap(a, b)[0], [1] with a = lane, b = 100 + lane
+__global__ void swaps(int *out)
+{
+    const unsigned a = threadIdx.x, b = 100 + threadIdx.x;
+    const v2u x = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    const v2u y = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    out[threadIdx.x * 4] = (int)x[0];
+    out[threadIdx.x * 4 + 1] = (int)x[1];
+    out[threadIdx.x * 4 + 2] = (int)y[0];
+    out[threadIdx.x * 4 + 3] = (int)y[1];
+}
+
+// [0]: a's low half (even rows) at home, b's low half (even rows) in the high half (odd rows);
+// [1]: a's high half (odd rows) in the low half (even rows), b's high half (odd rows) at home
+static int check_swaps()
+{
+    int o[64 * 4], *dout, bad = 0;
+    hipMalloc(&dout, sizeof(o));
+    hipLaunchKernelGGL(swaps, dim3(1), dim3(64), 0, 0, dout);
+    hipMemcpy(o, dout, sizeof(o), hipMemcpyDeviceToHost);
+    for (int lane = 0; lane < 64; ++lane) {
+        const bool lo32 = lane < 32, even = ((lane >> 4) & 1) == 0;
+        const int want[4] = {lo32 ? lane : 100 + lane - 32, lo32 ? lane + 32 : 100 + lane,
+                             even ? lane : 100 + lane - 16, even ? lane + 16 : 100 + lane};
+        for (int i = 0; i < 4; ++i)
+            if (o[lane * 4 + i] != want[i]) {
+                if (bad < 8) printf("lane %d permlane%d_swap [%d]: got %d want %d\n", lane, i < 2 ? 32 : 16, i & 1, o[lane * 4 + i], want[i]);
+                ++bad;
+            }
+    }
+    printf("swap_check: %s (%d mismatches)\n", bad ? "FAILED" : "ok", bad);
+    return bad;
+}
+
 int main()
 {
+    if (check_swaps()) return 1;
     int h[64 * 16], o[128], *din, *dout;
     srand(1);
     for (int i = 0; i < 64 * 16; ++i) h[i] = rand() % 100000;
