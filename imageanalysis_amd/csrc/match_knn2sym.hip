@@ -1252,48 +1252,36 @@ __global__ __launch_bounds__(NW * 64, WPE) void knn2sym_kernel(SymArgs A)
 //   sorted B rows q0 + 16 rn + block, rn = n's bit 3 moved to the bottom: lanes n and n ^ 8 hold
 //   a group of 32 consecutive rows (form 2's groups, so R_w and S_w are form 2's).  An accumulator
 //   is query n against train rows 4 lg + i of the tile.
-//   Row direction: the v_min3 chain over the 16 blocks is lane local (4 registers a tile); a
-//   transposing butterfly over the 16 lanes of a DPP row -- xor 8 (4 -> 2 registers, then the
-//   group floor), xor 4 (2 -> 1), inside the quad -- leaves train row 4 lg + 2 b2 + b3 in quad
-//   (b3, b2).  No lane exchange across DPP rows.
+//   Row direction: the v_min3 chain over the 16 blocks is lane local (4 registers a tile); the
+//   minimum over the 16 lanes n, with the group floors, goes through LDS (below; until round 21 a
+//   transposing butterfly over the DPP row, 16 VALU instructions a tile).
 //   Column direction: running minima per block and (tile32 & 3); train row bit 2 is lg & 1, so
 //   lane groups lg and lg ^ 2 are merged at the pair's end into form 2's eight groups (k, g).
 // The chunk loop is a compiler-scheduled software pipeline: 32 steps of 8 MFMAs (four blocks),
 // step s issues the MFMAs of step s + 1 beside the minima of step s, PIPE valu instructions a gap.
+//   Row direction, across lanes (round 21): through LDS, which the loop leaves three quarters idle,
+//   instead of a butterfly on the vector issue slots that bound it.  A lane stores the four raw
+//   registers of a tile with one ds_write_b128 into its wave's area ([tile][lg][n], a combo (tile, lg)
+//   every SWEEP16_RAW_COMBO bytes); the wave reads its own chunk back while the next chunk runs (no
+//   barrier: a wave's LDS operations complete in order).  Reader lane l takes combo l >> 1 and the four
+//   groups {n, n ^ 8} with (n & 7) = 2 j + (l & 1): 8 ds_read_b128, the pair minimum and the floor of
+//   every group, the minimum over its groups, one quad_perm minimum with lane l ^ 1, and the even lane
+//   stores the combo's four consecutive rows of R_w with one ds_write_b128.
+//   The combo stride of 288 bytes (18 slots of 16 bytes) puts the 16 lanes of each ds_read_b128 lane
+//   group -- combos {0,1,6,7,10..13} or {2..5,8,9,14,15} (+ 16), both halves -- on 16 different slots
+//   of the 256-byte bank row; a writer's 8 contiguous lanes store 128 contiguous bytes.
 // ---------------------------------------------------------------------------------
-// (in three pieces, which the chunk loop runs in three steps of the next tile)
-__device__ __forceinline__ void row16_level8(const int (&r)[4], int lo, int (&u)[2])
-{
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {              // lanes xor 8: quads 0,1 keep r[2k], quads 2,3 r[2k+1]
-        const int a = r[2 * k], b = r[2 * k + 1];
-        const int t1 = __builtin_amdgcn_update_dpp(b, a, 0x128, 0xF, 0x3, false);   // row_ror:8
-        const int t2 = __builtin_amdgcn_update_dpp(a, b, 0x128, 0xF, 0xC, false);
-        u[k] = min(t1, t2) + lo;
-    }
-}
-__device__ __forceinline__ int row16_level4(const int (&u)[2])
-{
-    // lanes xor 4: quads 0,2 keep u[0], quads 1,3 u[1]
-    const int t1 = __builtin_amdgcn_update_dpp(u[1], u[0], 0x12C, 0xF, 0x5, false);   // row_ror:12 = lane+4
-    const int t2 = __builtin_amdgcn_update_dpp(u[0], u[1], 0x124, 0xF, 0xA, false);   // row_ror:4  = lane-4
-    return min(t1, t2);
-}
-__device__ __forceinline__ int row16_quad(int w)
-{
-    w = min(w, __builtin_amdgcn_update_dpp(0, w, 0xB1, 0xF, 0xF, true));    // quad_perm:[1,0,3,2]
-    w = min(w, __builtin_amdgcn_update_dpp(0, w, 0x4E, 0xF, 0xF, true));    // quad_perm:[2,3,0,1]
-    return w;
-}
-__device__ __forceinline__ int row16_min4(const int (&r)[4], int lo)
-{
-    int u[2];
-    row16_level8(r, lo, u);
-    return row16_quad(row16_level4(u));
-}
-
 // valu instructions behind MFMA `g` (0..7) of a step of the 16x16x64 chunk loop that has `nv` of them
 constexpr int sweep16_gap_valu(int nv, int g) { return nv / 8 + (g < nv % 8 ? 1 : 0); }
+
+// the 16x16x64 item kernel's LDS (dynamic: over the 64 KB of a static array): form 2's layout -- two
+// stages, Ct, three R_w buffers, S_w, the dump area -- and behind it the waves' raw row minima, two
+// chunks each (the next chunk's writes begin while the reader runs)
+constexpr int SWEEP16_RAW_COMBO = 256 + 32;
+constexpr int SWEEP16_RAW_CHUNK = (CHUNK / 16) * 4 * SWEEP16_RAW_COMBO;
+constexpr int SWEEP16_LDS_FORM2 = 2 * CHUNK * D + 2 * CHUNK * 4 + 3 * 4 * CHUNK * 4 + 2 * 4 * 4 + (2 * 4 * CHUNK + 4 * 256) * 4;
+constexpr int SWEEP16_LDS_BYTES = SWEEP16_LDS_FORM2 + 4 * 2 * SWEEP16_RAW_CHUNK;
+static_assert(SWEEP16_LDS_FORM2 % 16 == 0 && SWEEP16_LDS_BYTES <= 160 * 1024, "aligned, and inside a compute unit's LDS");
 
 template <int PIPE>
 __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
@@ -1302,8 +1290,7 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
     constexpr int PIECES = CHUNK * D / 16 / NT;
     constexpr int NT16 = CHUNK / 16, SPT = 4, QS = QB / SPT, NS = NT16 * SPT;    // tiles, steps a tile, blocks a step
     static_assert(WGROWS == 1024 && PIECES == 4 && NS == 32 && D == 128, "form 2's workgroup");
-    // (the LDS layout of knn2sym_kernel: two stages, Ct, three R_w buffers, S_w, the dump area)
-    __shared__ __attribute__((aligned(16))) int8_t lds[2 * CHUNK * D + 2 * CHUNK * 4 + 3 * NW * CHUNK * 4 + 2 * NW * 4 + (2 * NW * CHUNK + NW * 256) * 4];
+    extern __shared__ __attribute__((aligned(16))) int8_t lds[];     // SWEEP16_LDS_BYTES
     int8_t *lds_tile = lds;
     int *lds_tb = reinterpret_cast<int *>(lds + 2 * CHUNK * D);      // [2][CHUNK]     Ct
     int *lds_row = lds_tb + 2 * CHUNK;                               // [3][NW][CHUNK] R_w
@@ -1321,9 +1308,13 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
     }
     int u = A.wg_off[3 * vid], u_end = u + A.wg_off[3 * vid + 1], item_wgi = A.wg_off[3 * vid + 2];
     v4i bq[QB][2];
-    int lo_lane;
+    int fl[4];                       // the Cq floors of the four groups (n & 7) = 2 j + (lane & 1) this lane reads back
     int bimg_held = -1;              // the B image whose slice bq holds
     asm volatile("" : "+v"(u_end), "+v"(item_wgi), "+v"(bimg_held));
+    // a lane's place in its wave's raw row minima: as the writer (n, lg) of a tile, as the reader of combo lane >> 1
+    const int raw_wave = SWEEP16_LDS_FORM2 + wave * (2 * SWEEP16_RAW_CHUNK);
+    const int raw_wr = raw_wave + lg * SWEEP16_RAW_COMBO + n * 16;
+    const int raw_rd = raw_wave + (lane >> 1) * SWEEP16_RAW_COMBO + (lane & 1) * 16;
 #if defined(IAMX_T_STAMPS)
     // (the diagnostic build stamps this kernel's whole chunk loop -- chunks, cycles, 100 MHz ticks -- and the
     //  pair tail: the cycles from the end of a pair's chunk loop to the start of the item's next pair's, which
@@ -1363,19 +1354,23 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
                     asm volatile("" : "+a"(bq[qb][s]));      // (only ever an MFMA source: the AGPR half)
                 }
             }
-            lo_lane = 0;
             {
                 int spread = 0;
                 if (wave_valid) {
                     const int g_lo = rn & ~1, g_hi = rn | 1;
                     const int r_lo = q0 + QB * g_lo < nb ? q0 + QB * g_lo : nb - 1;
                     const int r_hi = q0 + QB * g_hi + QB - 1 < nb ? q0 + QB * g_hi + QB - 1 : nb - 1;
-                    lo_lane = A.sn2[boff + r_lo] >> 1;
-                    spread = (A.sn2[boff + r_hi] >> 1) - lo_lane;
+                    spread = (A.sn2[boff + r_hi] >> 1) - (A.sn2[boff + r_lo] >> 1);
                 }
 #pragma unroll
                 for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
                 if (lane == 0) lds_cq[wave] = spread;
+            }
+            // (group (n & 7) holds rows q0 + 32 (n & 7) ..: the floor its two lanes n, n ^ 8 share)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r_lo = q0 + 2 * QB * (2 * j + (lane & 1));
+                fl[j] = wave_valid ? A.sn2[boff + (r_lo < nb ? r_lo : nb - 1)] >> 1 : 0;
             }
         }
         if (!wave_valid) {
@@ -1428,12 +1423,36 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
                                                   store ? (ch * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
         };
 
-        // after the butterfly quad (b3, b2) = (n >> 3, (n >> 2) & 1) of lane group lg holds train row
-        // 4 lg + 2 b2 + b3 of the tile.  One lane per quad stores it; the others, and a wave past the end of
-        // the B image, store into the dump area (no branch in the tile loop)
-        int *const row_dst = (lane & 3) == 0 && wave_valid
-            ? lds_row + wave * CHUNK + 4 * lg + 2 * ((n >> 2) & 1) + (n >> 3)
-            : lds_dump + wave * 256 + lane;                 // (+ row buffer offset + tile * 16: inside the dump area)
+        // the reader's even lanes hold train rows 4 c .. 4 c + 3 of the chunk, c = lane >> 1, and store them;
+        // the odd lanes, and a wave past the end of the B image (its rows of R_w stay BIG), store into the dump
+        // area: one ds_write_b128 a chunk.  A predicated store would be a branch in step RSTORE, and a step is
+        // one scheduling region (its sched_group_barrier deal ends at a block boundary), so the dump area stays
+        int *const row_dst = (lane & 1) == 0 && wave_valid
+            ? lds_row + wave * CHUNK + 4 * (lane >> 1)
+            : lds_dump + wave * 256 + 4 * lane;             // (+ row buffer offset: inside the dump area)
+        typedef __attribute__((address_space(3))) int8_t *lds_wbytes;
+        typedef __attribute__((address_space(3))) v4i *lds_v4i;
+        // the raw row minima of tile `tile`, into the wave's chunk at byte offset `at` (raw_wr + the buffer)
+        auto raw_write = [&](int at, int tile, const int (&rr)[4]) {
+            *reinterpret_cast<lds_v4i>((lds_wbytes)lds + at + tile * (4 * SWEEP16_RAW_COMBO)) = v4i{rr[0], rr[1], rr[2], rr[3]};
+        };
+        // the reader's group j of the chunk at `at` (raw_rd + the buffer): its two lanes' registers, then
+        // their minimum above the group's floor
+        auto raw_read = [&](int at, int j, v4i (&v)[2]) {
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+                v[hi] = *reinterpret_cast<lds_v4i>((lds_wbytes)lds + at + j * 32 + hi * 128);
+        };
+        auto raw_group = [&](int j, const v4i (&v)[2], int (&x)[4]) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[i] = min(v[0][i], v[1][i]) + fl[j];
+        };
+        // the other half of the combo's groups sits in lane ^ 1
+        auto raw_store = [&](int rbo_at, int (&x)[4]) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[i] = min(x[i], __builtin_amdgcn_update_dpp(0, x[i], 0xB1, 0xF, 0xF, true));   // quad_perm:[1,0,3,2]
+            *reinterpret_cast<v4i *>(row_dst + rbo_at) = v4i{x[0], x[1], x[2], x[3]};
+        };
         v4i aop[2][2], ct[2];
         v4i accs[2][QS];
         int r[2][4];
@@ -1495,28 +1514,36 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
         const unsigned lds_tile_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tile + wave_u * (64 * 16));
         const unsigned lds_tb_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tb + (wave_u & (CHUNK / 64 - 1)) * 64);
         const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
-        int bu[2] = {BIG, BIG}, bw = BIG;
 #if defined(IAMX_T_STAMPS)
         const unsigned long long loop_c0 = __builtin_amdgcn_s_memtime(), loop_r0 = __builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0) alone
         if (stamp_c1) stamp_tail += loop_c0 - stamp_c1;
 #endif
-        for (int ch = 0; ch < nchunks; ++ch) {
+        // a chunk.  STAGE: chunk + 2 of the pair exists and is staged; the pair's last two chunks stage nothing
+        auto chunk = [&](int ch, auto stage_c) __attribute__((always_inline)) {
+            constexpr bool STAGE = decltype(stage_c)::value != 0;
             const int buf = ch & 1;
             // the barrier step: every read of this chunk's stage has been issued (tile NT16 - 1's in the step
             // in front of it), the next chunk's stage has landed; the stage of chunk + 2 follows it, one piece
             // a step held between two column minima, and the merge of the previous chunk in three steps
             constexpr int BAR = (NT16 - 2) * SPT;
             static_assert(BAR + PIECES < NS, "the stage's five pieces fit behind the barrier");
-            const int chs = ch + 2 < nchunks ? ch + 2 : nchunks - 1;
-            const int8_t *const sg_tile = tbase + (int64_t)chs * (CHUNK * D);
-            const int8_t *const sg_ct = reinterpret_cast<const int8_t *>(tci + chs * CHUNK);
+            const int8_t *const sg_tile = tbase + (int64_t)(ch + 2) * (CHUNK * D);
+            const int8_t *const sg_ct = reinterpret_cast<const int8_t *>(tci + (ch + 2) * CHUNK);
+            // the raw row minima: this chunk's tiles go to buffer `buf`, the previous chunk's last tile and the
+            // reader to the other one
+            const int raw_cur = buf * SWEEP16_RAW_CHUNK, raw_prev = SWEEP16_RAW_CHUNK - raw_cur;
+            const int wr_cur = raw_wr + raw_cur, wr_prev = raw_wr + raw_prev, rd_prev = raw_rd + raw_prev;
             int mR[NW], mL = BIG, mU1 = BIG, mU2 = BIG;
+            constexpr int RSTORE = 4 * SPT + 1;                  // the step of the reader's row store
+            static_assert(RSTORE < BAR, "the rows are stored in front of the barrier");
+            v4i rdv[2];
+            int racc[4], rx[4], rh[4];
             static_for<0, NS>([&](auto st_c) {
                 constexpr int st = decltype(st_c)::value;
                 constexpr int t = st / SPT, ph = st % SPT, qp = QS * ph, cur = st & 1, kk = (t >> 1) & 3;
                 constexpr int nst = st + 1 < NS ? st + 1 : 0;
-                constexpr bool staging = st >= BAR && st <= BAR + PIECES;
+                constexpr bool staging = STAGE && st >= BAR && st <= BAR + PIECES;
                 if constexpr (st == BAR) {
                     __builtin_amdgcn_s_waitcnt(0x0070);              // vmcnt(0) lgkmcnt(0)
                     __syncthreads();
@@ -1546,10 +1573,28 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
                 for (int i = 0; i < 4; ++i)
                     rc_[i] = ph == 0 ? min(min(min(a0[i], a1[i]), a2[i]), a3[i])
                                      : min(min(min(min(rc_[i], a0[i]), a1[i]), a2[i]), a3[i]);
-                // the previous tile's row butterfly (tile NT16 - 1 of the previous chunk for t = 0), a level a step
-                if constexpr (ph == 1) row16_level8(r[(t + 1) & 1], lo_lane, bu);
-                if constexpr (ph == 2) bw = row16_level4(bu);
-                if constexpr (ph == 3) row_dst[(t > 0 ? rbo : rbo_prev) + (t > 0 ? t - 1 : NT16 - 1) * 16] = row16_quad(bw);
+                // the previous tile's raw row minima (tile NT16 - 1 of the previous chunk for t = 0)
+                if constexpr (ph == 0) raw_write(t > 0 ? wr_cur : wr_prev, t > 0 ? t - 1 : NT16 - 1, r[(t + 1) & 1]);
+                // the reader of the previous chunk: group j's reads behind tile j's write, its minima two steps
+                // on, the rows stored well in front of the barrier their merge reads behind
+                if constexpr (ph == 0 && t < 4) raw_read(rd_prev, t, rdv);
+                if constexpr (ph == 2 && t < 4) {
+                    if constexpr (t == 0) raw_group(0, rdv, racc);
+                    else raw_group(t, rdv, rx);
+                    if constexpr (t == 1) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) racc[i] = min(racc[i], rx[i]);
+                    }
+                    if constexpr (t == 2) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) rh[i] = rx[i];
+                    }
+                    if constexpr (t == 3) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) racc[i] = min(min(racc[i], rh[i]), rx[i]);
+                    }
+                }
+                if constexpr (st == RSTORE) raw_store(rbo_prev, racc);
                 // the operand reads of tile t + 2 (flattened across chunks), behind the last MFMAs of tile t;
                 // from tile NT16 on they read the next chunk's stage
                 if constexpr (ph == SPT - 1) {
@@ -1573,13 +1618,19 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
                         mU2 = min(max(mU1, uw), mU2);
                         mU1 = min(mU1, uw);
                     }
+                    // (no instruction: it keeps the eleven minima above in this step.  With the chunk instantiated
+                    //  twice the compiler otherwise forms them where step BAR + 3's store reads them -- one gap of 23
+                    //  and three empty gaps, against tests/test_sweep16_gaps.py's largest gap <= 11 and <= 2 empty
+                    //  gaps.  If a change of the `nv` deal makes it unnecessary, that test passes without it.)
+                    asm volatile("" : "+v"(mL), "+v"(mU1), "+v"(mU2));
                 }
                 if constexpr (st == BAR + 3)
                     __builtin_amdgcn_raw_buffer_store_b64(v2i{mL, pack_row_bounds(mL, mU1, mU2)}, rowp_rsrc,
                                                           merger && ch > 0 ? ((ch - 1) * CHUNK + mrow) * 8 : RANGE_DROP, 0, 0);
-                // 16 minima a step, the butterfly's piece, the chunk's own work: spread evenly over the eight gaps
-                constexpr int nv = 16 + (ph == 1 ? 8 : ph == 2 ? 3 : ph == 3 ? 2 : 0) + (staging ? 2 : 0) +
-                                   (st == BAR + 2 ? 11 : 0) + (st == BAR + 3 ? 5 : 0) + (st == NS - 1 ? 2 : 0) + (PIPE - 2);
+                // 16 minima a step, the reader's piece, the chunk's own work: spread evenly over the eight gaps
+                constexpr int nv = 16 + (ph == 2 && t < 4 ? (t & 1 ? 12 : 8) : 0) + (st == RSTORE ? 4 : 0) + (st == 0 ? 3 : 0) +
+                                   (staging ? 2 : 0) + (st == BAR + 2 ? 11 : 0) + (st == BAR + 3 ? 5 : 0) +
+                                   (st == NS - 1 ? 2 : 0) + (PIPE - 2);
                 static_for<0, 8>([&](auto g_c) {
                     constexpr int g = decltype(g_c)::value;
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1589,8 +1640,10 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
             });
             rbo_prev = rbo;
             rbo = rbo == 2 * NW * CHUNK ? 0 : rbo + NW * CHUNK;
-        }
-        (void)bu;
+        };
+        int ch = 0;
+        for (; ch + 2 < nchunks; ++ch) chunk(ch, int_c<1>{});
+        for (; ch < nchunks; ++ch) chunk(ch, int_c<0>{});
 #if defined(IAMX_T_STAMPS)
         {
             unsigned long long loop_c1;
@@ -1610,8 +1663,20 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
 #endif
         // this pair's first column-result row (it lands with the vmcnt(0) below)
         const int64_t col_v = A.col_off[u];
-        // the last chunk's last tile, its merge
-        row_dst[rbo_prev + (NT16 - 1) * 16] = row16_min4(r[(NT16 - 1) & 1], lo_lane);
+        // the last chunk's last tile, its reader, its merge
+        {
+            const int last = ((nchunks - 1) & 1) * SWEEP16_RAW_CHUNK;
+            raw_write(raw_wr + last, NT16 - 1, r[(NT16 - 1) & 1]);
+            v4i v[4][2];
+            int x[4][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) raw_read(raw_rd + last, j, v[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) raw_group(j, v[j], x[j]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[0][i] = min(min(x[0][i], x[1][i]), min(x[2][i], x[3][i]));
+            raw_store(rbo_prev, x[0]);
+        }
         wait_direct();
         __syncthreads();
         merge_rows(nchunks - 1, rbo_prev, merger);
@@ -3049,7 +3114,20 @@ extern "C" int iamx_knn2sym_sweep_items16(const int8_t *sdesc, const int32_t *sn
     if (n_u == 0 || n_items == 0) return IAMX_OK;
     SymArgs a{sdesc, sn2, sct, img_off, img_n, upairs, items, col_off, rowp_off, col, rowp, n_u, n_items,
               colmask SWEEP_STAMPS_ARG};
-    hipLaunchKernelGGL((knn2sym16_kernel<SWEEP16_PIPE>), dim3((unsigned)n_items), dim3(256), 0,
+    // (dynamic LDS above the 64 KB a launch gets by default: raised where a thread first launches on a device;
+    //  setting the same value again, from another thread, is harmless)
+    static thread_local int raised_dev = -1;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess)
+        return iamx::fail(IAMX_ELAUNCH, "iamx_knn2sym_sweep_items16: no current device");
+    if (dev != raised_dev) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&knn2sym16_kernel<SWEEP16_PIPE>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, SWEEP16_LDS_BYTES);
+        if (e != hipSuccess)
+            return iamx::fail(IAMX_ELAUNCH, "iamx_knn2sym_sweep_items16: dynamic LDS: %s", hipGetErrorString(e));
+        raised_dev = dev;
+    }
+    hipLaunchKernelGGL((knn2sym16_kernel<SWEEP16_PIPE>), dim3((unsigned)n_items), dim3(256), SWEEP16_LDS_BYTES,
                        iamx::as_stream(stream), a);
     return iamx::check_launch("iamx_knn2sym_sweep_items16");
 }
