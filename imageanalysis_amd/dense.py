@@ -10,7 +10,8 @@ surface is the sparse chains' Delaunay triangulation).
     refine_planes(planes, ratio)                         the size T of the next level's plane set
     refine(views, neighbours, ranges, coarse, planes, ratio=4, ...)   one finer level, swept only around
                                                          the coarse depths -> DepthMaps (REFINEMENT RULES)
-    fuse(views, depths, gsd)                             surviving points -> Surface (dsm, count)
+    fuse(views, depths, gsd, method='mean', ...)         surviving points -> Surface (dsm, count); method=
+                                                         'robust': ROBUST FUSION RULES (and support)
     save(surface, analysis_dir, points=None)             dense/dsm.npy, count.npy, dsm.wld, dense.json
     load(analysis_dir)                                   the inverse of save -> Surface
     fill(surface, rounds=8)                              holes closed from their rims -> (Surface, round_of)
@@ -154,6 +155,42 @@ cell (floor((y1 - north) / gsd), floor((east - x0) / gsd)).  Each cell holds an 
 int64 sum of rint(up 1024), both kept by integer atomics only: the result does not depend on
 scheduling.  dsm = float32(sum / 1024 / count) in float64, NaN where count == 0.
 
+ROBUST FUSION RULES (fuse(method='robust'); kernels: csrc/dense_fuse.hip; restated by
+tests/dense_fuse_restatement.py).  The mean above lets one wrong depth pull its cell by metres, and gives a
+cell that straddles a roof edge a height that exists nowhere.  This rule finds, per cell, the cluster of
+heights to average, from fixed-size histograms: one thread per point, integer atomics only.
+
+Parameters.  bins B, 4 .. 64 (IAMX_DENSE_FUSE_MIN_BINS, _MAX_BINS), default 32: histogram bins per cell.
+levels L, 1 .. 4 (IAMX_DENSE_FUSE_MAX_LEVELS), default 2.  band, metres, finite and > 0, default 0.5 gsd: the
+least bin width, wmin = max(1, rint(band 1024)) computed on the host, at most 2^40.  share, an integer
+1 .. 256, default 256: the first level's acceptance in 256ths of the strongest bin.  Anything else is a
+ValueError before any device call, and an error of the C entries without a launch.
+
+Frame and accepted points are the mean's: the frame from frame_of, cell = (floor((y1 - north) / gsd),
+floor((east - x0) / gsd)) inside the raster, q = rint(up 1024) as int64 accepted iff |q| <= 1e15 (a NaN
+fails every test).  count int32 counts a cell's accepted points: the mean's count, bit for bit.
+
+Range.  Per cell lo = min q, hi = max q over its accepted points (signed 64-bit atomic min and max).
+
+Level l = 1 .. L, for every cell with count > 0, all in int64:
+    wb = max(wmin, ceil((hi - lo + 1) / B))                     the integer ceiling
+    a point takes part iff lo <= q <= hi; its bin is b = (q - lo) div wb, below B by construction
+    hist[b] uint32;  s_b = hist[b-1] + hist[b] + hist[b+1], a bin outside 0 .. B-1 counting 0;  smax = max_b s_b
+    b* = the HIGHEST b with s_b 256 >= t smax;  t = share at level 1, 256 at every later level
+    lo' = max(lo, lo + (b* - 1) wb),  hi' = min(hi, lo + (b* + 2) wb - 1)      both from the OLD lo
+    (lo, hi) = (lo', hi')
+So level 1 picks the cluster, the highest one at least share/256 as populous as the strongest (a roof over
+the ground it hides, for share < 256); later levels centre on that cluster's mode; the higher bin wins a tie.
+
+Sum and resolve.  support int32 = the cell's accepted points with lo <= q <= hi after level L, sum int64 =
+the total of their q, dsm = float32(sum / 1024 / support) in float64 (iamx_dense_resolve as it is), NaN
+where count == 0; support >= 1 wherever count >= 1.  window int64 [H][W][2] = the final (lo, hi), (0, 0)
+for an empty cell.  lo, hi, the histograms, support and sum are each a minimum, a maximum or a count of
+integers: the result depends neither on scheduling nor on the order of the points.
+
+Memory: 4 bins + 16 + 4 + 4 + 8 + 4 bytes per cell (hist, window, count, support, sum, dsm); the size is
+checked against the device's free memory on the host.  Passes: 2 + L over the points, L over the cells.
+
 Fill (dense_fill) makes the fused DSM hole-free enough to drape frames over.  Round k = 1 .. rounds
 reads the raster as round k - 1 left it (ping-pong, nothing is updated in place).  A NaN cell with at
 least one finite value among its 8 neighbours becomes the float32 sum of those values divided by
@@ -181,6 +218,7 @@ NEIGHBOUR_RATIO = (0.05, 0.6)          # baseline over median chain depth
 RANGE_MARGIN = 0.1
 MAX_SIDE = 1 << 20
 REGULARIZE = ('none', 'sgm')
+FUSIONS = ('mean', 'robust')
 SGM_P1, SGM_P2 = 16, 128                 # the defaults of p1 / p2 (the table they come from)
 
 
@@ -211,10 +249,13 @@ class DepthMaps(object):
 
 class Surface(object):
     """dsm float32 [H, W] (NaN: empty), count int32 [H, W] (device tensors); x0 = west side of
-    column 0, y1 = north side of row 0, gsd metres per cell (local ENU about ned_reference)."""
+    column 0, y1 = north side of row 0, gsd metres per cell (local ENU about ned_reference).
+    fuse(method='robust'): support int32 [H, W], the points behind each height, and fusion, the dict of
+    the mode's parameters that save() writes; both None otherwise."""
 
-    def __init__(self, dsm, count, x0, y1, gsd):
+    def __init__(self, dsm, count, x0, y1, gsd, support=None, fusion=None):
         self.dsm, self.count, self.x0, self.y1, self.gsd = dsm, count, float(x0), float(y1), float(gsd)
+        self.support, self.fusion = support, fusion
 
     @property
     def shape(self):
@@ -572,16 +613,38 @@ def frame_of(east_min, east_max, north_min, north_max, gsd):
     return x0, y1, W, H
 
 
-def fuse(views, depths, gsd):
-    """The surviving points of depth_maps()'s result into a DSM at `gsd` metres per cell.  -> Surface"""
+def fusion_parameters(method='mean', bins=32, levels=2, band=None, share=256, gsd=None):
+    """the fusion and its parameters checked on the host (ValueError) -> None for 'mean', else the dict
+    dense.json carries: fusion, bins, levels, band in metres and share.  band None is 0.5 gsd, and stays
+    None where the gsd is not known yet (the command line checks its arguments before there is one)."""
+    from . import kernels
+    if method not in FUSIONS:
+        raise ValueError("method is one of %s, got %r" % (', '.join(FUSIONS), method))
+    if method == 'mean':
+        return None
+    if band is None and gsd is not None:
+        band = 0.5 * float(gsd)
+    bins, levels, _wmin, share = kernels.dense_fuse_check(bins, levels, 1.0 if band is None else band, share)
+    return {'fusion': method, 'bins': bins, 'levels': levels, 'band': None if band is None else float(band), 'share': share}
+
+
+def fuse(views, depths, gsd, method='mean', bins=32, levels=2, band=None, share=256):
+    """The surviving points of depth_maps()'s result into a DSM at `gsd` metres per cell.  method='mean': the
+    mean of a cell's points (THE RULES: Fusion); 'robust': ROBUST FUSION RULES with bins, levels, band (None:
+    0.5 gsd) and share, the Surface then carries support.  -> Surface"""
     import torch
     from . import kernels
+    mode = fusion_parameters(method, bins, levels, band, share, gsd)
     keep = depths.keep.reshape(-1).bool()
     if not bool(keep.any()):
         raise ValueError("no pixel survived: nothing to fuse")
     pts = depths.ned.reshape(-1, 3)[keep]
     lo, hi = pts.amin(dim=0).cpu().numpy(), pts.amax(dim=0).cpu().numpy()
     x0, y1, W, H = frame_of(float(lo[1]), float(hi[1]), float(lo[0]), float(hi[0]), gsd)
+    if mode is not None:
+        count, support, _total, _window, dsm = kernels.dense_fuse(depths.ned, depths.keep, x0, y1, gsd, W, H, bins=mode['bins'],
+                                                                  levels=mode['levels'], band=mode['band'], share=mode['share'])
+        return Surface(dsm, count, x0, y1, gsd, support=support, fusion=mode)
     count, _total, dsm = kernels.dense_splat(depths.ned, depths.keep, x0, y1, gsd, W, H)
     return Surface(dsm, count, x0, y1, gsd)
 
@@ -614,7 +677,9 @@ def save(surface, analysis_dir, points=None, extra=None):
     """<analysis_dir>/dense/dsm.npy (float32, NaN: empty), count.npy (int32), dsm.wld (the world file
     of the raster, local ENU metres, pixel-centre convention), dense.json; points = (xyz, intensity):
     points.ply as well; extra: a dict of further entries of dense.json (the semi-global mode's
-    parameters), appended after the others.  -> the json's dict"""
+    parameters), appended after the others.  A surface with support (fuse(method='robust')): support.npy
+    (int32) as well, and dense.json gains points_supporting, fusion, bins, levels, band and share; without
+    it the files are the ones written before that mode existed, byte for byte.  -> the json's dict"""
     import io
     from . import ortho, panda3d
     out_dir = os.path.join(analysis_dir, 'dense')
@@ -638,6 +703,13 @@ def save(surface, analysis_dir, points=None, extra=None):
             'bounds': {'west': surface.x0, 'east': surface.x0 + W * surface.gsd, 'north': surface.y1,
                        'south': surface.y1 - H * surface.gsd},
             'files': {'dsm': 'dsm.npy', 'count': 'count.npy', 'world_file': 'dsm.wld'}}
+    support = getattr(surface, 'support', None)
+    if support is not None:
+        support = support.cpu().numpy()
+        panda3d._write_atomic(os.path.join(out_dir, 'support.npy'), npy(support))
+        info['files']['support'] = 'support.npy'
+        info['points_supporting'] = int(support.sum())
+        info.update(getattr(surface, 'fusion', None) or {'fusion': 'robust'})
     if points is not None:
         panda3d._write_atomic(os.path.join(out_dir, 'points.ply'), ply_bytes(*points))
         info['files']['points'] = 'points.ply'
@@ -650,7 +722,7 @@ def save(surface, analysis_dir, points=None, extra=None):
 
 def load(analysis_dir, device=None):
     """<analysis_dir>/dense/dsm.npy, count.npy and dense.json back into a Surface, the inverse of
-    save().  The tensors go to the current HIP device; device=: somewhere else ('cpu': no device
+    save(); support.npy and the fusion's parameters too where the json names them.  The tensors go to the current HIP device; device=: somewhere else ('cpu': no device
     is needed)."""
     import torch
     out_dir = os.path.join(analysis_dir, 'dense')
@@ -664,13 +736,21 @@ def load(analysis_dir, device=None):
     if dsm.shape != (info['height'], info['width']):
         raise ValueError("%s: dsm.npy is %d x %d cells, dense.json says %d x %d"
                          % (out_dir, dsm.shape[1], dsm.shape[0], info['width'], info['height']))
+    support = fusion = None
+    if 'support' in files:
+        support = np.load(os.path.join(out_dir, files['support']))
+        if support.shape != dsm.shape or support.dtype != np.int32:
+            raise ValueError("%s: support.npy is int32 of the DSM's shape" % out_dir)
+        fusion = {k: info[k] for k in ('fusion', 'bins', 'levels', 'band', 'share') if k in info}
     if device is None:
         from . import kernels
         d, c = kernels._dev(dsm, torch.float32), kernels._dev(count, torch.int32)
+        s = kernels._dev(support, torch.int32) if support is not None else None
         torch.cuda.current_stream().synchronize()
     else:
         d, c = torch.from_numpy(dsm).to(device), torch.from_numpy(count).to(device)
-    return Surface(d, c, info['bounds']['west'], info['bounds']['north'], info['gsd'])
+        s = torch.from_numpy(support).to(device) if support is not None else None
+    return Surface(d, c, info['bounds']['west'], info['bounds']['north'], info['gsd'], support=s, fusion=fusion)
 
 
 def fill(surface, rounds=8):

@@ -2657,6 +2657,86 @@ def dense_splat(ned, keep, x0, y1, gsd, W, H, out=None):
     return count, total, dsm
 
 
+DENSE_FUSE_MIN_BINS, DENSE_FUSE_MAX_BINS, DENSE_FUSE_MAX_LEVELS = 4, 64, 4
+DENSE_FUSE_MAX_WIDTH = 1 << 40           # of wmin, the least bin width in units of q = rint(up 1024)
+
+
+def dense_fuse_check(bins=32, levels=2, band=None, share=256, gsd=None):
+    """the parameters of ROBUST FUSION RULES (dense.py), checked on the host -> (bins, levels, wmin, share)
+    with wmin = max(1, rint(band 1024)); band None: 0.5 gsd"""
+    if any(isinstance(v, float) and not float(v).is_integer() for v in (bins, levels, share)):
+        raise ValueError("bins, levels and share are integers, got %r, %r and %r" % (bins, levels, share))
+    bins, levels, share = int(bins), int(levels), int(share)
+    if not DENSE_FUSE_MIN_BINS <= bins <= DENSE_FUSE_MAX_BINS:
+        raise ValueError("bins is %d to %d, got %d" % (DENSE_FUSE_MIN_BINS, DENSE_FUSE_MAX_BINS, bins))
+    if not 1 <= levels <= DENSE_FUSE_MAX_LEVELS:
+        raise ValueError("levels is 1 to %d, got %d" % (DENSE_FUSE_MAX_LEVELS, levels))
+    if not 1 <= share <= 256:
+        raise ValueError("share is 1 to 256 (256ths of the strongest bin), got %d" % share)
+    if band is None:
+        if gsd is None:
+            raise ValueError("band defaults to half the gsd: one of them is wanted")
+        band = 0.5 * float(gsd)
+    band = float(band)
+    if not (band > 0.0 and math.isfinite(band)):
+        raise ValueError("band is a positive number of metres, got %r" % band)
+    wmin = max(1, int(np.rint(band * 1024.0)))
+    if wmin > DENSE_FUSE_MAX_WIDTH:
+        raise ValueError("band %g m is %d units of 1/1024 m, above 2^40" % (band, wmin))
+    return bins, levels, wmin, share
+
+
+def dense_fuse_bytes(W, H, bins):
+    """what dense_fuse holds per call: 4 bins (hist) + 16 (window) + 4 (count) + 4 (support) + 8 (sum) + 4 (dsm)
+    bytes per cell"""
+    return int(W) * int(H) * (4 * int(bins) + 16 + 4 + 4 + 8 + 4)
+
+
+def dense_fuse(ned, keep, x0, y1, gsd, W, H, bins=32, levels=2, band=None, share=256, out=None):
+    """The robust fusion rule (dense.py, ROBUST FUSION RULES): NED points [..., 3] (numpy or device) with keep
+    [...] (or None: all) into the raster frame; band None: 0.5 gsd.  2 + levels passes over the points, `levels`
+    over the cells and the resolve, stream ordered.  -> device count int32 [H, W], support int32 [H, W], sum
+    int64 [H, W] of the supporting rint(up 1024), window int64 [H, W, 2] = the final (lo, hi), dsm float32
+    [H, W].  out: those five; they are initialised here.  The call holds 4 bins + 40 bytes per cell
+    (dense_fuse_bytes), the histograms among them; more than the device has free is a ValueError before a launch."""
+    W, H, gsd = int(W), int(H), float(gsd)
+    if not (W >= 1 and H >= 1 and gsd > 0.0 and math.isfinite(gsd) and math.isfinite(x0) and math.isfinite(y1)):
+        raise ValueError("a raster frame of at least one cell at a positive gsd wanted")
+    bins, levels, wmin, share = dense_fuse_check(bins, levels, band, share, gsd)
+    dev = require_gpu()
+    need = dense_fuse_bytes(W, H, bins) if out is None else W * H * 4 * bins
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    if need > free:                                        # (free on the device, or free in torch's own pool)
+        raise ValueError("a %d x %d cell raster with %d bins takes %d bytes (4 bins + 40 per cell), %d are free"
+                         % (W, H, bins, need, free))
+    P = _dev(ned, F64).reshape(-1, 3)
+    n = int(P.shape[0])
+    Kp = None
+    if keep is not None:
+        Kp = _dev(keep, U8).reshape(-1)
+        if int(Kp.shape[0]) != n:
+            raise ValueError("one keep flag per point")
+    count, support, total, window, dsm = _dense_out(out, [((H, W), I32), ((H, W), I32), ((H, W), I64), ((H, W, 2), I64),
+                                                          ((H, W), torch.float32)], dev)
+    hist = torch.zeros((H, W, bins), dtype=I32, device=dev)          # (the bits of uint32 counters)
+    count.zero_()
+    support.zero_()
+    total.zero_()
+    window[..., 0] = torch.iinfo(I64).max
+    window[..., 1] = torch.iinfo(I64).min
+    L, s = lib(), stream_ptr()
+    frame = (_ptr(P), _ptr(Kp), n, float(x0), float(y1), gsd, W, H)
+    check(L.iamx_dense_fuse_range(*(frame + (_ptr(count), _ptr(window), s))), 'iamx_dense_fuse_range')
+    for level in range(levels):
+        check(L.iamx_dense_fuse_hist(*(frame + (_ptr(window), bins, wmin, _ptr(hist), s))), 'iamx_dense_fuse_hist')
+        check(L.iamx_dense_fuse_select(_ptr(count), W, H, bins, wmin, share if level == 0 else 256, _ptr(hist), _ptr(window),
+                                       s), 'iamx_dense_fuse_select')
+    check(L.iamx_dense_fuse_sum(*(frame + (_ptr(window), _ptr(support), _ptr(total), s))), 'iamx_dense_fuse_sum')
+    check(L.iamx_dense_resolve(_ptr(support), _ptr(total), W, H, _ptr(dsm), s), 'iamx_dense_resolve')
+    torch.cuda.current_stream().synchronize()
+    return count, support, total, window, dsm
+
+
 def dense_fill(dsm, rounds=8):
     """The DSM hole fill (dense.py, THE RULES: fill), one launch per round and one to sort the cells:
     dsm float32 [H, W] (numpy or device), NaN: empty.  -> device (filled float32 [H, W], round_of uint8

@@ -8,6 +8,8 @@ aggregation of dense.py's SEMI-GLOBAL RULES between the cost volume and the winn
 --refine LEVELS goes coarse to fine (dense.py's REFINEMENT RULES): the sweep above runs at
 scale / 2^LEVELS, and each level after it doubles the scale and sweeps, per tile, only a window of
 --refine-ratio times finer planes around the depths of the level before; --scale stays the final scale.
+--fusion robust replaces the mean of a cell's points by dense.py's ROBUST FUSION RULES (per-cell height
+histograms pick the cluster to average) and writes dense/support.npy beside the count.
 Run from the reference's scripts/ directory: python <repo>/imageanalysis_amd/scripts/5d-dense-surface.py PROJECT
 """
 import argparse
@@ -36,9 +38,15 @@ ap.add_argument('--paths', type=int, choices=(4, 8), default=8, help='sgm: direc
 ap.add_argument('--refine', type=int, default=0, metavar='LEVELS',
                 help='coarse to fine: sweep at scale / 2^LEVELS, then LEVELS guided levels up to --scale')
 ap.add_argument('--refine-ratio', type=int, default=4, metavar='R', help='refine: fine planes per coarse plane step')
+ap.add_argument('--fusion', choices=dense.FUSIONS, default='mean', help='mean: every point of a cell; robust: the cluster its histograms find')
+ap.add_argument('--fusion-bins', type=int, default=32, help='robust: histogram bins per cell, 4 .. 64')
+ap.add_argument('--fusion-levels', type=int, default=2, help='robust: histogram levels, 1 .. 4')
+ap.add_argument('--fusion-band', type=float, default=None, metavar='METRES', help='robust: least bin width (default: half the gsd)')
+ap.add_argument('--fusion-share', type=int, default=256, help='robust: first level accepts a cluster of this many 256ths of the strongest, 1 .. 256')
 args = ap.parse_args()
 try:
     sgm = dense.sgm_parameters(args.planes, args.regularize, args.p1, args.p2, args.paths)
+    fusion = dense.fusion_parameters(args.fusion, args.fusion_bins, args.fusion_levels, args.fusion_band, args.fusion_share)
     if not 0 <= args.refine <= 8:
         raise ValueError("--refine is 0 to 8 levels, got %d" % args.refine)
     planes_total = args.planes
@@ -83,9 +91,16 @@ if gsd <= 0.0:
     if not mids:
         raise SystemExit("no image of group %d observes a positioned chain" % args.group)
     gsd = mids[len(mids) // 2] / float(views[0].K[0])
-surface = dense.fuse(views, maps, gsd)
+if fusion is None:
+    surface = dense.fuse(views, maps, gsd)
+else:
+    surface = dense.fuse(views, maps, gsd, method=args.fusion, bins=fusion['bins'], levels=fusion['levels'],
+                         band=fusion['band'], share=fusion['share'])
 info = dense.save(surface, proj.analysis_dir, points=dense.surface_points(views, maps) if args.ply else None,
                   extra=mode)
 print('DSM: %d x %d cells at %.3f m, %d of them filled by %d points, %.1f s'
       % (info['width'], info['height'], gsd, info['cells_filled'], info['points_fused'], time.perf_counter() - t0))
+if fusion is not None:
+    print('Robust fusion: %d of the %d points support their cells (%d bins, %d levels, band %.3f m, share %d/256)'
+          % (info['points_supporting'], info['points_fused'], info['bins'], info['levels'], info['band'], info['share']))
 print('Wrote %s to %s/dense' % (', '.join(sorted(info['files'].values())), proj.analysis_dir))

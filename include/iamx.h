@@ -1900,6 +1900,48 @@ int iamx_dense_sweep_guided(const float *ref, const double *rays, const float *n
                             float *score, float *depth, float *around, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Dense surface, robust fusion (csrc/dense_fuse.hip): a DSM cell's height from the cluster of its
+ * points that per-cell histograms find, in place of the mean of all of them.  The rules are stated
+ * in imageanalysis_amd/dense.py ("ROBUST FUSION RULES") and restated in numpy by
+ * tests/dense_fuse_restatement.py; the device follows them bit for bit.  All pointers DEV.
+ *
+ * ned, keep, num_points, x0, y1, gsd, width, height are iamx_dense_splat's, and so is the set of
+ * accepted points: keep != 0, the cell inside the raster, q = rint(up 1024) with |q| <= 1e15.
+ * window [H][W][2] int64 = (lo, hi) of a cell in units of q; hist [H][W][bins] uint32;
+ * IAMX_DENSE_FUSE_MIN_BINS <= bins <= IAMX_DENSE_FUSE_MAX_BINS; wmin, the least bin width in units
+ * of q, 1 .. 2^40; the bin width of a window is wb = max(wmin, ceil((hi - lo + 1) / bins)).
+ *
+ * iamx_dense_fuse_range, one thread per point: adds 1 to count [H][W] and takes the signed 64-bit
+ *   atomic minimum / maximum of q into window; the caller starts count at 0 and every window at
+ *   (INT64_MAX, INT64_MIN).
+ * iamx_dense_fuse_hist, one thread per point: a point with lo <= q <= hi adds 1 to bin
+ *   (q - lo) div wb of its cell; the caller zeroes hist before the first level only.
+ * iamx_dense_fuse_select, 128 cells per workgroup: with s_b = hist[b-1] + hist[b] + hist[b+1] and
+ *   smax their largest, b* = the highest b with s_b 256 >= share smax; window becomes
+ *   (max(lo, lo + (b* - 1) wb), min(hi, lo + (b* + 2) wb - 1)), both from the old lo, and (0, 0) for
+ *   a cell with count == 0; hist is left zeroed for the next level.  share 1 .. 256.  One level of
+ *   the rule is hist then select; at most IAMX_DENSE_FUSE_MAX_LEVELS levels are meant to be chained.
+ * iamx_dense_fuse_sum, one thread per point: a point with lo <= q <= hi adds 1 to support [H][W] and
+ *   q to sum [H][W]; the caller zeroes both.  iamx_dense_resolve(support, sum) makes the DSM.
+ * A size or a parameter out of range, a null pointer: IAMX_EINVAL without a launch; num_points == 0:
+ * IAMX_OK without one (iamx_dense_fuse_select always launches).
+ * ------------------------------------------------------------------------------------ */
+#define IAMX_DENSE_FUSE_MIN_BINS 4
+#define IAMX_DENSE_FUSE_MAX_BINS 64
+#define IAMX_DENSE_FUSE_MAX_LEVELS 4
+int iamx_dense_fuse_range(const double *ned, const uint8_t *keep, int64_t num_points, double x0,
+                          double y1, double gsd, int width, int height, int32_t *count,
+                          int64_t *window, void *stream);
+int iamx_dense_fuse_hist(const double *ned, const uint8_t *keep, int64_t num_points, double x0,
+                         double y1, double gsd, int width, int height, const int64_t *window,
+                         int bins, int64_t wmin, uint32_t *hist, void *stream);
+int iamx_dense_fuse_select(const int32_t *count, int width, int height, int bins, int64_t wmin,
+                           int share, uint32_t *hist, int64_t *window, void *stream);
+int iamx_dense_fuse_sum(const double *ned, const uint8_t *keep, int64_t num_points, double x0,
+                        double y1, double gsd, int width, int height, const int64_t *window,
+                        int32_t *support, int64_t *sum, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * True orthophoto (csrc/ortho_dsm.hip): a group's frames draped over the dense DSM, every mosaic
  * pixel placed at its DSM height, projected through the full camera model and coloured only from
  * the frames that see it.  The rules are stated in imageanalysis_amd/ortho.py ("THE TRUE-ORTHO
