@@ -1899,6 +1899,15 @@ def image_prep_stages(h, w):
     return views
 
 
+def resize_area_shape(h, w, fx, fy):
+    """(rows, columns) of resize_area's result for an h x w image (host arithmetic, no device)"""
+    import ctypes
+    oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().iamx_image_area_dims(int(h), int(w), float(fx), float(fy), ctypes.byref(oh), ctypes.byref(ow)),
+          'iamx_image_area_dims')
+    return max(oh.value, 0), max(ow.value, 0)
+
+
 def resize_area(img, fx, fy):
     """cv2.resize(img, (0, 0), fx=fx, fy=fy, interpolation=cv2.INTER_AREA) on the device
     (csrc/image_area.hip; downscale only).  img uint8 [h,w,3] or [h,w] (numpy or device) ->
@@ -1911,12 +1920,8 @@ def resize_area(img, fx, fy):
         h, w, ch = src.shape
     else:
         raise ValueError("expected a uint8 [h,w,3] or [h,w] image")
-    import ctypes
-    oh, ow = ctypes.c_int(0), ctypes.c_int(0)
-    check(lib().iamx_image_area_dims(h, w, float(fx), float(fy), ctypes.byref(oh), ctypes.byref(ow)),
-          'iamx_image_area_dims')
     # (argument errors -- an upscale, an empty result -- are reported by the call before it launches)
-    shape = (max(oh.value, 0), max(ow.value, 0)) + ((ch,) if src.dim() == 3 else ())
+    shape = resize_area_shape(h, w, fx, fy) + ((ch,) if src.dim() == 3 else ())
     out = torch.empty(shape, dtype=U8, device=dev)
     check(lib().iamx_image_resize_area(_ptr(src), h, w, ch, float(fx), float(fy), _ptr(out), stream_ptr()),
           'iamx_image_resize_area')
@@ -2787,3 +2792,31 @@ def ortho_dsm_image(mode, dsm, ss, params, frame, image_index, box, acc, index, 
                                      params.ctypes.data_as(_lib.c_void_p), _ptr(frame), int(frame.shape[0]),
                                      int(frame.shape[1]), int(image_index), c0, r0, c1, r1, _ptr(acc), _ptr(index),
                                      _ptr(count), _ptr(bgr), stream_ptr()), 'iamx_ortho_dsm_image')
+
+
+def _ortho_dsm_args(params, box):
+    params = np.ascontiguousarray(params, np.float64)
+    if params.shape != (ORTHO_DSM_PARAMS,):
+        raise ValueError("%d parameters wanted" % ORTHO_DSM_PARAMS)
+    return params, tuple(int(v) for v in box)
+
+
+def ortho_dsm_owner(dsm, ss, params, frame_hw, image_index, box, metric, index, count):
+    """The owner pass of one image (ortho.py, THE TRUE-ORTHO RULES, mode multiband): mode best's count,
+    metric and index from the geometry alone; frame_hw = (h, w) of the frame that will follow, the
+    rest as ortho_dsm_image."""
+    params, (c0, r0, c1, r1) = _ortho_dsm_args(params, box)
+    check(lib().iamx_ortho_dsm_owner(_ptr(dsm), int(dsm.shape[0]), int(dsm.shape[1]), int(ss),
+                                     params.ctypes.data_as(_lib.c_void_p), int(frame_hw[0]), int(frame_hw[1]),
+                                     int(image_index), c0, r0, c1, r1, _ptr(metric), _ptr(index), _ptr(count),
+                                     stream_ptr()), 'iamx_ortho_dsm_owner')
+
+
+def ortho_dsm_layer(dsm, ss, params, frame, image_index, box, index, layer):
+    """The layer of one image over its work box: layer device float32 [box pixels][4] = (C_b, C_g,
+    C_r, A), iamx_ortho_mb_layer's layout; every pixel of the box is written."""
+    params, (c0, r0, c1, r1) = _ortho_dsm_args(params, box)
+    check(lib().iamx_ortho_dsm_layer(_ptr(dsm), int(dsm.shape[0]), int(dsm.shape[1]), int(ss),
+                                     params.ctypes.data_as(_lib.c_void_p), _ptr(frame), int(frame.shape[0]),
+                                     int(frame.shape[1]), int(image_index), c0, r0, c1, r1, _ptr(index), _ptr(layer),
+                                     stream_ptr()), 'iamx_ortho_dsm_layer')

@@ -101,7 +101,7 @@ and L accumulates over its regions; the collapse runs once over every level.
 
 THE TRUE-ORTHO RULES
 
-    compose_dense(surface, cameras, frames, mode, upsample, bias)   the drape on ready arrays
+    compose_dense(surface, cameras, frames, mode, upsample, bias, bands=)   the drape on ready arrays
     render_dense(proj, group_list, group_index, surface, ...)       poses, frames and filters of a project
 
 A true orthophoto over the dense DSM (dense.py; 5e-true-ortho.py): every mosaic pixel is placed at
@@ -147,8 +147,38 @@ accumulators are those of best and feather above (iamx_ortho_clear and iamx_orth
             uncovered; count uint16, the images that cover AND see the pixel, saturating.
   feather   d = min(min(fx_, (w_k - 1) - fx_), min(fy_, (h_k - 1) - fy_)),
             w = max(d / (0.5 min(w_k - 1, h_k - 1)), 2^-20); accumulated and resolved as feather above.
-  multiband with a dense surface is a ValueError: its pyramid kernels want an owner pass and a layer
-            pass from this kernel (a later change).
+  multiband mode='multiband' stays a ValueError over a dense surface; the blend is asked for with
+            bands=B, 1 .. 16, beside mode='best' (bands=0, the default, is mode best as above; a
+            non-integer, a value outside 0 .. 16 or bands > 0 with mode feather is a ValueError before
+            any device call).  It is mode multiband above along mode best's seams HERE, with the two
+            passes that its pyramid kernels want from csrc/ortho_dsm.hip
+            (tests/ortho_dense_multiband_restatement.py restates it).  Everything not said here is
+            the rules of this section (height, cover, visibility, sample, work box) and mode
+            multiband's (bands, reduce, expand, pyramids, accumulate, resolve, extents), as written.
+    owner   before any layer: index and count of compose_dense(mode='best') on the same surface,
+            cameras and frame sizes, byte for byte.  It is geometry only: it needs each frame's
+            (h_k, w_k), and through them K_k, but no pixels.  The metric plane (8 bytes per mosaic
+            pixel) is freed before the first layer, as in the sparse mode.
+    layer   of image k, over its work box: C_k(p) = the bilinear sample in float64, cast to float32,
+            wherever image k COVERS p, whether it sees p or not, 0 elsewhere; A_k(p) = 1 where
+            index(p) == k, else 0.  Four floats (C_b, C_g, C_r, A) per pixel in the layout
+            iamx_ortho_mb_layer writes.  Every pixel of the box is written: the layer buffer is
+            reused between images and is not cleared.
+            Why covered and not seen: the owner already keeps an occluded view from colouring a pixel
+            at full resolution, and what the coarse bands of a neighbour bring across a seam is
+            low-frequency colour.  With a zero inside the occlusion shadow the result leaves the range
+            of the inputs.  A numpy prototype (the roof scene of tests/test_ortho_dense.py at 96 x 96,
+            its first three cameras, flat 400 x 400 frames of 100, 200 and 150 at focal 150 so that
+            every camera covers the whole mosaic, bias 0.5) gave blended pixels of 86 .. 222 at 3 bands
+            and 98 .. 225 at 5 with a layer of the visible pixels only, and 100 .. 200 at 1, 3, 5 and 8
+            bands with the rule above: under it every level of every image is its colour times the
+            same border term, so the blend is a convex combination.  On the same scene at 5 bands,
+            inside a margin of 8 pixels, the largest step between neighbouring pixels was 5 where mode
+            best has 100 (the largest overall, 59, sits in a corner of the mosaic: the zero padding,
+            as in the sparse mode), and a single image came out within one grey level of mode best.
+    pyramids, accumulate, resolve, extents: the sparse mode's, with the work box in place of the
+            pixel box: level_regions(box, sizes).  bgr is 0 where count == 0.  The Mosaic carries
+            mode 'multiband', bands = L, surface 'dense', upsample, bias, index and count.
 
 Work box per image (host, float64; work_box()): the undistorted rays (undistort.undistort_points) of
 the frame's four corners and of every 32nd border pixel are cut with the horizontal planes at the
@@ -160,11 +190,14 @@ between two samples, the float32 of the undistortion and the rounding of h), the
 It assumes a distortion model that is monotonic over the frame's cone.  The restatement computes
 every image over the whole mosaic; equality checks the box.
 
-Departures, none of them measured on real frames.  Occluders are the DSM's cells at their nearest-cell
+Departures, none of them measured on real frames.  Whether the blend's covered-not-seen layer shows
+as ghosting on real frames (an occluded view's colour of the roof, where the ground is owned by
+another, enters the coarse bands beside the seam) has not been measured.  Occluders are the DSM's cells at their nearest-cell
 heights while the point's own height is bilinear: on a slope steeper than bias / gsd per cell a
 point can be hidden by the cell it stands in or the next one, which is what bias is for.  bias=None
 means 1.0 gsd; no real DSM has been measured against that default.  Memory: the mosaic's
-accumulators as above (17 or 37 bytes per pixel) plus the DSM.
+accumulators as above (17 or 37 bytes per pixel; with bands, multiband_bytes(sizes, work boxes)) plus
+the DSM.
 """
 import ctypes
 import json
@@ -367,7 +400,88 @@ def _check_frame(frame):
     return frame.contiguous()
 
 
-class _Composer(object):
+class _Pyramids(object):
+    """mode multiband's level accumulators and the steps every multiband composer shares: the layer
+    pyramid of one image into the accumulators, the collapse.  A composer provides sizes, index, count,
+    bgr, dev, mode, _p and _call = (lib, check, stream_ptr), and writes the level-0 layer itself."""
+
+    def _mb_alloc(self, torch, temp_bytes):
+        """the accumulators of every level, zeroed, and the layer pyramid's buffer"""
+        self.bands = len(self.sizes)
+        self.offsets = np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])]).astype(np.int64)
+        self.acc = torch.zeros((int(self.offsets[-1]), 4), dtype=torch.float32, device=self.dev)
+        self.temp = torch.empty((max(temp_bytes // 16, 1), 4), dtype=torch.float32, device=self.dev)
+        self.finished = False
+
+    def _level(self, l):
+        return self.acc[int(self.offsets[l]):int(self.offsets[l + 1])]
+
+    def accumulators(self):
+        """multiband, before finish(): per level (N float32 [H_l][W_l][3], D float32 [H_l][W_l]), views"""
+        if self.mode != 'multiband' or self.finished:
+            raise RuntimeError("accumulators(): mode multiband only, and before finish() (the collapse works in place)")
+        out = []
+        for l, (h, w) in enumerate(self.sizes):
+            a = self._level(l).view(h, w, 4)
+            out.append((a[:, :, :3], a[:, :, 3]))
+        return out
+
+    def _mb_layers(self, box):
+        """(per-level regions, per-level layer buffers) of an image with the level-0 box (c0, r0, c1, r1)"""
+        regions = level_regions(box, self.sizes)
+        at = np.concatenate([[0], np.cumsum([_area(r) for r in regions])])
+        return regions, [self.temp[int(at[l]):int(at[l + 1])] for l in range(len(regions))]
+
+    def _mb_reduce(self, plan):
+        """kernel (b): the layer's Gaussian pyramid"""
+        L, check, stream_ptr = self._call
+        p = self._p
+        regions, layers = plan[-2:]
+        st = stream_ptr()
+        for l in range(len(regions) - 1):
+            h, w = self.sizes[l]
+            check(L.iamx_ortho_mb_reduce(h, w, p(layers[l]), *regions[l], p(layers[l + 1]), *regions[l + 1], st),
+                  'iamx_ortho_mb_reduce')
+
+    def _mb_accumulate(self, plan):
+        """kernel (c): every level of the pyramid into the accumulators"""
+        L, check, stream_ptr = self._call
+        p = self._p
+        regions, layers = plan[-2:]
+        st = stream_ptr()
+        top = len(regions) - 1
+        for l in range(top + 1):
+            h, w = self.sizes[l]
+            coarse, cr = (p(layers[l + 1]), regions[l + 1]) if l < top else (None, (0, 0, 0, 0))
+            check(L.iamx_ortho_mb_accumulate(h, w, p(layers[l]), *regions[l], coarse, *cr, p(self._level(l)), st),
+                  'iamx_ortho_mb_accumulate')
+
+    def _mb_pyramid(self, plan):
+        """kernels (b) and (c): the layer's Gaussian pyramid, then every level into the accumulators"""
+        self._mb_reduce(plan)
+        self._mb_accumulate(plan)
+
+    def _mb_collapse(self):
+        """kernel (d), from the top level down; level 0 ends in bgr"""
+        L, check, stream_ptr = self._call
+        p = self._p
+        top = len(self.sizes) - 1
+        for l in range(top, -1, -1):
+            h, w = self.sizes[l]
+            up = p(self._level(l + 1)) if l < top else None
+            count, bgr = (p(self.count), p(self.bgr)) if l == 0 else (None, None)
+            check(L.iamx_ortho_mb_collapse(h, w, p(self._level(l)), up, count, bgr, stream_ptr()),
+                  'iamx_ortho_mb_collapse')
+
+    def _mb_finish(self):
+        if self.finished:
+            raise RuntimeError("finish() was called before: the collapse works in place")
+        self.finished = True
+        self._mb_collapse()
+        self.temp = None
+
+
+class _Composer(_Pyramids):
     """the accumulators of one mosaic and the group's tables on the device; add(k, frame) rasterises
     image k (call it in group order), finish() -> Mosaic"""
 
@@ -452,24 +566,7 @@ class _Composer(object):
                                         rf.H, rf.W, p(metric), p(self.index), p(self.count), stream_ptr()),
                   'iamx_ortho_mb_owner')
         del metric                                         # (stream ordered: the allocator hands it on in order)
-        self.bands = len(self.sizes)
-        self.offsets = np.concatenate([[0], np.cumsum([h * w for h, w in self.sizes])]).astype(np.int64)
-        self.acc = torch.zeros((int(self.offsets[-1]), 4), dtype=torch.float32, device=dev)
-        self.temp = torch.empty((max(temp_bytes // 16, 1), 4), dtype=torch.float32, device=dev)
-        self.finished = False
-
-    def _level(self, l):
-        return self.acc[int(self.offsets[l]):int(self.offsets[l + 1])]
-
-    def accumulators(self):
-        """multiband, before finish(): per level (N float32 [H_l][W_l][3], D float32 [H_l][W_l]), views"""
-        if self.mode != 'multiband' or self.finished:
-            raise RuntimeError("accumulators(): mode multiband only, and before finish() (the collapse works in place)")
-        out = []
-        for l, (h, w) in enumerate(self.sizes):
-            a = self._level(l).view(h, w, 4)
-            out.append((a[:, :, :3], a[:, :, 3]))
-        return out
+        self._mb_alloc(torch, temp_bytes)
 
     def _mb_plan(self, k):
         """image k's launch arguments: (params, pixel box, per-level regions, per-level layer buffers);
@@ -478,9 +575,7 @@ class _Composer(object):
         box = self.boxes[k]
         if params is None or box[2] < box[0] or box[3] < box[1]:
             return None
-        regions = level_regions(box, self.sizes)
-        at = np.concatenate([[0], np.cumsum([_area(r) for r in regions])])
-        return params, box, regions, [self.temp[int(at[l]):int(at[l + 1])] for l in range(len(regions))]
+        return (params, box) + self._mb_layers(box)
 
     def _mb_layer(self, k, frame, plan):
         """kernel (a): C_k and A_k over the image's pixel box"""
@@ -492,48 +587,15 @@ class _Composer(object):
                                     p(frame), int(frame.shape[0]), int(frame.shape[1]), params, int(k), *box,
                                     rf.H, rf.W, p(self.index), p(layers[0]), stream_ptr()), 'iamx_ortho_mb_layer')
 
-    def _mb_pyramid(self, plan):
-        """kernels (b) and (c): the layer's Gaussian pyramid, then every level into the accumulators"""
-        L, check, stream_ptr = self._call
-        p = self._p
-        _params, _box, regions, layers = plan
-        st = stream_ptr()
-        top = len(regions) - 1
-        for l in range(top):
-            h, w = self.sizes[l]
-            check(L.iamx_ortho_mb_reduce(h, w, p(layers[l]), *regions[l], p(layers[l + 1]), *regions[l + 1], st),
-                  'iamx_ortho_mb_reduce')
-        for l in range(top + 1):
-            h, w = self.sizes[l]
-            coarse, cr = (p(layers[l + 1]), regions[l + 1]) if l < top else (None, (0, 0, 0, 0))
-            check(L.iamx_ortho_mb_accumulate(h, w, p(layers[l]), *regions[l], coarse, *cr, p(self._level(l)), st),
-                  'iamx_ortho_mb_accumulate')
-
     def _add_multiband(self, k, frame):
         plan = self._mb_plan(k)
         if plan is not None:
             self._mb_layer(k, frame, plan)
             self._mb_pyramid(plan)
 
-    def _mb_collapse(self):
-        """kernel (d), from the top level down; level 0 ends in bgr"""
-        L, check, stream_ptr = self._call
-        p = self._p
-        top = len(self.sizes) - 1
-        for l in range(top, -1, -1):
-            h, w = self.sizes[l]
-            up = p(self._level(l + 1)) if l < top else None
-            count, bgr = (p(self.count), p(self.bgr)) if l == 0 else (None, None)
-            check(L.iamx_ortho_mb_collapse(h, w, p(self._level(l)), up, count, bgr, stream_ptr()),
-                  'iamx_ortho_mb_collapse')
-
     def _finish_multiband(self):
         rf = self.rf
-        if self.finished:
-            raise RuntimeError("finish() was called before: the collapse works in place")
-        self.finished = True
-        self._mb_collapse()
-        self.temp = None
+        self._mb_finish()
         return Mosaic(bgr=self.bgr, index=self.index, count=self.count, x0=rf.x0, y1=rf.y1, gsd=rf.gsd,
                       mode=self.mode, names=self.names, bands=self.bands)
 
@@ -762,18 +824,32 @@ def surface_heights(dsm):
     return float(finite.min()), float(finite.max()), float(finite.double().mean())
 
 
-class _DenseComposer(object):
-    """the accumulators of one true orthophoto and the DSM on the device; add(k, camera, frame)
-    drapes image k (call it in group order), finish() -> Mosaic"""
+def _check_bands(mode, bands):
+    """compose_dense's bands: 0 (no blend) .. 16, an integer; a blend follows mode best's seams"""
+    if mode == 'multiband':
+        raise ValueError("mode multiband over a dense surface is asked for with bands=: mode='best', bands=1 .. %d"
+                         % MAX_BANDS)
+    if mode not in DENSE_MODES:
+        raise ValueError("mode must be 'best' or 'feather'")
+    if isinstance(bands, bool) or not isinstance(bands, (int, np.integer)) or not 0 <= int(bands) <= MAX_BANDS:
+        raise ValueError("bands is an integer 0 .. %d (got %r)" % (MAX_BANDS, bands))
+    if bands and mode != 'best':
+        raise ValueError("bands=%d blends along mode best's seams: mode %s takes bands=0 only" % (bands, mode))
+    return int(bands)
 
-    def __init__(self, surface, mode, upsample, bias, names=None):
+
+class _DenseComposer(_Pyramids):
+    """the accumulators of one true orthophoto and the DSM on the device; add(k, camera, frame)
+    drapes image k (call it in group order), finish() -> Mosaic.  bands > 0 (mode multiband's blend
+    along best's seams) wants every camera and every frame's (h, w) up front (frame_sizes: a list, or
+    a function of this composer that returns one): the owner pass runs here, add() then takes the
+    frames, each of the size it was announced with."""
+
+    def __init__(self, surface, mode, upsample, bias, names=None, bands=0, cameras=None, frame_sizes=None):
         import torch
         from . import kernels
         from ._lib import check, lib, require_gpu, stream_ptr
-        if mode == 'multiband':
-            raise ValueError("mode multiband over a dense surface is not built: use 'best' or 'feather'")
-        if mode not in DENSE_MODES:
-            raise ValueError("mode must be 'best' or 'feather'")
+        bands = _check_bands(mode, bands)
         if isinstance(upsample, bool) or int(upsample) != upsample or not 1 <= int(upsample) <= MAX_UPSAMPLE:
             raise ValueError("upsample is an integer 1 .. %d (got %r)" % (MAX_UPSAMPLE, upsample))
         gsd = float(surface.gsd)
@@ -784,6 +860,11 @@ class _DenseComposer(object):
             raise ValueError("bias is a finite number of metres, at least 0 (got %r)" % bias)
         if len(surface.dsm.shape) != 2 or min(surface.dsm.shape) < 1:
             raise ValueError("a DSM is [H, W]")
+        if bands:
+            mode = 'multiband'
+            if cameras is None or frame_sizes is None:
+                raise ValueError("bands > 0 wants every camera and every frame's (h, w) before the first frame")
+            cameras = [_camera_of(cam) for cam in cameras]
         self.mode, self.ss, self.bias, self.names = mode, int(upsample), bias, list(names) if names is not None else None
         H, W = (int(v) for v in surface.dsm.shape)
         self.Ho, self.Wo, self.g = H * self.ss, W * self.ss, gsd / self.ss
@@ -792,16 +873,20 @@ class _DenseComposer(object):
         self.x0, self.y1, self.gsd = float(surface.x0), float(surface.y1), gsd
         dev = self.dev = require_gpu()
         need = self.Wo * self.Ho * BYTES_PER_PIXEL[mode]
-        free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
-        if need > free:
-            raise MemoryError("a %d x %d pixel mosaic (mode %s) needs %.2f GB of accumulators, %.2f GB of device "
-                              "memory are free: use a smaller upsample (band splitting is not implemented)"
-                              % (self.Wo, self.Ho, mode, need / 1e9, free / 1e9))
+        if bands:
+            # (the boxes want the DSM's heights on the device: first what holds whatever they are)
+            self.sizes = band_levels(self.Ho, self.Wo, bands)
+            stay, metric, _temp = multiband_bytes(self.sizes, [])
+            need = stay + metric + 4 * H * W
+        self._fits(torch, need)
         self.dsm = kernels._dev(surface.dsm, torch.float32)
         self.z_lo, self.z_hi, self.z_mean = surface_heights(self.dsm)
         n = (self.Ho, self.Wo)
         self._p, self._kernels = kernels._ptr, kernels
         self._call = (lib(), check, stream_ptr)
+        if bands:
+            self._init_multiband(torch, cameras, frame_sizes)
+            return
         self.acc = torch.empty(n if mode == 'best' else n + (4,), dtype=torch.float64, device=dev)
         self.index = torch.empty(n, dtype=torch.int32, device=dev) if mode == 'best' else None
         self.count = torch.empty(n, dtype=torch.uint16, device=dev)
@@ -810,37 +895,108 @@ class _DenseComposer(object):
         check(L.iamx_ortho_clear(MODES[mode], self.Ho, self.Wo, p(self.acc), p(self.index), p(self.count), p(self.bgr),
                                  stream_ptr()), 'iamx_ortho_clear')
 
+    def _fits(self, torch, need):
+        free = torch.cuda.mem_get_info()[0] + torch.cuda.memory_reserved() - torch.cuda.memory_allocated()
+        if need > free:
+            raise MemoryError("a %d x %d pixel mosaic (mode %s) needs %.2f GB of accumulators, %.2f GB of device "
+                              "memory are free: use a smaller upsample (band splitting is not implemented)"
+                              % (self.Wo, self.Ho, self.mode, need / 1e9, free / 1e9))
+
     def box(self, K, dist, R, C, w, h):
         return work_box(K, dist, R, C, w, h, self.z_lo, self.z_hi, self.x0, self.y1, self.g, self.Ho, self.Wo)
 
-    def add(self, k, camera, frame):
+    def _image(self, camera, h, w):
+        """-> (the kernels' parameters, the work box) of a camera with an h x w frame"""
         from . import dense
-        K, width, height, dist, R, C = _camera_of(camera)
-        _check_dense_frame(frame)
-        frame = self._kernels._dev(frame, self._kernels.U8)
-        h, w = int(frame.shape[0]), int(frame.shape[1])
+        K, width, height, dist, R, C = camera
         Ks = dense.scaled_K(K, width, height, w, h)
         params = self._kernels.ortho_dsm_params(self.x0, self.y1, self.gsd, self.bias, self.z_hi, Ks, dist, R, C)
-        self._kernels.ortho_dsm_image(MODES[self.mode], self.dsm, self.ss, params, frame, k,
-                                      self.box(Ks, dist, R, C, w, h), self.acc, self.index, self.count, self.bgr)
+        return params, self.box(Ks, dist, R, C, w, h)
+
+    # ---- bands > 0: mode multiband's blend ----
+    def _init_multiband(self, torch, cameras, frame_sizes):
+        """the owner pass (mode best's index and count, from the geometry and the frame sizes alone),
+        then the accumulators of every level, zeroed, and the layer pyramid's buffer"""
+        L, check, stream_ptr = self._call
+        p, dev, n = self._p, self.dev, (self.Ho, self.Wo)
+        if callable(frame_sizes):                          # (render_dense: they depend on the DSM's mean height)
+            frame_sizes = frame_sizes(self)
+        self.frame_sizes = frame_sizes = [(int(h), int(w)) for h, w in frame_sizes]
+        if len(frame_sizes) != len(cameras) or any(h < 2 or w < 2 for h, w in frame_sizes):
+            raise ValueError("one frame size (h, w), at least 2 x 2, per camera")
+        self.images = [self._image(cam, h, w) for cam, (h, w) in zip(cameras, frame_sizes)]
+        stay, metric_bytes, temp_bytes = multiband_bytes(self.sizes, [box for _params, box in self.images])
+        self._fits(torch, stay + max(metric_bytes, temp_bytes))      # (the DSM is allocated by now)
+        self.index = torch.empty(n, dtype=torch.int32, device=dev)
+        self.count = torch.empty(n, dtype=torch.uint16, device=dev)
+        self.bgr = torch.empty(n + (3,), dtype=torch.uint8, device=dev)
+        metric = torch.empty(n, dtype=torch.float64, device=dev)
+        check(L.iamx_ortho_clear(MODES['best'], self.Ho, self.Wo, p(metric), p(self.index), p(self.count), p(self.bgr),
+                                 stream_ptr()), 'iamx_ortho_clear')
+        for k, ((params, box), hw) in enumerate(zip(self.images, frame_sizes)):
+            self._kernels.ortho_dsm_owner(self.dsm, self.ss, params, hw, k, box, metric, self.index, self.count)
+        del metric                                         # (stream ordered: the allocator hands it on in order)
+        self._mb_alloc(torch, temp_bytes)
+
+    def _mb_plan(self, k):
+        """image k's launch arguments: (params, work box, per-level regions, per-level layer buffers);
+        None when its work box is empty"""
+        params, box = self.images[k]
+        if box[2] < box[0] or box[3] < box[1]:
+            return None
+        return (params, box) + self._mb_layers(box)
+
+    def _mb_layer(self, k, frame, plan):
+        """C_k and A_k over the image's work box"""
+        params, box, _regions, layers = plan
+        self._kernels.ortho_dsm_layer(self.dsm, self.ss, params, frame, k, box, self.index, layers[0])
+
+    def _add_multiband(self, k, frame):
+        if self.finished:
+            raise RuntimeError("add() after finish(): the collapse works in place")
+        name = self.names[k] if self.names is not None else 'image %d' % k
+        if (int(frame.shape[0]), int(frame.shape[1])) != self.frame_sizes[k]:
+            raise RuntimeError("%s: a %d x %d frame arrived where the owner pass was told %d x %d (nothing of it "
+                               "is accumulated)" % ((name, frame.shape[1], frame.shape[0]) + self.frame_sizes[k][::-1]))
+        frame = self._kernels._dev(frame, self._kernels.U8)
+        plan = self._mb_plan(k)
+        if plan is not None:
+            self._mb_layer(k, frame, plan)
+            self._mb_pyramid(plan)
+
+    def add(self, k, camera, frame):
+        """bands > 0: the camera is the one the owner pass was given for image k, and is not read again"""
+        _check_dense_frame(frame)
+        if self.mode == 'multiband':
+            return self._add_multiband(k, frame)
+        frame = self._kernels._dev(frame, self._kernels.U8)
+        params, box = self._image(_camera_of(camera), int(frame.shape[0]), int(frame.shape[1]))
+        self._kernels.ortho_dsm_image(MODES[self.mode], self.dsm, self.ss, params, frame, k, box, self.acc, self.index,
+                                      self.count, self.bgr)
 
     def finish(self):
         L, check, stream_ptr = self._call
         p = self._p
+        extra = {}
+        if self.mode == 'multiband':
+            self._mb_finish()
+            extra['bands'] = self.bands
         if self.mode == 'feather':
             check(L.iamx_ortho_resolve(self.Ho, self.Wo, p(self.acc), p(self.count), p(self.bgr), stream_ptr()),
                   'iamx_ortho_resolve')
         return Mosaic(bgr=self.bgr, index=self.index, count=self.count, x0=self.x0, y1=self.y1, gsd=self.g,
-                      mode=self.mode, names=self.names, surface='dense', upsample=self.ss, bias=self.bias)
+                      mode=self.mode, names=self.names, surface='dense', upsample=self.ss, bias=self.bias, **extra)
 
 
-def compose_dense(surface, cameras, frames, mode='best', upsample=1, bias=None, names=None):
+def compose_dense(surface, cameras, frames, mode='best', upsample=1, bias=None, names=None, bands=0):
     """The true orthophoto on ready arrays (THE TRUE-ORTHO RULES): surface a dense.Surface (filled:
     dense.fill), cameras a list of (K at camera size, width, height, dist, R NED -> camera, C NED) or
     of dense.View-like objects, frames one BGR uint8 [h, w, 3] per camera (device tensors or numpy),
     of any size at least 2 x 2; upsample: mosaic pixels per DSM cell and side, 1 .. 8; bias: metres a
     DSM cell must stand above the ray to hide the point, None: 1.0 * surface.gsd -- a default no real
-    DSM has been measured against.  -> Mosaic (gsd: the mosaic's, surface.gsd / upsample)"""
+    DSM has been measured against; bands: 0, or with mode best 1 .. 16 pyramid levels of mode
+    multiband's blend along best's seams.  -> Mosaic (gsd: the mosaic's, surface.gsd / upsample; with
+    bands: mode 'multiband', bands the levels used)"""
     cameras, frames = list(cameras), list(frames)
     if len(frames) != len(cameras):
         raise ValueError("%d frames for %d cameras" % (len(frames), len(cameras)))
@@ -849,7 +1005,8 @@ def compose_dense(surface, cameras, frames, mode='best', upsample=1, bias=None, 
     for cam, frame in zip(cameras, frames):                # (every ValueError before any device call)
         _camera_of(cam)
         _check_dense_frame(frame)
-    comp = _DenseComposer(surface, mode, upsample, bias, names)
+    comp = _DenseComposer(surface, mode, upsample, bias, names, bands, cameras,
+                          [tuple(frame.shape[:2]) for frame in frames])
     for k, (cam, frame) in enumerate(zip(cameras, frames)):
         comp.add(k, cam, frame)
     return comp.finish()
@@ -878,13 +1035,25 @@ def _colour_frame(frame, name, histogram, mask):
     return kernels.colour_lut(frame, lut if lut is not None else _IDENTITY_LUT, mask)
 
 
+def _dense_frame_size(h, w, f, prefilter):
+    """render_dense's prefilter decision for an h x w frame with the factor f -> (the size (h, w) the
+    frame is draped at, shrunk?)"""
+    if prefilter and f < PREFILTER_BELOW and round(h * f) >= 2 and round(w * f) >= 2:
+        from . import kernels
+        return kernels.resize_area_shape(h, w, f, f), True
+    return (int(h), int(w)), False
+
+
 def render_dense(proj, group_list, group_index, surface, mode='best', upsample=1, bias=None, prefilter=True,
-                 histogram=False, vignette=False, frames=None):
+                 histogram=False, vignette=False, frames=None, bands=0):
     """The true orthophoto of one group over `surface` (dense.load, then dense.fill): poses from
     dense.image_pose, the optimised K and distortion as dense.views_from_project takes them, the
     frames decoded by histogram.frame_pass in group order (frames=: ready device tensors instead),
     the colour tables as prepare_frame applies them, and kernels.resize_area by
-    dense_prefilter_factor() when that is below 0.75.  -> Mosaic"""
+    dense_prefilter_factor() when that is below 0.75.  bands: compose_dense's; the owner pass then
+    runs before the first frame, on the sizes the frames will have (the camera's image size, or the
+    tensors' with frames=, after the prefilter decision), and a frame that arrives with another size
+    is a RuntimeError naming the image.  -> Mosaic"""
     from . import dense, histogram as _histogram, kernels
     t0 = time.perf_counter()
     camera = _deps.camera()
@@ -894,27 +1063,42 @@ def render_dense(proj, group_list, group_index, surface, mode='best', upsample=1
     group = dense.group_indices(proj, group_list, group_index)
     images = [proj.image_list[i] for i in group]
     names = [im.name for im in images]
-    comp = _DenseComposer(surface, mode, upsample, bias, names)
+    if frames is not None:
+        frames = list(frames)
+        if len(frames) != len(images):
+            raise ValueError("%d frames for the group's %d images" % (len(frames), len(images)))
+    cameras = raw = sizes = None
+    if _check_bands(mode, bands):
+        # the owner pass wants every frame's size before the first frame; the prefilter decision wants
+        # the DSM's mean height, which the composer knows once the DSM is on the device
+        cameras = [(K, width, height, dist) + tuple(dense.image_pose(im)) for im in images]
+        raw = [tuple(int(v) for v in f.shape[:2]) for f in frames] if frames is not None else \
+            [(int(height), int(width))] * len(images)
+
+        def sizes(comp):
+            return [_dense_frame_size(h, w, dense_prefilter_factor(K, cam[5], comp.z_mean, comp.g), prefilter)[0]
+                    for (h, w), cam in zip(raw, cameras)]
+    comp = _DenseComposer(surface, mode, upsample, bias, names, bands, cameras, sizes)
     mask = _vignette_mask(proj.analysis_dir) if vignette else None
     state = {'k': 0, 'shrunk': 0}
 
     def on_frames(batch):
         for frame in batch:
             k = state['k']
+            if raw is not None and tuple(int(v) for v in frame.shape[:2]) != raw[k]:
+                raise RuntimeError("%s: a %d x %d frame arrived where the owner pass was told %d x %d (nothing of "
+                                   "it is accumulated)" % ((names[k], frame.shape[1], frame.shape[0]) + raw[k][::-1]))
             frame = _colour_frame(_check_frame(frame), names[k], histogram, mask)
             R, C = dense.image_pose(images[k])
             if prefilter:
                 f = dense_prefilter_factor(K, C, comp.z_mean, comp.g)
-                if f < PREFILTER_BELOW and round(frame.shape[0] * f) >= 2 and round(frame.shape[1] * f) >= 2:
+                if _dense_frame_size(int(frame.shape[0]), int(frame.shape[1]), f, True)[1]:
                     frame = kernels.resize_area(frame, f, f)
                     state['shrunk'] += 1
             comp.add(k, (K, width, height, dist, R, C), frame)
             state['k'] = k + 1
 
     if frames is not None:
-        frames = list(frames)
-        if len(frames) != len(images):
-            raise ValueError("%d frames for the group's %d images" % (len(frames), len(images)))
         on_frames(frames)
     else:
         _histogram.frame_pass(images, want_hist=False, on_frames=on_frames)

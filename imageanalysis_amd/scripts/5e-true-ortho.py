@@ -22,6 +22,9 @@ ap.add_argument('--upsample', type=int, default=1, help='mosaic pixels per DSM c
 ap.add_argument('--mode', choices=ortho.DENSE_MODES, default='best',
                 help="best: the frame that looks most steeply down on the pixel; feather: the frames that see it, "
                      "blended by distance from their borders")
+ap.add_argument('--bands', type=int, default=0,
+                help='blend along the seams of mode best with this many pyramid levels, 1 .. %d (0: no blend)'
+                     % ortho.MAX_BANDS)
 ap.add_argument('--bias', type=float, default=None,
                 help='metres a DSM cell must stand above the ray to hide a pixel (default: one DSM cell, unmeasured)')
 ap.add_argument('--fill-rounds', type=int, default=8, help='rounds of the DSM hole fill, 0 .. 254')
@@ -41,6 +44,9 @@ print('Group sizes:', " ".join(str(len(g)) for g in group_list))
 
 if not os.path.exists(os.path.join(proj.analysis_dir, 'dense', 'dense.json')):
     raise SystemExit("%s/dense is missing: make the dense surface with 5d-dense-surface.py first" % proj.analysis_dir)
+if not 0 <= args.bands <= ortho.MAX_BANDS or (args.bands and args.mode != 'best'):
+    raise SystemExit("--bands is 0 .. %d and blends along the seams of --mode best (got --bands %d with --mode %s)"
+                     % (ortho.MAX_BANDS, args.bands, args.mode))
 if args.histogram and not histogram.load(proj.analysis_dir):
     raise SystemExit("--histogram: %s/histogram is missing (make it with 99-vignette.py --histogram)"
                      % proj.analysis_dir)
@@ -51,9 +57,11 @@ print('DSM: %d x %d cells at %.3f m, %d filled in %d rounds, %d still empty'
       % (surface.shape[1], surface.shape[0], surface.gsd, filled, args.fill_rounds, empty))
 mosaic = ortho.render_dense(proj, group_list, args.group, surface, mode=args.mode, upsample=args.upsample,
                             bias=args.bias, prefilter=not args.no_prefilter, histogram=args.histogram,
-                            vignette=args.vignette)
+                            vignette=args.vignette, bands=args.bands)
 h, w = mosaic.shape
 print('Mosaic: %d x %d pixels at %.3f m, bias %.3f m, %d images, %.1f frames/s'
       % (w, h, mosaic.gsd, mosaic.bias, ortho.render_dense_stats['images'], ortho.render_dense_stats['frames_per_s']))
+if args.bands:
+    print('Blended over %d pyramid levels' % mosaic.bands)
 info = ortho.save(mosaic, proj.analysis_dir, tile=args.tile, fmt=args.format, subdir='true_ortho')
 print('Wrote %d tiles and ortho.json to %s/true_ortho' % (len(info['tiles']), proj.analysis_dir))

@@ -1958,6 +1958,16 @@ int iamx_dense_fuse_sum(const double *ned, const uint8_t *keep, int64_t num_poin
  *   c0, r0, c1, r1: the inclusive work box in mosaic pixels (c1 < c0 or r1 < r0: nothing is launched
  *   and the call succeeds).  mode, acc, index, count and bgr are iamx_ortho_raster_image's, over the
  *   mosaic: iamx_ortho_clear starts them and iamx_ortho_resolve finishes mode feather.
+ * iamx_ortho_dsm_owner and iamx_ortho_dsm_layer, the two passes mode multiband's pyramid kernels
+ *   (iamx_ortho_mb_reduce, _accumulate, _collapse) want over the dense surface; dsm, H, W, ss, params,
+ *   h_s, w_s, image_index and the box are iamx_ortho_dsm_image's, and so are their checks.
+ *   owner: mode best without frame and bgr -- count, metric f64 [H ss][W ss] and index exactly as
+ *   iamx_ortho_dsm_image(mode 0) leaves count, acc and index; h_s, w_s: the size of the frame that
+ *   will follow (the cover rule needs it, the pixels are not read).
+ *   layer: no march.  layer f32 [r1 - r0 + 1][c1 - c0 + 1][4], 16-byte aligned, row-major over the
+ *   box, iamx_ortho_mb_layer's layout = (C_b, C_g, C_r, A): C the bilinear sample (f64, cast to f32)
+ *   wherever the image covers the pixel, seen or not, 0 elsewhere; A = 1 where index == image_index,
+ *   else 0.  Every pixel of the box is written; index [H ss][W ss] is only read.
  * iamx_dense_fill, one round of the DSM hole fill per launch: round 0 copies src to dst and writes
  *   round_dst = 0 for a finite cell, 255 for an empty one (round_src is not read and may be NULL);
  *   round k = 1 .. 254 gives an empty cell with a finite value among its 8 neighbours of src their
@@ -1973,6 +1983,12 @@ int iamx_ortho_dsm_image(int mode, const float *dsm, int H, int W, int ss, const
                          const uint8_t *frame, int h_s, int w_s, int image_index, int c0, int r0,
                          int c1, int r1, double *acc, int32_t *index, uint16_t *count, uint8_t *bgr,
                          void *stream);
+int iamx_ortho_dsm_owner(const float *dsm, int H, int W, int ss, const double *params, int h_s,
+                         int w_s, int image_index, int c0, int r0, int c1, int r1, double *metric,
+                         int32_t *index, uint16_t *count, void *stream);
+int iamx_ortho_dsm_layer(const float *dsm, int H, int W, int ss, const double *params,
+                         const uint8_t *frame, int h_s, int w_s, int image_index, int c0, int r0,
+                         int c1, int r1, const int32_t *index, float *layer, void *stream);
 int iamx_dense_fill(const float *src, const uint8_t *round_src, int width, int height, int round,
                     float *dst, uint8_t *round_dst, void *stream);
 
