@@ -334,7 +334,8 @@ struct SymArgs {
                                  //      that can be the query's best or second (narrow exact stage)
 #if defined(IAMX_T_STAMPS)
     unsigned long long *stamps;  // [workgroups][waves][4]: segment sum (knn2sym16_kernel: pair tails), chunks, loop cycles, loop 100 MHz ticks --
-                                 //      a buffer of its own: nothing in the library reads it
+                                 //      a buffer of its own: nothing in the library reads it; knn2sym16_kernel also writes
+                                 //      [workgroups][waves] item-start cycles behind that block (5 words a wave in all)
 #endif
 };
 
@@ -548,6 +549,24 @@ __device__ __forceinline__ void stage_piece_held(const void *gsrc, unsigned lds_
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(m0_was), "+v"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
     after = keep;
+}
+
+// The same piece where nothing has to hold it: a pair's first two stages of the 16x16x64 item kernel, issued in
+// front of the B slice's loads.  An asm load as above, so the compiler neither counts it -- the waits it puts
+// behind the loads that follow count those alone, and loads return in order -- nor puts a wait of its own in
+// front of a later LDS access; the kernel's explicit s_waitcnt vmcnt(0) in front of the pair's first barrier
+// waits for it.
+template <int BYTES>
+__device__ __forceinline__ void stage_piece(const void *gsrc, unsigned lds_dst)
+{
+    static_assert(BYTES == 16 || BYTES == 4, "one dwordx4 or one dword a lane");
+    unsigned m0_was;
+    if constexpr (BYTES == 16)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_was) : "v"(gsrc), "s"(lds_dst) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(m0_was) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
 // IAMX_T_STAMPS=<segment>: a DIAGNOSTIC build of form 2 (tools/sweep_stamps.py; never the shipped library)
@@ -1299,6 +1318,9 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 15, lg = lane >> 4;
     const int rn = ((n & 7) << 1) | (n >> 3);
+#if defined(IAMX_T_STAMPS)
+    const unsigned long long stamp_entry = __builtin_amdgcn_s_memtime();
+#endif
 
     int vid;
     {
@@ -1318,8 +1340,10 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
 #if defined(IAMX_T_STAMPS)
     // (the diagnostic build stamps this kernel's whole chunk loop -- chunks, cycles, 100 MHz ticks -- and the
     //  pair tail: the cycles from the end of a pair's chunk loop to the start of the item's next pair's, which
-    //  cover the last merge, the column epilogue, the barrier, the first two stages and the first operand reads)
-    unsigned long long stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0, stamp_tail = 0, stamp_c1 = 0;
+    //  cover the last merge, the column epilogue, the barrier, the first two stages and the first operand reads;
+    //  and the ITEM START: the cycles from the kernel's entry to the start of the first pair's chunk loop -- the
+    //  table chain, the B slice, the first two stages --, stored behind the [workgroups][waves][4] block)
+    unsigned long long stamp_chunks = 0, stamp_cycles = 0, stamp_ticks = 0, stamp_tail = 0, stamp_c1 = 0, stamp_start = 0;
 #endif
     // the table entries of the pair the loop runs next, read one pair ahead (see knn2sym_kernel)
     int nx_b = A.upairs[2 * u], nx_a = A.upairs[2 * u + 1];
@@ -1339,39 +1363,79 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
         //  lds_row reads -- before an invalid wave refills its rows with BIG below)
         if (uniform32(bimg_held) >= 0) __syncthreads();
 
+        const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
+        const int32_t *tci = A.sct + aoff;
+        // global -> LDS directly; the XOR swizzle of the 16-byte slots is applied on the source side
+        typedef __attribute__((address_space(3))) void *lds_ptr;
+        // (one lane offset for every piece and chunk beside a scalar base, the wave's LDS destination from a
+        //  scalar register: piece j holds rows 32 j + (tid >> 3), slot (tid & 7) ^ ((row >> 1) & 7))
+        const int wave_u = uniform32(wave);
+        const unsigned stage_voff = (unsigned)((tid >> 3) * D + (((tid & 7) ^ ((tid >> 4) & 7)) * 16));
+        const unsigned lds_tile_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tile + wave_u * (64 * 16));
+        const unsigned lds_tb_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tb + (wave_u & (CHUNK / 64 - 1)) * 64);
+        const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
+        // chunk `ch` into stage buffer `buf`: all 256 threads, five loads a lane
+        auto stage_direct = [&](int ch, int buf) {
+            const int8_t *const src = tbase + (int64_t)ch * (CHUNK * D) + stage_voff;
+#pragma unroll
+            for (int j = 0; j < PIECES; ++j)
+                stage_piece<16>(src + j * ((NT / 8) * D), lds_tile_at + buf * (CHUNK * D) + j * NT * 16);
+            stage_piece<4>(reinterpret_cast<const int8_t *>(tci + ch * CHUNK) + ct_voff, lds_tb_at + buf * (CHUNK * 4));
+        };
+        auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
+        // chunks 0 and 1 of the pair, as soon as its A image is known and in front of the B slice's loads: one
+        // round trip for the stage, the squared norms and the slice where B changes (the wait and the barrier
+        // in front of the first operand reads are below; every wave is past its reads of both stage buffers)
+        stage_direct(0, 0);
+        stage_direct(nchunks > 1 ? 1 : 0, 1);
+
         // B operand: rows past the end repeat the last row; the Cq floor of a lane's group of 32 rows
         // and the wave's largest spread S_w as in knn2sym_kernel
         if (bimg != uniform32(bimg_held)) {
             bimg_held = bimg;
+            // the squared norms the spread and the floors are made of: loaded in front of the slice, with it
+            // and not behind its wait (a wave past the end reads the image's last row and uses nothing of it)
+            int sn_lo, sn_hi, sn_fl[4];
+            {
+                const int g_lo = rn & ~1, g_hi = rn | 1;
+                const int r_lo = q0 + QB * g_lo < nb ? q0 + QB * g_lo : nb - 1;
+                const int r_hi = q0 + QB * g_hi + QB - 1 < nb ? q0 + QB * g_hi + QB - 1 : nb - 1;
+                sn_hi = A.sn2[boff + r_hi];
+                sn_lo = A.sn2[boff + r_lo];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int r_fl = q0 + 2 * QB * (2 * j + (lane & 1));
+                    sn_fl[j] = A.sn2[boff + (r_fl < nb ? r_fl : nb - 1)];
+                }
+            }
+            // (all 32 loads of a lane are issued before the first is waited for: the registers they land in are
+            //  free here, the column minima are not live yet; a wait behind every load made them 32 round trips)
+            v4i braw[QB][2];
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) {
                 int row = q0 + QB * rn + qb;
                 row = row < nb ? row : nb - 1;
                 const v4i *src = reinterpret_cast<const v4i *>(A.sdesc + (int64_t)(boff + row) * D);
 #pragma unroll
+                for (int s = 0; s < 2; ++s) braw[qb][s] = src[4 * s + lg];
+            }
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb) {
+#pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    bq[qb][s] = ~src[4 * s + lg];
+                    bq[qb][s] = ~braw[qb][s];
                     asm volatile("" : "+a"(bq[qb][s]));      // (only ever an MFMA source: the AGPR half)
                 }
             }
             {
-                int spread = 0;
-                if (wave_valid) {
-                    const int g_lo = rn & ~1, g_hi = rn | 1;
-                    const int r_lo = q0 + QB * g_lo < nb ? q0 + QB * g_lo : nb - 1;
-                    const int r_hi = q0 + QB * g_hi + QB - 1 < nb ? q0 + QB * g_hi + QB - 1 : nb - 1;
-                    spread = (A.sn2[boff + r_hi] >> 1) - (A.sn2[boff + r_lo] >> 1);
-                }
+                int spread = wave_valid ? (sn_hi >> 1) - (sn_lo >> 1) : 0;
 #pragma unroll
                 for (int sh = 32; sh >= 1; sh >>= 1) spread = max(spread, __shfl_xor(spread, sh));
                 if (lane == 0) lds_cq[wave] = spread;
             }
             // (group (n & 7) holds rows q0 + 32 (n & 7) ..: the floor its two lanes n, n ^ 8 share)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r_lo = q0 + 2 * QB * (2 * j + (lane & 1));
-                fl[j] = wave_valid ? A.sn2[boff + (r_lo < nb ? r_lo : nb - 1)] >> 1 : 0;
-            }
+            for (int j = 0; j < 4; ++j) fl[j] = wave_valid ? sn_fl[j] >> 1 : 0;
         }
         if (!wave_valid) {
 #pragma unroll
@@ -1384,22 +1448,6 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
 #pragma unroll
             for (int k = 0; k < 4; ++k) m[qb][k] = BIG;
 
-        const int8_t *tbase = A.sdesc + (int64_t)aoff * D;
-        const int32_t *tci = A.sct + aoff;
-        // global -> LDS directly; the XOR swizzle of the 16-byte slots is applied on the source side
-        typedef __attribute__((address_space(3))) void *lds_ptr;
-        auto stage_direct = [&](int ch, int buf) {
-#pragma unroll
-            for (int j = 0; j < PIECES; ++j) {
-                const int e = j * NT + tid, row = e >> 3, slot = (e & 7) ^ ((row >> 1) & 7);
-                const int8_t *gsrc = tbase + (int64_t)(ch * CHUNK + row) * D + slot * 16;
-                int8_t *ldst = lds_tile + buf * (CHUNK * D) + (j * NT + wave * 64) * 16;
-                __builtin_amdgcn_global_load_lds(gsrc, (lds_ptr)ldst, 16, 0, 0);
-            }
-            __builtin_amdgcn_global_load_lds(tci + ch * CHUNK + (tid & (CHUNK - 1)),
-                                             (lds_ptr)(lds_tb + buf * CHUNK + (wave & (CHUNK / 64 - 1)) * 64), 4, 0, 0);
-        };
-        auto wait_direct = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); };       // vmcnt(0)
         // per train row: the waves' group minima -> (L, U1, U2), stored by waves 0 and 1 through a buffer
         // resource over this workgroup's partials (an offset past num_records drops the store)
         const int mrow = (wave & 1) * 64 + lane;
@@ -1465,8 +1513,6 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
             nx_a = A.upairs[2 * un + 1];
             nx_rowp = A.rowp_off[un];
         }
-        stage_direct(0, 0);
-        stage_direct(nchunks > 1 ? 1 : 0, 1);
         wait_direct();
         __syncthreads();
 #pragma unroll
@@ -1507,17 +1553,12 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
         // row buffers (offsets in ints) of this chunk and of the previous one; "chunk -1" stores its
         // (meaningless) last tile into the buffer chunk 2 overwrites
         int rbo = 0, rbo_prev = 2 * NW * CHUNK;
-        // (the stage inside the chunk loop, as in form 2's: one lane offset for every piece and chunk beside a
-        //  scalar base, the wave's LDS destination from a scalar register, one held piece a step)
-        const int wave_u = uniform32(wave);
-        const unsigned stage_voff = (unsigned)((tid >> 3) * D + (((tid & 7) ^ ((tid >> 4) & 7)) * 16));
-        const unsigned lds_tile_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tile + wave_u * (64 * 16));
-        const unsigned lds_tb_at = (unsigned)(uintptr_t)(lds_ptr)(lds_tb + (wave_u & (CHUNK / 64 - 1)) * 64);
-        const unsigned ct_voff = (unsigned)((tid & (CHUNK - 1)) * 4);
+        // (the stage inside the chunk loop, as in form 2's: the same offsets, one held piece a step)
 #if defined(IAMX_T_STAMPS)
         const unsigned long long loop_c0 = __builtin_amdgcn_s_memtime(), loop_r0 = __builtin_amdgcn_s_memrealtime();
         __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0) alone
         if (stamp_c1) stamp_tail += loop_c0 - stamp_c1;
+        else stamp_start = loop_c0 - stamp_entry;
 #endif
         // a chunk.  STAGE: chunk + 2 of the pair exists and is staged; the pair's last two chunks stage nothing
         auto chunk = [&](int ch, auto stage_c) __attribute__((always_inline)) {
@@ -1658,6 +1699,7 @@ __global__ __launch_bounds__(256, 1) void knn2sym16_kernel(SymArgs A)
                 o[1] = stamp_chunks;
                 o[2] = stamp_cycles;
                 o[3] = stamp_ticks;
+                A.stamps[(size_t)gridDim.x * NW * 4 + (size_t)blockIdx.x * NW + wave] = stamp_start;
             }
         }
 #endif

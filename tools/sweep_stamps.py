@@ -14,7 +14,8 @@ with s_memtime and s_memrealtime: the in-kernel clock.  The 16x16x64 item kernel
 loop and its PAIR TAIL: the cycles from the end of a pair's chunk loop to the start of the item's next
 pair's (the last merge, the column epilogue, the barrier, the first two stages, the first operand reads).
 The tail's median is over every wave that ran chunks, waves past the end of the B image included (their tail
-has no column epilogue); the 4096-row store has none.
+has no column epilogue); the 4096-row store has none.  It also stamps its ITEM START: the cycles from the
+kernel's entry to the start of the first pair's chunk loop (a library from before that stamp leaves it at 0).
 
 Prints the median over waves of cycles per chunk and the share of the loop's cycles per chunk IN THE
 SAME BUILD.  Read the shares: a stamped build's fences forbid overlaps the shipped loop has, so its run
@@ -127,7 +128,8 @@ def startup_store():
 
 def measure(L, kernel, args, n_wg, seconds, pair_chunks=0):
     launch = {'items': L.iamx_knn2sym_sweep_items, 'items16': L.iamx_knn2sym_sweep_items16}.get(kernel, L.iamx_knn2sym_sweep)
-    buf = torch.zeros((n_wg, NW, 4), dtype=torch.int64, device='cuda')
+    # [workgroups][waves][4], and behind it the 16x16x64 kernel's [workgroups][waves] item starts
+    buf = torch.zeros(n_wg * NW * 5, dtype=torch.int64, device='cuda')
     L.iamx_knn2sym_set_stamps(buf.data_ptr())
     t_end = time.time() + seconds
     while time.time() < t_end:
@@ -135,8 +137,10 @@ def measure(L, kernel, args, n_wg, seconds, pair_chunks=0):
             rc = launch(*args, stream_ptr())
             assert rc == 0, rc
         torch.cuda.synchronize()
-    v = buf.cpu().numpy().reshape(-1, 4).astype(np.float64)
+    raw = buf.cpu().numpy().astype(np.float64)
     L.iamx_knn2sym_set_stamps(None)
+    v, start = raw[:n_wg * NW * 4].reshape(-1, 4), raw[n_wg * NW * 4:]
+    start = float(np.median(start[v[:, 1] > 0]))
     v = v[v[:, 1] > 0]
     seg = float(np.median(v[:, 0] / v[:, 1]))
     loop = float(np.median(v[:, 2] / v[:, 1]))
@@ -145,6 +149,7 @@ def measure(L, kernel, args, n_wg, seconds, pair_chunks=0):
         # the 16x16x64 kernel's segment sum is its pair tails: the pairs of a wave's item but the last have one
         tails = v[:, 1] / pair_chunks - 1
         seg = float(np.median(v[tails > 0, 0] / tails[tails > 0]))
+        return seg, loop, ghz, start
     return seg, loop, ghz
 
 
@@ -176,11 +181,11 @@ def main():
         for rep in range(3):
             for kernel in ('items', 'items16'):
                 pair_chunks = ss.ROWS // 128 if kernel == 'items16' else 0
-                tail, loop, ghz = measure(L, kernel, a, n_wg, args.seconds, pair_chunks)
+                tail, loop, ghz, *start = measure(L, kernel, a, n_wg, args.seconds, pair_chunks)
                 print('  %-8s chunk loop %7.0f cycles a chunk, in-kernel clock %.3f GHz, %.3f us a chunk'
                       % (kernel, loop, ghz, loop / ghz * 1e-3) +
-                      (', pair tail %.0f cycles (%.2f %% of a pair of %d chunks)'
-                       % (tail, 100.0 * tail / (tail + loop * pair_chunks), pair_chunks) if pair_chunks else ''))
+                      (', pair tail %.0f cycles (%.2f %% of a pair of %d chunks), item start %.0f cycles'
+                       % (tail, 100.0 * tail / (tail + loop * pair_chunks), pair_chunks, start[0]) if pair_chunks else ''))
         return
     stores = [('dense', ) + dense_store(), ('4096-row', ) + startup_store()]
     res = {}
