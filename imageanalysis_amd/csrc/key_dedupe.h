@@ -1,7 +1,7 @@
 // First-come-wins de-duplication of a match list on the "%.2f-%.2f" keys of either end point
 // (scripts/lib/matcher.py:157-182 filter_duplicates), with the order-preserving compaction and the
-// workgroup sum it is built from: shared by the select stages of the 'bestratio' and 'smart'
-// strategies (match_ratio.hip, match_smart.hip).  A workgroup of NT threads calls these, all threads together.
+// workgroup sum it is built from: what the select stages of the 'bestratio', 'smart' and 'bruteforce'
+// strategies take a list with (bin_select.h).  A workgroup of NT threads calls these, all threads together.
 #pragma once
 #include "iamx_common.h"
 

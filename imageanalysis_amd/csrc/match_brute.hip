@@ -23,21 +23,18 @@
 // No contraction anywhere in this file: every expression rounds as the Python it restates.  The
 // pragma below is this source's -ffp-contract=off (the build's table of per-file flags stays as it is).
 #include "iamx_common.h"
-#include "key_dedupe.h"
+#include "bin_select.h"
 
-// (It covers what follows it in THIS file.  The two headers above hold no floating-point arithmetic.)
+// (It covers what follows it in THIS file.  The headers above hold no floating-point arithmetic.)
 #pragma clang fp contract(off)
 
 namespace {
 
-using namespace iamx_kd;          // NT = 256, compact(), dedupe(), block_sum()
+using namespace iamx_bs;          // NT = 256, gate(), WorkSlice, take_list(), scan_and_pack()
 constexpr int ND = IAMX_BRUTE_DIST_BINS, NA = IAMX_BRUTE_ANGLE_BINS, NC = IAMX_BRUTE_CELLS;
-constexpr int MAX_ROWS = 1 << 24;
 constexpr int CHUNK = 2048;                // rows whose cell codes are held in LDS at a time
 constexpr int OWN = (NC + NT - 1) / NT;    // cells a thread of the fill kernel owns
 static_assert(ND == 41 && NA == 21 && NC == ND * NA, "41 distance bins x 21 angle bins");
-
-typedef int v2i __attribute__((ext_vector_type(2)));
 
 struct BinArgs {
     const int32_t *idx, *d2;           // [rows][3] iamx_knn3_l2_pairs
@@ -112,12 +109,6 @@ __device__ __forceinline__ bool in_angle(int ra, int ca)
     if (ra == 0) return ca == NA - 1 || ca == 0 || ca == 1;
     if (ra == NA - 1) return ca == NA - 2 || ca == NA - 1 || ca == 0;
     return ca >= ra - 1 && ca <= ra + 1;
-}
-
-// is a cell of `len` members looked at?  (matcher.py:797, and the four points a homography needs)
-__device__ __forceinline__ bool gate(int len, double min_pairs)
-{
-    return (double)len >= min_pairs && len >= 4;
 }
 
 struct PairCtx {
@@ -258,13 +249,10 @@ __global__ __launch_bounds__(NT) void brute_select_kernel(SelArgs A)
     __shared__ int fit[NA];
     const int p = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int32_t *w = A.work + (int64_t)p * (6 * (int64_t)A.stride + 2 * (int64_t)A.tab_size);
-    int32_t *cand = w, *slotq = w + 2 * (int64_t)A.stride, *slott = slotq + A.stride,
-            *cont = slott + A.stride, *keep = cont + A.stride, *tabq = keep + A.stride,
-            *tabt = tabq + A.tab_size;
+    const WorkSlice W(A.work, p, A.stride, A.tab_size);
+    const PairKeys K(A.key2, A.kp_off, A.pairs, p);
     int32_t *out = A.out_slots + (int64_t)p * A.stride * 2;
     int32_t *fc = A.fit_cnt + (int64_t)p * NC;
-    const int32_t *kq = A.key2 + 2 * A.kp_off[A.pairs[2 * p]], *kt = A.key2 + 2 * A.kp_off[A.pairs[2 * p + 1]];
     for (int k = threadIdx.x; k < NC; k += NT) fc[k] = -1;              // not looked at, or not reached
     int best = 0, chosen = -1, walked = 0, looked = 0;
     bool refused = false;
@@ -312,16 +300,9 @@ __global__ __launch_bounds__(NT) void brute_select_kernel(SelArgs A)
     if (!refused && chosen >= 0 && (double)best >= A.min_pairs) {
         const int64_t o = A.seg_off[(int64_t)p * NC + chosen];
         const int n = A.seg_cnt[(int64_t)p * NC + chosen];
-        const uint8_t *mk = A.mask + o;
-        const int32_t *rw = A.rows + 2 * o;
-        const int m = compact(red, n, [&](int i) { return mk[i] != 0; },
-                              [&](int pos, int i) { cand[2 * pos] = rw[2 * i]; cand[2 * pos + 1] = rw[2 * i + 1]; });
-        uniq = dedupe(red, kq, kt, cand, m, tabq, tabt, slotq, slott, cont, keep, A.tab_size);
-        if ((double)uniq >= A.min_pairs) {
-            cnt = uniq;
-            compact(red, m, [&](int i) { return keep[i] != 0; },
-                    [&](int pos, int i) { out[2 * pos] = cand[2 * i]; out[2 * pos + 1] = cand[2 * i + 1]; });
-        }
+        const auto enough = [&](int u) { return (double)u >= A.min_pairs; };
+        uniq = take_list(red, A.mask + o, A.rows + 2 * o, n, K, W, out, enough).y;
+        if (enough(uniq)) cnt = uniq;
     }
     if (threadIdx.x == 0) {
         A.out_cnt[p] = cnt;
@@ -332,20 +313,6 @@ __global__ __launch_bounds__(NT) void brute_select_kernel(SelArgs A)
         A.stats[4 * p + 3] = looked;
         if (refused) atomicAdd(A.flag + 1, 1);
     }
-}
-
-__global__ __launch_bounds__(NT) void brute_pack_kernel(const int32_t *__restrict__ cnt,
-                                                        const int64_t *__restrict__ off,
-                                                        const int32_t *__restrict__ slots, int stride,
-                                                        int64_t cap, int32_t *__restrict__ out_rows)
-{
-    const int p = blockIdx.x;
-    const int c = cnt[p];
-    const int64_t o = off[p];
-    if (c <= 0 || c > stride || o < 0 || o + c > cap) return;
-    const v2i *src = reinterpret_cast<const v2i *>(slots) + (int64_t)p * stride;
-    v2i *dst = reinterpret_cast<v2i *>(out_rows) + o;
-    for (int i = threadIdx.x; i < c; i += NT) dst[i] = src[i];
 }
 
 }  // namespace
@@ -392,20 +359,14 @@ extern "C" int iamx_brute_select(const int32_t *pairs, const int64_t *kp_off, co
                  "null pointer");
     IAMX_REQUIRE(n_pairs >= 0 && cap >= 0 && out_cap >= 0, "negative count");
     IAMX_REQUIRE((int64_t)n_pairs * NC < (1ll << 31), "too many segments");
-    IAMX_REQUIRE(stride >= 1 && stride <= MAX_ROWS, "stride outside 1..2^24");
-    IAMX_REQUIRE(tab_size >= 64 && (tab_size & (tab_size - 1)) == 0 && (int64_t)tab_size >= 2 * (int64_t)stride,
-                 "tab_size must be a power of two >= max(64, 2 * stride)");
+    IAMX_REQUIRE_WORK_SLICE(stride, tab_size);
     if (n_pairs == 0) return IAMX_OK;                       // (nothing is written, out_off[0] included)
     hipStream_t st = iamx::as_stream(stream);
     SelArgs A{pairs, kp_off, key2, min_pairs, seg_cnt, seg_off, rows, mask, vstatus, cap, stride,
               tab_size, work, out_slots, out_cnt, chosen, stats, fit_cnt, flag};
     hipLaunchKernelGGL(brute_select_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
-    int rc = iamx::check_launch("iamx_brute_select");
+    const int rc = iamx::check_launch("iamx_brute_select");
     if (rc != IAMX_OK) return rc;
-    rc = iamx_exclusive_scan_i32(out_cnt, n_pairs, out_off, stream);
-    if (rc != IAMX_OK) return rc;
-    hipLaunchKernelGGL(brute_pack_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st,
-                       (const int32_t *)out_cnt, (const int64_t *)out_off, (const int32_t *)out_slots,
-                       stride, out_cap, out_rows);
-    return iamx::check_launch("iamx_brute_select");
+    return scan_and_pack("iamx_brute_select", n_pairs, out_cnt, out_off, out_slots, stride, out_rows,
+                         out_cap, stream);
 }

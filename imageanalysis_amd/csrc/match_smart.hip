@@ -22,21 +22,18 @@
 // No contraction anywhere in this file: every expression rounds as the Python it restates.  The
 // pragma below is this source's -ffp-contract=off (the build's table of per-file flags stays as it is).
 #include "iamx_common.h"
-#include "key_dedupe.h"
+#include "bin_select.h"
 
-// (It covers what follows it in THIS file.  The two headers above hold no floating-point arithmetic;
+// (It covers what follows it in THIS file.  The headers above hold no floating-point arithmetic;
 //  any that is ever added to them, or to a header included from here on, needs a pragma of its own.)
 #pragma clang fp contract(off)
 
 namespace {
 
-using namespace iamx_kd;          // NT = 256, compact(), dedupe(), block_sum()
+using namespace iamx_bs;          // NT = 256, gate(), the bin kernels, walk_bins(), scan_and_pack()
 constexpr int NB = IAMX_SMART_BINS;
-constexpr int MAX_ROWS = 1 << 24;
 constexpr int SWEEPS = 12;                 // cyclic Jacobi sweeps of the 9 x 9 eigenproblem
 static_assert(NB == 7, "the bins are best_dist < 32 * 2^b, b = 0 .. 6");
-
-typedef int v2i __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ double nan_d() { return __longlong_as_double(0x7FF8000000000000LL); }
 
@@ -282,134 +279,38 @@ __device__ __forceinline__ unsigned choose(const int32_t *__restrict__ nn, const
     return m | 0x80000000u;                // bit 31: the row has a survivor (it may be in no bin)
 }
 
-// is a bin of `len` members looked at?  (matcher.py:529, and the four points a homography needs)
-__device__ __forceinline__ bool gate(int len, double min_pairs)
-{
-    return (double)len >= min_pairs && len >= 4;
-}
-
-struct PairCtx {
+// the row rule of bin_select.h's bin kernels; a pair that is not active has no rows
+struct SmartRule {
+    typedef StatArgs Args;
+    static __device__ __forceinline__ int n_bins(const StatArgs &) { return NB; }
+    const StatArgs &A;
     int64_t b0;
     int n;
-    bool live, oversize;
+    bool oversize;
     const float *xq, *xt, *sq, *st;
     Hm H;
+    __device__ __forceinline__ SmartRule(const StatArgs &A_, int p) : A(A_)
+    {
+        b0 = A.row_off[p];
+        const int64_t n64 = A.row_off[p + 1] - b0;
+        const bool live = A.active == nullptr || A.active[p] != 0;
+        oversize = live && (n64 < 0 || n64 > MAX_ROWS);
+        n = !live || oversize ? 0 : (int)n64;
+        const int64_t oq = A.kp_off[A.pairs[2 * p]], ot = A.kp_off[A.pairs[2 * p + 1]];
+        xq = A.xy + 2 * oq; xt = A.xy + 2 * ot;
+        sq = A.size + oq; st = A.size + ot;
+#pragma unroll
+        for (int j = 0; j < 9; ++j) H.m[j] = A.H[9 * (int64_t)p + j];
+    }
+    __device__ __forceinline__ unsigned bins(int i, bool &zero, int &t) const
+    {
+        return choose(A.idx + 3 * (b0 + i), A.d2 + 3 * (b0 + i), i, xq, xt, sq, st, H, A.match_ratio, t, zero);
+    }
+    __device__ __forceinline__ float4 point(int i, int &t) const
+    {
+        return make_float4(xq[2 * i], xq[2 * i + 1], xt[2 * t], xt[2 * t + 1]);
+    }
 };
-
-__device__ __forceinline__ PairCtx pair_ctx(const StatArgs &A, int p)
-{
-    PairCtx c;
-    c.b0 = A.row_off[p];
-    const int64_t n64 = A.row_off[p + 1] - c.b0;
-    c.live = A.active == nullptr || A.active[p] != 0;
-    c.oversize = c.live && (n64 < 0 || n64 > MAX_ROWS);
-    c.n = !c.live || c.oversize ? 0 : (int)n64;
-    const int64_t oq = A.kp_off[A.pairs[2 * p]], ot = A.kp_off[A.pairs[2 * p + 1]];
-    c.xq = A.xy + 2 * oq; c.xt = A.xy + 2 * ot;
-    c.sq = A.size + oq; c.st = A.size + ot;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) c.H.m[j] = A.H[9 * (int64_t)p + j];
-    return c;
-}
-
-__global__ __launch_bounds__(NT) void smart_count_kernel(StatArgs A)
-{
-    __shared__ int wsum[NT / 64][NB];
-    const int p = blockIdx.x;
-    const PairCtx c = pair_ctx(A, p);
-    int cnt[NB], zd = 0;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) cnt[b] = 0;
-    for (int i = threadIdx.x; i < c.n; i += NT) {
-        bool zero;
-        int t;
-        const unsigned m = choose(A.idx + 3 * (c.b0 + i), A.d2 + 3 * (c.b0 + i), i, c.xq, c.xt, c.sq, c.st,
-                                  c.H, A.match_ratio, t, zero);
-        zd += zero ? 1 : 0;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) cnt[b] += (m >> b) & 1;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        zd += __shfl_xor(zd, s);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) cnt[b] += __shfl_xor(cnt[b], s);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) wsum[threadIdx.x >> 6][b] = cnt[b];
-        if (zd) atomicAdd(A.flag, zd);
-    }
-    if (threadIdx.x == 0 && c.oversize) atomicAdd(A.flag + 1, 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // a bin with as many members as the last bin that was looked at IS that bin (the bins are
-        // nested): its consensus would be the same and cannot win under `>`, so it gets no segment
-        int prev = -1;
-        for (int b = 0; b < NB; ++b) {
-            const int m = wsum[0][b] + wsum[1][b] + wsum[2][b] + wsum[3][b];
-            A.bin_cnt[p * NB + b] = m;
-            const bool g = gate(m, A.min_pairs);
-            A.seg_cnt[p * NB + b] = g && m != prev ? m : 0;
-            if (g) prev = m;
-        }
-    }
-}
-
-__global__ __launch_bounds__(NT) void smart_fill_kernel(StatArgs A)
-{
-    __shared__ int wcnt[NT / 64][NB];
-    const int p = blockIdx.x;
-    unsigned on = 0;
-    int base[NB];
-    int64_t first[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        base[b] = 0;
-        first[b] = 0;
-        if (A.seg_cnt[p * NB + b] > 0) {
-            on |= 1u << b;
-            first[b] = A.seg_off[p * NB + b];
-        }
-    }
-    if (!on) return;
-    const PairCtx c = pair_ctx(A, p);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int s = 0; s < c.n; s += NT) {
-        const int i = s + threadIdx.x;
-        unsigned m = 0;
-        int t = -1;
-        if (i < c.n) {
-            bool zero;
-            m = choose(A.idx + 3 * (c.b0 + i), A.d2 + 3 * (c.b0 + i), i, c.xq, c.xt, c.sq, c.st, c.H,
-                       A.match_ratio, t, zero) & on;
-        }
-        int pre[NB];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const unsigned long long bal = __ballot((m >> b) & 1);
-            pre[b] = __popcll(bal & ((1ull << lane) - 1));
-            if (lane == 0) wcnt[wave][b] = __popcll(bal);
-        }
-        __syncthreads();
-        if (m) {
-            const float x1 = c.xq[2 * i], y1 = c.xq[2 * i + 1], x2 = c.xt[2 * t], y2 = c.xt[2 * t + 1];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if (!((m >> b) & 1)) continue;
-                int pos = base[b] + pre[b];
-                for (int w = 0; w < wave; ++w) pos += wcnt[w][b];
-                const int64_t o = first[b] + pos;
-                if (o < 0 || o >= A.cap) continue;          // (never: cap >= NB * rows)
-                *reinterpret_cast<float4 *>(A.pts + 4 * o) = make_float4(x1, y1, x2, y2);
-                *reinterpret_cast<v2i *>(A.rows + 2 * o) = v2i{i, t};
-            }
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) base[b] += wcnt[0][b] + wcnt[1][b] + wcnt[2][b] + wcnt[3][b];
-        __syncthreads();
-    }
-}
 
 // ---------------------------------------------------------------------------------
 // the walk over a pass' bins
@@ -420,13 +321,8 @@ struct SelArgs {
     const int32_t *key2;               // [total kp][2] round-half-even(100 * kp.pt) ("%.2f")
     const int32_t *active;             // [n_pairs] or null
     double min_pairs;
-    const int32_t *bin_cnt, *seg_cnt;  // [n_pairs][NB]
-    const int64_t *seg_off;            // [n_pairs * NB + 1]
-    const int32_t *rows;               // [cap][2]
-    const uint8_t *mask;               // [cap] iamx_verify_pairs
-    const int32_t *vstatus;            // [n_pairs * NB]
-    int64_t cap;
-    int stride, tab_size;
+    Segments S;
+    int tab_size;
     int32_t *work;                     // [n_pairs][6 * stride + 2 * tab_size]
     int32_t *best;                     // [n_pairs][2] unique, fitted of the pair's list (read and written)
     int32_t *improved;                 // [n_pairs] 0, or 1 + the bin that was taken last
@@ -435,6 +331,7 @@ struct SelArgs {
     int32_t *flag;
 };
 
+// matcher.py:542-555: the walk starts at the pair's running best
 __global__ __launch_bounds__(NT) void smart_select_kernel(SelArgs A)
 {
     __shared__ int red[NT / 64];
@@ -443,74 +340,21 @@ __global__ __launch_bounds__(NT) void smart_select_kernel(SelArgs A)
         if (threadIdx.x == 0) A.improved[p] = 0;
         return;
     }
-    int32_t *w = A.work + (int64_t)p * (6 * (int64_t)A.stride + 2 * (int64_t)A.tab_size);
-    int32_t *cand = w, *slotq = w + 2 * (int64_t)A.stride, *slott = slotq + A.stride,
-            *cont = slott + A.stride, *keep = cont + A.stride, *tabq = keep + A.stride,
-            *tabt = tabq + A.tab_size;
-    int32_t *out = A.out_slots + (int64_t)p * A.stride * 2;
-    int32_t *stat = A.stats + (int64_t)p * NB * 3;
-    const int32_t *kq = A.key2 + 2 * A.kp_off[A.pairs[2 * p]], *kt = A.key2 + 2 * A.kp_off[A.pairs[2 * p + 1]];
-    int best = A.best[2 * p], best_fit = A.best[2 * p + 1], taken = 0, prev_fit = -1, prev_uniq = -1;
-    bool refused = false;
-    for (int b = 0; b < NB; ++b) {
-        const int seg = p * NB + b, len = A.bin_cnt[seg];
-        int fit = -1, uniq = -1;
-        if (gate(len, A.min_pairs)) {
-            const int n = A.seg_cnt[seg];
-            const int64_t o = A.seg_off[seg];
-            if (n == 0) {                               // the same set as the bin before it
-                fit = prev_fit;
-                uniq = prev_uniq;
-            } else if (n > A.stride || o < 0 || o + n > A.cap) {
-                refused = true;                         // (never: the caller sizes stride and cap)
-            } else {
-                const uint8_t *mk = A.mask + o;
-                const int32_t *rw = A.rows + 2 * o;
-                // a bin without a model (IAMX_VERIFY_NO_MODEL) has no inliers
-                fit = A.vstatus[seg] != IAMX_VERIFY_OK ? 0 :
-                    compact(red, n, [&](int i) { return mk[i] != 0; },
-                            [&](int pos, int i) { cand[2 * pos] = rw[2 * i]; cand[2 * pos + 1] = rw[2 * i + 1]; });
-                uniq = dedupe(red, kq, kt, cand, fit, tabq, tabt, slotq, slott, cont, keep, A.tab_size);
-                if (uniq > best) {                      // strictly more (matcher.py:542)
-                    best = uniq;
-                    best_fit = fit;
-                    taken = b + 1;
-                    compact(red, fit, [&](int i) { return keep[i] != 0; },
-                            [&](int pos, int i) { out[2 * pos] = cand[2 * i]; out[2 * pos + 1] = cand[2 * i + 1]; });
-                }
-                prev_fit = fit;
-                prev_uniq = uniq;
-            }
-        }
-        if (threadIdx.x == 0) { stat[3 * b] = len; stat[3 * b + 1] = fit; stat[3 * b + 2] = uniq; }
-    }
+    const Walked w = walk_bins(red, A.S, p, NB, A.min_pairs, PairKeys(A.key2, A.kp_off, A.pairs, p),
+                               WorkSlice(A.work, p, A.S.stride, A.tab_size),
+                               A.out_slots + (int64_t)p * A.S.stride * 2, A.stats + (int64_t)p * NB * 3,
+                               A.best[2 * p], A.best[2 * p + 1]);
     if (threadIdx.x == 0) {
-        if (refused) {
-            atomicAdd(A.flag + 1, 1);
-            taken = 0;
-        }
+        if (w.refused) atomicAdd(A.flag + 1, 1);
+        const int taken = w.refused ? 0 : w.taken;
         A.improved[p] = taken;
         if (taken) {
             // matcher.py:582-593: the fitted list, then the de-duplicated one, against min_pairs
-            A.best[2 * p] = best;
-            A.best[2 * p + 1] = best_fit;
-            A.out_cnt[p] = (double)best_fit >= A.min_pairs && (double)best >= A.min_pairs ? best : 0;
+            A.best[2 * p] = w.best;
+            A.best[2 * p + 1] = w.best_fit;
+            A.out_cnt[p] = (double)w.best_fit >= A.min_pairs && (double)w.best >= A.min_pairs ? w.best : 0;
         }
     }
-}
-
-__global__ __launch_bounds__(NT) void smart_pack_kernel(const int32_t *__restrict__ cnt,
-                                                        const int64_t *__restrict__ off,
-                                                        const int32_t *__restrict__ slots, int stride,
-                                                        int64_t cap, int32_t *__restrict__ out_rows)
-{
-    const int p = blockIdx.x;
-    const int c = cnt[p];
-    const int64_t o = off[p];
-    if (c <= 0 || c > stride || o < 0 || o + c > cap) return;
-    const v2i *src = reinterpret_cast<const v2i *>(slots) + (int64_t)p * stride;
-    v2i *dst = reinterpret_cast<v2i *>(out_rows) + o;
-    for (int i = threadIdx.x; i < c; i += NT) dst[i] = src[i];
 }
 
 }  // namespace
@@ -545,12 +389,12 @@ extern "C" int iamx_smart_stats(const int32_t *idx, const int32_t *d2, const int
     hipStream_t st = iamx::as_stream(stream);
     StatArgs A{idx, d2, row_off, pairs, kp_off, xy, size, H, active, match_ratio, min_pairs, cap,
                bin_cnt, seg_cnt, seg_off, pts, rows, flag};
-    hipLaunchKernelGGL(smart_count_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
+    hipLaunchKernelGGL((bin_count_kernel<NB, SmartRule>), dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
     int rc = iamx::check_launch("iamx_smart_stats");
     if (rc != IAMX_OK) return rc;
     rc = iamx_exclusive_scan_i32(seg_cnt, (int64_t)n_pairs * NB, seg_off, stream);
     if (rc != IAMX_OK) return rc;
-    hipLaunchKernelGGL(smart_fill_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
+    hipLaunchKernelGGL((bin_fill_kernel<NB, SmartRule>), dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
     return iamx::check_launch("iamx_smart_stats");
 }
 
@@ -570,14 +414,13 @@ extern "C" int iamx_smart_select(const int32_t *pairs, const int64_t *kp_off, co
                  "null pointer");
     IAMX_REQUIRE(n_pairs >= 0 && cap >= 0 && out_cap >= 0, "negative count");
     IAMX_REQUIRE((int64_t)n_pairs * NB < (1ll << 31), "too many segments");
-    IAMX_REQUIRE(stride >= 1 && stride <= MAX_ROWS, "stride outside 1..2^24");
-    IAMX_REQUIRE(tab_size >= 64 && (tab_size & (tab_size - 1)) == 0 && (int64_t)tab_size >= 2 * (int64_t)stride,
-                 "tab_size must be a power of two >= max(64, 2 * stride)");
+    IAMX_REQUIRE_WORK_SLICE(stride, tab_size);
     IAMX_REQUIRE(((uintptr_t)pts & 15) == 0, "pts must be 16-byte aligned");
     hipStream_t st = iamx::as_stream(stream);
     if (n_pairs) {
-        SelArgs A{pairs, kp_off, key2, active, min_pairs, bin_cnt, seg_cnt, seg_off, rows, mask, vstatus,
-                  cap, stride, tab_size, work, best, improved, out_slots, out_cnt, stats, flag};
+        SelArgs A{pairs, kp_off, key2, active, min_pairs,
+                  {bin_cnt, seg_cnt, seg_off, rows, mask, vstatus, cap, stride},
+                  tab_size, work, best, improved, out_slots, out_cnt, stats, flag};
         hipLaunchKernelGGL(smart_select_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st, A);
         int rc = iamx::check_launch("iamx_smart_select");
         if (rc != IAMX_OK) return rc;
@@ -587,11 +430,6 @@ extern "C" int iamx_smart_select(const int32_t *pairs, const int64_t *kp_off, co
         rc = iamx::check_launch("iamx_smart_select");
         if (rc != IAMX_OK) return rc;
     }
-    const int rc = iamx_exclusive_scan_i32(out_cnt, n_pairs, out_off, stream);
-    if (rc != IAMX_OK) return rc;
-    if (n_pairs)
-        hipLaunchKernelGGL(smart_pack_kernel, dim3((unsigned)n_pairs), dim3(NT), 0, st,
-                           (const int32_t *)out_cnt, (const int64_t *)out_off,
-                           (const int32_t *)out_slots, stride, out_cap, out_rows);
-    return iamx::check_launch("iamx_smart_select");
+    return scan_and_pack("iamx_smart_select", n_pairs, out_cnt, out_off, out_slots, stride, out_rows,
+                         out_cap, stream);
 }

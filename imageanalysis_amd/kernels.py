@@ -729,6 +729,113 @@ def five_point(rays):
 
 
 # --------------------------------------------------------------------------------------
+# what the 'bestratio', 'smart' and 'bruteforce' strategies share (csrc/bin_select.h): a search, the
+# rows of every pair in bins materialised as segments, verify_pairs over the segments, the select stage
+# --------------------------------------------------------------------------------------
+class _StrategyResult(object):
+    """keyword constructor over a result class' __slots__ (a field not given is None)"""
+    __slots__ = ()
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _tab_size(stride):
+    """entries of a key table of the select stage: a power of two >= max(64, 2 * stride)"""
+    t = 64
+    while t < 2 * stride:
+        t *= 2
+    return t
+
+
+def _live_pairs(store, pairs):
+    """-> (pairs int32 [P, 2], nq int64 [P] the rows of every query image, live: the pairs whose two
+    images both have at least 2 rows -- the others end with nothing, raw_matches' guards)"""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    counts = np.asarray(store.counts, np.int64)
+    nq = counts[pairs[:, 0]] if len(pairs) else np.zeros(0, np.int64)
+    ok = (nq >= 2) & (counts[pairs[:, 1]] >= 2) if len(pairs) else np.zeros(0, bool)
+    return pairs, nq, np.nonzero(ok)[0]
+
+
+def _split_by_bytes(live, nq, bytes_of, batch_bytes):
+    """`live` cut into launches of at most batch_bytes each, at least one pair (a launch's stride is
+    its largest query image: bytes_of takes the launch's query rows)"""
+    chunks, a = [], 0
+    while a < len(live):
+        b = a + 1
+        while b < len(live) and bytes_of(nq[live[a:b + 1]]) <= batch_bytes:
+            b += 1
+        chunks.append(live[a:b])
+        a = b
+    return chunks
+
+
+def _bin_tables(P, nb, cap, dev):
+    """-> bin_cnt, seg_cnt int32 [P, nb], seg_off int64 [P * nb + 1] (zeros), pts f32 [cap, 4], rows
+    int32 [cap, 2] of the segments (at least one entry: an empty tensor has no address to pass)"""
+    return (torch.zeros((P, nb), dtype=I32, device=dev), torch.zeros((P, nb), dtype=I32, device=dev),
+            torch.zeros(P * nb + 1, dtype=I64, device=dev),
+            torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev),
+            torch.empty((max(cap, 1), 2), dtype=I32, device=dev))
+
+
+def _select_buffers(P, stride, total, dev):
+    """-> tab_size, work int32 [P * (6 * stride + 2 * tab_size)], slots int32 [P, stride, 2], cnt int32
+    [P], off int64 [P + 1] (zeros), out_rows int32 [total, 2] of a select stage"""
+    tab = _tab_size(stride)
+    return (tab, torch.empty(P * (6 * stride + 2 * tab), dtype=I32, device=dev),
+            torch.empty((P, stride, 2), dtype=I32, device=dev), torch.zeros(P, dtype=I32, device=dev),
+            torch.zeros(P + 1, dtype=I64, device=dev), torch.empty((max(total, 1), 2), dtype=I32, device=dev))
+
+
+class _Launch(object):
+    """the tensors of one launch chain, by name"""
+
+
+def _launch_chain(cls, store, pairs, knn, nb, per_row, tol, hypotheses, seed, flag, bins, select):
+    """one launch chain over pairs whose images all have at least 2 rows: the search knn(store, pairs),
+    bins(b) -- at most per_row segment entries a query row over nb segments a pair --, the consensus of
+    every segment (iamx_verify_pairs on its points), select(b) -> the extra fields of cls"""
+    dev = require_gpu()
+    b = _Launch()
+    b.P, b.flag = len(pairs), flag
+    b.idx, b.d2, out_off = knn(store, pairs)
+    b.total = int(out_off[-1])
+    b.stride = max(int(np.diff(out_off).max()), 1)
+    b.cap = per_row * b.total
+    b.pairs = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev)
+    b.row_off = torch.from_numpy(out_off).to(dev)
+    b.bin_cnt, b.seg_cnt, b.seg_off, b.pts, b.rows = _bin_tables(b.P, nb, b.cap, dev)
+    bins(b)
+    b.mask, _model, _best, b.vstatus = verify_pairs(b.pts[:b.cap], b.seg_off, 'homography', float(tol),
+                                                    hypotheses=hypotheses, seed=seed)
+    b.tab, b.work, b.slots, b.cnt, b.off, b.out_rows = _select_buffers(b.P, b.stride, b.total, dev)
+    return cls(rows=b.out_rows, off=b.off, cnt=b.cnt, flag=flag, slots=b.slots, stride=b.stride, **select(b))
+
+
+def _merge_launches(cls, P, chunks, parts, flag, fields):
+    """several launches' results side by side over all P pairs (copies and one scan, no arithmetic of
+    their own).  fields: per extra field of cls its shape behind P and what a pair without a launch
+    holds, a number or one per entry of the last axis; cnt is 0 there.  No slots: they are a launch's."""
+    dev = flag.device
+    out = dict(cnt=torch.zeros(P, dtype=I32, device=dev))
+    for k, (shape, fill) in fields.items():
+        out[k] = torch.tensor(fill, dtype=I32, device=dev).expand((P,) + shape).contiguous()
+    rows = []
+    for c, r in zip(chunks, parts):
+        where = torch.from_numpy(c).to(dev)
+        for k in out:
+            out[k][where] = getattr(r, k)
+        rows.append(r.rows[:int(r.off[-1])])
+    off = exclusive_scan(out['cnt']) if P else torch.zeros(1, dtype=I64, device=dev)
+    rows = torch.cat(rows) if rows else torch.empty((0, 2), dtype=I32, device=dev)
+    return cls(rows=rows, off=off, flag=flag, slots=None, stride=parts[0].stride if len(parts) == 1 else None,
+               **out)
+
+
+# --------------------------------------------------------------------------------------
 # the 'bestratio' strategy (csrc/match_ratio.hip): ratio bins -> RANSAC homography per bin -> select
 # --------------------------------------------------------------------------------------
 RATIO_CUTOFFS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85)       # matcher.py:622
@@ -736,7 +843,7 @@ RATIO_MIN_UNIQUE = 20                                              # matcher.py:
 RATIO_BATCH_BYTES = 4 << 30
 
 
-class RatioResult(object):
+class RatioResult(_StrategyResult):
     """what ratio_pairs() returns, device tensors over its n pairs: rows int32 [total, 2] (query
     row, train row) packed back to back, off int64 [n + 1], cnt int32 [n], chosen int32 [n] (-1:
     no bin taken), stats int32 [n, n_bins, 3] = members, fit, unique (-1 where a bin is not looked
@@ -744,17 +851,6 @@ class RatioResult(object):
     2]: the same lists in fixed slots (iamx_similarity_pairs' layout) when the call was one launch,
     else None."""
     __slots__ = ('rows', 'off', 'cnt', 'chosen', 'stats', 'flag', 'slots', 'stride')
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
-
-
-def _ratio_tab_size(stride):
-    t = 64
-    while t < 2 * stride:
-        t *= 2
-    return t
 
 
 def ratio_bytes(nq, n_bins=len(RATIO_CUTOFFS)):
@@ -766,46 +862,31 @@ def ratio_bytes(nq, n_bins=len(RATIO_CUTOFFS)):
     if not len(nq):
         return 0
     stride = max(int(nq.max()), 1)
-    return int(nq.sum()) * (24 + 25 * n_bins) + len(nq) * (32 * stride + 8 * _ratio_tab_size(stride) + 64 * n_bins)
+    return int(nq.sum()) * (24 + 25 * n_bins) + len(nq) * (32 * stride + 8 * _tab_size(stride) + 64 * n_bins)
 
 
 def _ratio_launch(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed, cut, flag):
-    """one launch chain over pairs whose images all have at least 2 rows"""
-    dev = require_gpu()
     L = lib()
-    nb, P = len(cut), len(pairs)
-    idx, d2, out_off = knn2_pairs(store, pairs)
-    total = int(out_off[-1])
-    nq = np.diff(out_off)
-    stride = max(int(nq.max()), 1)
-    tab = _ratio_tab_size(stride)
-    cap = nb * total
-    d_pairs = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev)
-    row_off = torch.from_numpy(out_off).to(dev)
-    z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
-    bin_cnt, seg_cnt = z32(P, nb), z32(P, nb)
-    seg_off = torch.zeros(P * nb + 1, dtype=I64, device=dev)
-    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
-    check(L.iamx_ratio_bins(_ptr(idx), _ptr(d2), _ptr(row_off), _ptr(d_pairs), _ptr(kp_off), _ptr(xy),
-                            P, nb, _lib.c_void_p(cut.ctypes.data), float(min_pairs), cap,
-                            _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts), _ptr(rows),
-                            _ptr(flag), stream_ptr()), 'iamx_ratio_bins')
-    # bin b's consensus is iamx_verify_pairs on that bin's points as one segment
-    mask, _model, _best, vstatus = verify_pairs(pts[:cap], seg_off, 'homography',
-                                                float(tol), hypotheses=hypotheses, seed=seed)
-    work = torch.empty(P * (6 * stride + 2 * tab), dtype=I32, device=dev)
-    slots = torch.empty((P, stride, 2), dtype=I32, device=dev)
-    cnt, chosen, stats = z32(P), z32(P), z32(P, nb, 3)
-    off = torch.zeros(P + 1, dtype=I64, device=dev)
-    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
-    check(L.iamx_ratio_select(_ptr(d_pairs), _ptr(kp_off), _ptr(key2), P, nb, float(min_pairs),
-                              RATIO_MIN_UNIQUE, _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(rows),
-                              _ptr(mask), _ptr(vstatus), cap, stride, tab, _ptr(work), _ptr(slots),
-                              _ptr(cnt), _ptr(off), _ptr(out_rows), total, _ptr(chosen), _ptr(stats),
-                              _ptr(flag), stream_ptr()), 'iamx_ratio_select')
-    return RatioResult(rows=out_rows, off=off, cnt=cnt, chosen=chosen, stats=stats, flag=flag,
-                       slots=slots, stride=stride)
+    nb = len(cut)
+
+    def bins(b):
+        check(L.iamx_ratio_bins(_ptr(b.idx), _ptr(b.d2), _ptr(b.row_off), _ptr(b.pairs), _ptr(kp_off), _ptr(xy),
+                                b.P, nb, _lib.c_void_p(cut.ctypes.data), float(min_pairs), b.cap,
+                                _ptr(b.bin_cnt), _ptr(b.seg_cnt), _ptr(b.seg_off), _ptr(b.pts), _ptr(b.rows),
+                                _ptr(flag), stream_ptr()), 'iamx_ratio_bins')
+
+    def select(b):
+        chosen = torch.zeros(b.P, dtype=I32, device=flag.device)
+        stats = torch.zeros((b.P, nb, 3), dtype=I32, device=flag.device)
+        check(L.iamx_ratio_select(_ptr(b.pairs), _ptr(kp_off), _ptr(key2), b.P, nb, float(min_pairs),
+                                  RATIO_MIN_UNIQUE, _ptr(b.bin_cnt), _ptr(b.seg_cnt), _ptr(b.seg_off),
+                                  _ptr(b.rows), _ptr(b.mask), _ptr(b.vstatus), b.cap, b.stride, b.tab,
+                                  _ptr(b.work), _ptr(b.slots), _ptr(b.cnt), _ptr(b.off), _ptr(b.out_rows),
+                                  b.total, _ptr(chosen), _ptr(stats), _ptr(flag), stream_ptr()),
+              'iamx_ratio_select')
+        return dict(chosen=chosen, stats=stats)
+
+    return _launch_chain(RatioResult, store, pairs, knn2_pairs, nb, nb, tol, hypotheses, seed, flag, bins, select)
 
 
 def ratio_pairs(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed,
@@ -822,40 +903,15 @@ def ratio_pairs(store, pairs, kp_off, xy, key2, tol, min_pairs, hypotheses, seed
     nb = len(cut)
     if not 1 <= nb <= 8:
         raise ValueError("ratio_pairs: 1 to 8 cutoffs")
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    P = len(pairs)
-    counts = np.asarray(store.counts, np.int64)
-    nq = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
-    ok = (nq >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
-    live = np.nonzero(ok)[0]
-    # launches of at most batch_bytes (a launch's stride is its largest query image)
-    chunks, a = [], 0
-    while a < len(live):
-        b = a + 1
-        while b < len(live) and ratio_bytes(nq[live[a:b + 1]], nb) <= batch_bytes:
-            b += 1
-        chunks.append(live[a:b])
-        a = b
+    pairs, nq, live = _live_pairs(store, pairs)
+    chunks = _split_by_bytes(live, nq, lambda q: ratio_bytes(q, nb), batch_bytes)
     flag = torch.zeros(2, dtype=I32, device=dev)            # (the launches only ever raise it)
     parts = [_ratio_launch(store, pairs[c], kp_off, xy, key2, tol, min_pairs, hypotheses, seed, cut, flag)
              for c in chunks]
-    if len(parts) == 1 and len(live) == P:
+    if len(parts) == 1 and len(live) == len(pairs):
         return parts[0]
-    # the launches' results side by side (copies and one scan, no arithmetic of their own)
-    cnt = torch.zeros(P, dtype=I32, device=dev)
-    chosen = torch.full((P,), -1, dtype=I32, device=dev)
-    stats = torch.full((P, nb, 3), -1, dtype=I32, device=dev)
-    stats[:, :, 0] = 0
-    rows = []
-    for c, r in zip(chunks, parts):
-        where = torch.from_numpy(c).to(dev)
-        cnt[where], chosen[where], stats[where] = r.cnt, r.chosen, r.stats
-        rows.append(r.rows[:int(r.off[-1])])
-    off = exclusive_scan(cnt) if P else torch.zeros(1, dtype=I64, device=dev)
-    rows = torch.cat(rows) if rows else torch.empty((0, 2), dtype=I32, device=dev)
-    one = len(parts) == 1
-    return RatioResult(rows=rows, off=off, cnt=cnt, chosen=chosen, stats=stats, flag=flag,
-                       slots=None, stride=parts[0].stride if one else None)
+    return _merge_launches(RatioResult, len(pairs), chunks, parts, flag,
+                           dict(chosen=((), -1), stats=((nb, 3), (0, -1, -1))))
 
 
 # --------------------------------------------------------------------------------------
@@ -894,7 +950,7 @@ def homography_fit(pts, seg_off, mask=None):
     return H[:n], status[:n]
 
 
-class SmartResult(object):
+class SmartResult(_StrategyResult):
     """what smart_pairs() returns over its n pairs: rows int32 [total, 2] (query row, train row)
     packed back to back, off int64 [n + 1], cnt int32 [n] (device tensors: the lists after the
     min_pairs gates and filter_duplicates); H f64 [n, 3, 3] the last prediction of every pair (device);
@@ -905,10 +961,6 @@ class SmartResult(object):
     (host) = unique, fitted of the final lists before the gates; flag int32 [2] (host): rows with a
     zero nearest distance, pairs refused."""
     __slots__ = ('rows', 'off', 'cnt', 'H', 'passes', 'stats', 'taken', 'best', 'flag')
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def smart_pairs(store, pairs, kp_off, xy, size, key2, H0, tol, min_pairs, match_ratio, hypotheses=2048,
@@ -925,18 +977,13 @@ def smart_pairs(store, pairs, kp_off, xy, size, key2, H0, tol, min_pairs, match_
     dev = require_gpu()
     L = lib()
     NB = len(SMART_CUTOFFS)
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    P = len(pairs)
-    counts = np.asarray(store.counts, np.int64)
+    pairs, _nq, live = _live_pairs(store, pairs)
+    P, n = len(pairs), len(live)
     H0 = np.ascontiguousarray(np.asarray(H0, np.float64).reshape(-1, 9))
     if len(H0) != P:
         raise ValueError("smart_pairs: one predicted homography per pair")
-    nq_all = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
-    ok = (nq_all >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
-    if knn is not None and not ok.all():
+    if knn is not None and n != P:
         raise ValueError("smart_pairs: a search handed in covers pairs of images with at least 2 rows only")
-    live = np.nonzero(ok)[0]
-    n = len(live)
     passes = np.zeros(P, np.int64)
     res = SmartResult(passes=passes, stats=[], taken=[], flag=np.zeros(2, np.int32),
                       best=np.tile(np.array([SMART_MIN_UNIQUE, 0], np.int32), (P, 1)))
@@ -948,26 +995,18 @@ def smart_pairs(store, pairs, kp_off, xy, size, key2, H0, tol, min_pairs, match_
         return res
     idx, d2, out_off = knn if knn is not None else knn3_pairs(store, pairs[live])
     total = int(out_off[-1])
-    nq = np.diff(out_off)
-    stride = max(int(nq.max()), 1)
-    tab = _ratio_tab_size(stride)
+    stride = max(int(np.diff(out_off).max()), 1)
     cap = NB * total
     z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
     d_pairs = torch.from_numpy(np.ascontiguousarray(pairs[live])).to(dev)
     row_off = torch.from_numpy(np.ascontiguousarray(out_off, np.int64)).to(dev)
     Hl = H[torch.from_numpy(live).to(dev)].contiguous() if n != P else H
-    bin_cnt, seg_cnt = z32(n, NB), z32(n, NB)
-    seg_off = torch.zeros(n * NB + 1, dtype=I64, device=dev)
-    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
+    bin_cnt, seg_cnt, seg_off, pts, rows = _bin_tables(n, NB, cap, dev)
     flag = z32(2)
-    work = torch.empty(n * (6 * stride + 2 * tab), dtype=I32, device=dev)
-    slots = torch.empty((n, stride, 2), dtype=I32, device=dev)
+    tab, work, slots, cnt, off, out_rows = _select_buffers(n, stride, total, dev)
     best = torch.from_numpy(np.tile(np.array([SMART_MIN_UNIQUE, 0], np.int32), (n, 1))).to(dev)
-    improved, cnt, fit_status = z32(n), z32(n), z32(n)
+    improved, fit_status = z32(n), z32(n)
     stats = z32(n, NB, 3)
-    off = torch.zeros(n + 1, dtype=I64, device=dev)
-    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
     active = torch.ones(n, dtype=I32, device=dev)
     act_h = np.ones(n, bool)
     while act_h.any() and (max_passes is None or len(res.stats) < max_passes):
@@ -1018,7 +1057,7 @@ BRUTE_STEP_A = 2 * math.pi / (BRUTE_ANGLE_BINS - 1)               # matcher.py:7
 BRUTE_BATCH_BYTES = 4 << 30
 
 
-class BruteResult(object):
+class BruteResult(_StrategyResult):
     """what brute_pairs() returns, device tensors over its n pairs: rows int32 [total, 2] (query
     row, train row) packed back to back, off int64 [n + 1], cnt int32 [n], chosen int32 [n] (the
     taken cell dbin * 21 + abin, -1: none), stats int32 [n, 4] = fitted, unique (-1: the
@@ -1028,10 +1067,6 @@ class BruteResult(object):
     refused).  slots int32 [n, stride, 2]: the same lists in fixed slots (iamx_similarity_pairs'
     layout) when the call was one launch, else None."""
     __slots__ = ('rows', 'off', 'cnt', 'chosen', 'stats', 'fit_cnt', 'bin_cnt', 'flag', 'slots', 'stride')
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw.get(k))
 
 
 def brute_bytes(nq):
@@ -1044,48 +1079,34 @@ def brute_bytes(nq):
     if not len(nq):
         return 0
     stride = max(int(nq.max()), 1)
-    return int(nq.sum()) * (32 + 25 * 9) + len(nq) * (32 * stride + 8 * _ratio_tab_size(stride) + 112 * BRUTE_CELLS)
+    return int(nq.sum()) * (32 + 25 * 9) + len(nq) * (32 * stride + 8 * _tab_size(stride) + 112 * BRUTE_CELLS)
 
 
 def _brute_launch(store, pairs, kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d, hypotheses,
                   seed, flag):
-    """one launch chain over pairs whose images all have at least 2 rows"""
-    dev = require_gpu()
     L = lib()
-    NC, P = BRUTE_CELLS, len(pairs)
-    idx, d2, out_off = knn3_pairs(store, pairs)
-    total = int(out_off[-1])
-    nq = np.diff(out_off)
-    stride = max(int(nq.max()), 1)
-    tab = _ratio_tab_size(stride)
-    cap = 9 * total
-    d_pairs = torch.from_numpy(np.ascontiguousarray(pairs, np.int32)).to(dev)
-    row_off = torch.from_numpy(out_off).to(dev)
-    z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=dev)
-    bin_cnt, seg_cnt = z32(P, NC), z32(P, NC)
-    seg_off = torch.zeros(P * NC + 1, dtype=I64, device=dev)
-    pts = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-    rows = torch.empty((max(cap, 1), 2), dtype=I32, device=dev)
-    check(L.iamx_brute_bins(_ptr(idx), _ptr(d2), _ptr(row_off), _ptr(d_pairs), _ptr(kp_off), _ptr(xy),
-                            _ptr(size), P, float(match_ratio), float(min_pairs), float(step_d),
-                            BRUTE_STEP_A, cap, _ptr(bin_cnt), _ptr(seg_cnt), _ptr(seg_off), _ptr(pts),
-                            _ptr(rows), _ptr(flag), stream_ptr()), 'iamx_brute_bins')
-    # every cell's consensus is iamx_verify_pairs on that cell's points as one segment (the cells the
-    # early exit leaves unreached included: the walk alone is pruned)
-    mask, _model, _best, vstatus = verify_pairs(pts[:cap], seg_off, 'homography',
-                                                float(tol), hypotheses=hypotheses, seed=seed)
-    work = torch.empty(P * (6 * stride + 2 * tab), dtype=I32, device=dev)
-    slots = torch.empty((P, stride, 2), dtype=I32, device=dev)
-    cnt, chosen, stats, fit_cnt = z32(P), z32(P), z32(P, 4), z32(P, NC)
-    off = torch.zeros(P + 1, dtype=I64, device=dev)
-    out_rows = torch.empty((max(total, 1), 2), dtype=I32, device=dev)
-    check(L.iamx_brute_select(_ptr(d_pairs), _ptr(kp_off), _ptr(key2), P, float(min_pairs), _ptr(seg_cnt),
-                              _ptr(seg_off), _ptr(rows), _ptr(mask), _ptr(vstatus), cap, stride, tab,
-                              _ptr(work), _ptr(slots), _ptr(cnt), _ptr(off), _ptr(out_rows), total,
-                              _ptr(chosen), _ptr(stats), _ptr(fit_cnt), _ptr(flag), stream_ptr()),
-          'iamx_brute_select')
-    return BruteResult(rows=out_rows, off=off, cnt=cnt, chosen=chosen, stats=stats, fit_cnt=fit_cnt,
-                       bin_cnt=bin_cnt, flag=flag, slots=slots, stride=stride)
+    NC = BRUTE_CELLS
+
+    def bins(b):
+        check(L.iamx_brute_bins(_ptr(b.idx), _ptr(b.d2), _ptr(b.row_off), _ptr(b.pairs), _ptr(kp_off), _ptr(xy),
+                                _ptr(size), b.P, float(match_ratio), float(min_pairs), float(step_d),
+                                BRUTE_STEP_A, b.cap, _ptr(b.bin_cnt), _ptr(b.seg_cnt), _ptr(b.seg_off),
+                                _ptr(b.pts), _ptr(b.rows), _ptr(flag), stream_ptr()), 'iamx_brute_bins')
+
+    # (the consensus runs on every cell, the cells the early exit leaves unreached included: the walk
+    #  alone is pruned)
+    def select(b):
+        z32 = lambda *shape: torch.zeros(shape, dtype=I32, device=flag.device)
+        chosen, stats, fit_cnt = z32(b.P), z32(b.P, 4), z32(b.P, NC)
+        check(L.iamx_brute_select(_ptr(b.pairs), _ptr(kp_off), _ptr(key2), b.P, float(min_pairs),
+                                  _ptr(b.seg_cnt), _ptr(b.seg_off), _ptr(b.rows), _ptr(b.mask), _ptr(b.vstatus),
+                                  b.cap, b.stride, b.tab, _ptr(b.work), _ptr(b.slots), _ptr(b.cnt), _ptr(b.off),
+                                  _ptr(b.out_rows), b.total, _ptr(chosen), _ptr(stats), _ptr(fit_cnt),
+                                  _ptr(flag), stream_ptr()), 'iamx_brute_select')
+        return dict(chosen=chosen, stats=stats, fit_cnt=fit_cnt, bin_cnt=b.bin_cnt)
+
+    # (a query row is in at most 3 x 3 cells)
+    return _launch_chain(BruteResult, store, pairs, knn3_pairs, NC, 9, tol, hypotheses, seed, flag, bins, select)
 
 
 def brute_pairs(store, pairs, kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d, hypotheses,
@@ -1103,43 +1124,16 @@ def brute_pairs(store, pairs, kp_off, xy, size, key2, tol, min_pairs, match_rati
     NC = BRUTE_CELLS
     if not (float(step_d) > 0.0 and math.isfinite(float(step_d))):
         raise ValueError("brute_pairs: step_d must be positive and finite")
-    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-    P = len(pairs)
-    counts = np.asarray(store.counts, np.int64)
-    nq = counts[pairs[:, 0]] if P else np.zeros(0, np.int64)
-    ok = (nq >= 2) & (counts[pairs[:, 1]] >= 2) if P else np.zeros(0, bool)
-    live = np.nonzero(ok)[0]
-    # launches of at most batch_bytes (a launch's stride is its largest query image)
-    chunks, a = [], 0
-    while a < len(live):
-        b = a + 1
-        while b < len(live) and brute_bytes(nq[live[a:b + 1]]) <= batch_bytes:
-            b += 1
-        chunks.append(live[a:b])
-        a = b
+    pairs, nq, live = _live_pairs(store, pairs)
+    chunks = _split_by_bytes(live, nq, brute_bytes, batch_bytes)
     flag = torch.zeros(2, dtype=I32, device=dev)            # (the launches only ever raise it)
     parts = [_brute_launch(store, pairs[c], kp_off, xy, size, key2, tol, min_pairs, match_ratio, step_d,
                            hypotheses, seed, flag) for c in chunks]
-    if len(parts) == 1 and len(live) == P:
+    if len(parts) == 1 and len(live) == len(pairs):
         return parts[0]
-    # the launches' results side by side (copies and one scan, no arithmetic of their own)
-    cnt = torch.zeros(P, dtype=I32, device=dev)
-    chosen = torch.full((P,), -1, dtype=I32, device=dev)
-    stats = torch.zeros((P, 4), dtype=I32, device=dev)
-    stats[:, 1] = -1
-    fit_cnt = torch.full((P, NC), -1, dtype=I32, device=dev)
-    bin_cnt = torch.zeros((P, NC), dtype=I32, device=dev)
-    rows = []
-    for c, r in zip(chunks, parts):
-        where = torch.from_numpy(c).to(dev)
-        cnt[where], chosen[where], stats[where] = r.cnt, r.chosen, r.stats
-        fit_cnt[where], bin_cnt[where] = r.fit_cnt, r.bin_cnt
-        rows.append(r.rows[:int(r.off[-1])])
-    off = exclusive_scan(cnt) if P else torch.zeros(1, dtype=I64, device=dev)
-    rows = torch.cat(rows) if rows else torch.empty((0, 2), dtype=I32, device=dev)
-    one = len(parts) == 1
-    return BruteResult(rows=rows, off=off, cnt=cnt, chosen=chosen, stats=stats, fit_cnt=fit_cnt,
-                       bin_cnt=bin_cnt, flag=flag, slots=None, stride=parts[0].stride if one else None)
+    return _merge_launches(BruteResult, len(pairs), chunks, parts, flag,
+                           dict(chosen=((), -1), stats=((4,), (0, -1, 0, 0)), fit_cnt=((NC,), -1),
+                                bin_cnt=((NC,), 0)))
 
 
 # --------------------------------------------------------------------------------------

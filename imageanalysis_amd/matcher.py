@@ -497,14 +497,17 @@ def filter_cross_check(idx_pairs1, idx_pairs2):
 # --------------------------------------------------------------------------------------
 # single pair entry points -- matcher.py:203-347
 # --------------------------------------------------------------------------------------
+def _both_have_rows(i1, i2):
+    """the reference's guards (:205-210): both images have descriptors, more than one row each"""
+    if i1.des_list is None or i2.des_list is None:
+        return False
+    return all(len(im.des_list.shape) != 0 and im.des_list.shape[0] > 1 for im in (i1, i2))
+
+
 def raw_matches(i1, i2, k=2):
     """Returns (idx[nq,2] int32, dist[nq,2] float32) -- the content of cv2's list of DMatch
     pairs -- or [] under the reference's guards (:205-210)."""
-    if i1.des_list is None or i2.des_list is None:
-        return []
-    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
-        return []
-    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+    if not _both_have_rows(i1, i2):
         return []
     if the_matcher is None:
         configure()
@@ -598,6 +601,21 @@ def _ratio_flags(flag):
                            "rows, or buffers of the wrong size)" % int(flag[1]))
 
 
+def _single_pair_arena(i1, i2, with_size=False):
+    """the two images of a single-pair entry on the device: -> (store of the two, kp_off, xy, key2,
+    and kp.size beside xy or None)"""
+    import torch
+    from . import kernels
+    dev = _lib.require_gpu()
+    xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
+    store = kernels.DescriptorStore.from_arrays([np.ascontiguousarray(i1.des_list),
+                                                 np.ascontiguousarray(i2.des_list)])
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    size = up(np.concatenate([_kp_size(i1), _kp_size(i2)]).astype(np.float32, copy=False)) if with_size else None
+    return (store, up(np.array([0, len(xy1)], np.int64)), up(np.concatenate([xy1, xy2]).astype(np.float32, copy=False)),
+            up(np.concatenate([kp_key2(xy1), kp_key2(xy2)])), size)
+
+
 def ratio_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None, seed=0):
     """matcher.py:595-694 for one ordered pair -> (idx_pairs, rev_pairs).  review / est_rotation are
     accepted and unused (the reference's review path opens windows).  The RANSAC homography of every
@@ -605,30 +623,19 @@ def ratio_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None
     `seed`), not cv2's."""
     global ratio_last
     ratio_last = None
-    if i1.des_list is None or i2.des_list is None:
-        return [], []
-    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
-        return [], []
-    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+    if not _both_have_rows(i1, i2):
         return [], []
     if the_matcher is None:
         configure()
-    import torch
     from . import kernels
-    dev = _lib.require_gpu()
-    xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
-    store = kernels.DescriptorStore.from_arrays([np.ascontiguousarray(i1.des_list),
-                                                 np.ascontiguousarray(i2.des_list)])
-    xy = np.ascontiguousarray(np.concatenate([xy1, xy2]), np.float32)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    r = kernels.ratio_pairs(store, [[0, 1]], up(np.array([0, len(xy1)], np.int64)), up(xy),
-                            up(np.concatenate([kp_key2(xy1), kp_key2(xy2)])), _ratio_tol(), min_pairs,
+    store, kp_off, xy, key2, _size = _single_pair_arena(i1, i2)
+    r = kernels.ratio_pairs(store, [[0, 1]], kp_off, xy, key2, _ratio_tol(), min_pairs,
                             RATIO_HYPOTHESES if hypotheses is None else hypotheses, seed,
                             cutoffs=RATIO_CUTOFFS)
     _ratio_flags(r.flag.cpu().numpy())
     stats, chosen = r.stats.cpu().numpy()[0], int(r.chosen.cpu().numpy()[0])
     ratio_last = dict(stats=stats, chosen=chosen)
-    _qlog("  raw matches:", len(xy1))
+    _qlog("  raw matches:", len(_kp_xy(i1)))
     for b, (n, fit, unique) in enumerate(stats.tolist()):
         _qlog("bin:", b, "cutoff:", RATIO_CUTOFFS[b], "len:", n)
         if fit >= 0:
@@ -640,26 +647,57 @@ def ratio_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None
     return pairs.tolist(), pairs[:, ::-1].tolist()
 
 
-def _ratio_pairs_per_batch(rows):
-    """ordered pairs per round of the 'bestratio' strategy: as many as RATIO_BATCH_BYTES hold at
-    `rows` descriptors per image (kernels.ratio_bytes), at most PAIRS_PER_BATCH"""
+# --------------------------------------------------------------------------------------
+# a round of the strategies that need no prior: 'bestratio', 'bruteforce'
+# --------------------------------------------------------------------------------------
+def _ratio_round(kernels, dm, store, slots, kp_off, xy, key2, match_ratio):
+    """-> (RatioResult, n_fwd: the members of the widest bin)"""
+    r = kernels.ratio_pairs(store, slots, kp_off, xy, key2, _ratio_tol(), min_pairs,
+                            RATIO_HYPOTHESES, 0, cutoffs=RATIO_CUTOFFS, batch_bytes=1 << 62)
+    return r, r.stats[:, -1, 0]
+
+
+def _brute_round(kernels, dm, store, slots, kp_off, xy, key2, match_ratio):
+    """-> (BruteResult, n_fwd: the members of the taken cell, computed on the device)"""
+    import torch
+    r = kernels.brute_pairs(store, slots, kp_off, xy, dm.sizes(), key2, _brute_tol(), min_pairs,
+                            match_ratio, _brute_step(), BRUTE_HYPOTHESES, 0, batch_bytes=1 << 62)
+    took = r.chosen >= 0
+    return r, torch.where(took, torch.gather(r.bin_cnt, 1, r.chosen.clamp(min=0).long()[:, None])[:, 0],
+                          torch.zeros_like(r.chosen))
+
+
+# per strategy: the round's kernels.*_pairs call (one launch chain: the round was sized by
+# _strategy_pairs_per_batch) with its n_fwd -- what the reference's log calls the filtered matches --,
+# the name of the round's memory bound (read when a round is sized), the bytes of a pair at `rows`
+_STRATEGY_ROUNDS = {
+    'bestratio': (_ratio_round, 'RATIO_BATCH_BYTES',
+                  lambda kernels, rows: kernels.ratio_bytes([rows], len(RATIO_CUTOFFS))),
+    'bruteforce': (_brute_round, 'BRUTE_BATCH_BYTES', lambda kernels, rows: kernels.brute_bytes([rows])),
+}
+
+
+def _strategy_pairs_per_batch(strategy, rows):
+    """ordered pairs per round of `strategy`: as many as its *_BATCH_BYTES hold at `rows` descriptors
+    per image (kernels.ratio_bytes / brute_bytes), at most PAIRS_PER_BATCH"""
     from . import kernels
-    per_pair = max(kernels.ratio_bytes([max(int(rows), 1)], len(RATIO_CUTOFFS)), 1)
-    return int(max(1, min(PAIRS_PER_BATCH, RATIO_BATCH_BYTES // per_pair)))
+    _round, bound, bytes_of = _STRATEGY_ROUNDS[strategy]
+    per_pair = max(bytes_of(kernels, max(int(rows), 1)), 1)
+    return int(max(1, min(PAIRS_PER_BATCH, globals()[bound] // per_pair)))
 
 
-def _launch_ratio_batch(view, rows_i, rows_j, surface):
-    """a round of find_matches(strategy='bestratio'): ENQUEUES, on the current stream, the k=2
-    search of the FORWARD pairs only, the ratio stage (kernels.ratio_pairs) and, with `surface`,
-    the similarity fits; the handle goes to _finish_ratio_arrays().  A pair with an image of at most
-    one row never reaches the device (raw_matches' guards)."""
+def _launch_strategy_batch(view, rows_i, rows_j, surface, strategy, match_ratio):
+    """a round of `strategy`: ENQUEUES, on the current stream, the search of the FORWARD pairs only,
+    the strategy's stage (kernels.ratio_pairs / brute_pairs) and, with `surface`, the similarity
+    fits; the handle goes to _finish_strategy_arrays().  A pair with an image of at most one row
+    never reaches the device (raw_matches' guards)."""
     import torch
     from . import kernels
     from .kernels import _ptr, check, lib, stream_ptr
     dm = the_matcher
     n = len(view)
     live = np.nonzero((np.asarray(rows_i) > 1) & (np.asarray(rows_j) > 1))[0]
-    h = dict(ratio=True, batch=view, n=n, live=live, surface=surface, r=None)
+    h = dict(strategy=strategy, batch=view, n=n, live=live, surface=surface, r=None)
     if len(live):
         slot_of = np.zeros(len(view.image_list), np.int32)
         for u in np.unique(np.concatenate([view.pi[live], view.pj[live]])).tolist():
@@ -670,9 +708,8 @@ def _launch_ratio_batch(view, rows_i, rows_j, surface):
         store = dm.store()
         kp_off, xy, key2 = dm.keypoints()
         slots = np.ascontiguousarray(np.stack([slot_of[view.pi[live]], slot_of[view.pj[live]]], 1), np.int32)
-        # (one launch chain: the round was sized by _ratio_pairs_per_batch)
-        r = h['r'] = kernels.ratio_pairs(store, slots, kp_off, xy, key2, _ratio_tol(), min_pairs,
-                                         RATIO_HYPOTHESES, 0, cutoffs=RATIO_CUTOFFS, batch_bytes=1 << 62)
+        r, h['n_fwd'] = _STRATEGY_ROUNDS[strategy][0](kernels, dm, store, slots, kp_off, xy, key2, match_ratio)
+        h['r'] = r
         if surface:
             dev = xy.device
             d_pairs = torch.from_numpy(slots).to(dev)
@@ -687,9 +724,8 @@ def _launch_ratio_batch(view, rows_i, rows_j, surface):
     return h
 
 
-def _finish_ratio_arrays(h):
-    """-> _RoundResult of a round of the 'bestratio' strategy.  n_fwd: the members of the widest bin
-    (what the reference's log calls the filtered matches), n_rev 0: there is no reverse search; the
+def _finish_strategy_arrays(h):
+    """-> _RoundResult of a round of _launch_strategy_batch.  n_rev 0: there is no reverse search; the
     reverse list is the forward one mirrored, which is _RoundResult's invariant."""
     h['done'].synchronize()
     n, live, r, view = h['n'], h['live'], h['r'], h['batch']
@@ -700,7 +736,7 @@ def _finish_ratio_arrays(h):
     if r is not None:
         _ratio_flags(r.flag.cpu().numpy())
         cnt[live] = r.cnt.cpu().numpy()
-        R.n_fwd[live] = r.stats.cpu().numpy()[:, -1, 0]
+        R.n_fwd[live] = h['n_fwd'].cpu().numpy()
         src = np.ascontiguousarray(r.rows[:int(cnt.sum())].cpu().numpy())
     R.cc, R.quiet = cnt, cnt == 0
     hit = np.nonzero(cnt > 0)[0]
@@ -855,11 +891,7 @@ def smart_pair_matches(i1, i2, review=False, est_rotation=False, hypotheses=None
     smart_last = None
     H0, _ground_m, _reproj = smart_prior(i1, i2, est_rotation)
     match_ratio = matcher_node.getFloat("match_ratio")
-    if i1.des_list is None or i2.des_list is None:
-        return [], []
-    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
-        return [], []
-    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+    if not _both_have_rows(i1, i2):
         return [], []
     if the_matcher is None:
         configure()
@@ -998,32 +1030,20 @@ def bruteforce_pair_matches(i1, i2, review=False, hypotheses=None, seed=0):
     global brute_last
     brute_last = None
     match_ratio = matcher_node.getFloat('match_ratio')
-    if i1.des_list is None or i2.des_list is None:
-        return [], []
-    if len(i1.des_list.shape) == 0 or i1.des_list.shape[0] <= 1:
-        return [], []
-    if len(i2.des_list.shape) == 0 or i2.des_list.shape[0] <= 1:
+    if not _both_have_rows(i1, i2):
         return [], []
     if the_matcher is None:
         configure()
-    import torch
     from . import kernels
-    dev = _lib.require_gpu()
-    xy1, xy2 = _kp_xy(i1), _kp_xy(i2)
-    store = kernels.DescriptorStore.from_arrays([np.ascontiguousarray(i1.des_list),
-                                                 np.ascontiguousarray(i2.des_list)])
-    xy = np.ascontiguousarray(np.concatenate([xy1, xy2]), np.float32)
-    size = np.ascontiguousarray(np.concatenate([_kp_size(i1), _kp_size(i2)]), np.float32)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    r = kernels.brute_pairs(store, [[0, 1]], up(np.array([0, len(xy1)], np.int64)), up(xy), up(size),
-                            up(np.concatenate([kp_key2(xy1), kp_key2(xy2)])), _brute_tol(), min_pairs,
+    store, kp_off, xy, key2, size = _single_pair_arena(i1, i2, with_size=True)
+    r = kernels.brute_pairs(store, [[0, 1]], kp_off, xy, size, key2, _brute_tol(), min_pairs,
                             match_ratio, _brute_step(),
                             BRUTE_HYPOTHESES if hypotheses is None else hypotheses, seed)
     _ratio_flags(r.flag.cpu().numpy())                  # (matcher.py:721: 0.0 / 0.0)
     stats, chosen = r.stats.cpu().numpy()[0], int(r.chosen.cpu().numpy()[0])
     fit_cnt = r.fit_cnt.cpu().numpy()[0]
     brute_last = dict(stats=stats, chosen=chosen, fit_cnt=fit_cnt)
-    _qlog("  raw matches:", len(xy1))
+    _qlog("  raw matches:", len(_kp_xy(i1)))
     _qlog("  collect stats...")
     _brute_log(r.bin_cnt.cpu().numpy()[0], fit_cnt, stats[2])
     pairs = r.rows[:int(r.off[-1])].cpu().numpy()
@@ -1031,87 +1051,6 @@ def bruteforce_pair_matches(i1, i2, review=False, hypotheses=None, seed=0):
         return [], []
     _qlog("  initial matches =", len(pairs))
     return pairs.tolist(), pairs[:, ::-1].tolist()
-
-
-def _brute_pairs_per_batch(rows):
-    """ordered pairs per round of the 'bruteforce' strategy: as many as BRUTE_BATCH_BYTES hold at
-    `rows` descriptors per image (kernels.brute_bytes), at most PAIRS_PER_BATCH"""
-    from . import kernels
-    per_pair = max(kernels.brute_bytes([max(int(rows), 1)]), 1)
-    return int(max(1, min(PAIRS_PER_BATCH, BRUTE_BATCH_BYTES // per_pair)))
-
-
-def _launch_brute_batch(view, rows_i, rows_j, surface, match_ratio):
-    """a round of bruteforce_matches: ENQUEUES, on the current stream, the k=3 search of the FORWARD
-    pairs only, the cells / consensus / walk (kernels.brute_pairs) and, with `surface`, the similarity
-    fits; the handle goes to _finish_brute_arrays().  A pair with an image of at most one row never
-    reaches the device (raw_matches' guards)."""
-    import torch
-    from . import kernels
-    from .kernels import _ptr, check, lib, stream_ptr
-    dm = the_matcher
-    n = len(view)
-    live = np.nonzero((np.asarray(rows_i) > 1) & (np.asarray(rows_j) > 1))[0]
-    h = dict(brute=True, batch=view, n=n, live=live, surface=surface, r=None)
-    if len(live):
-        slot_of = np.zeros(len(view.image_list), np.int32)
-        for u in np.unique(np.concatenate([view.pi[live], view.pj[live]])).tolist():
-            slot_of[u] = dm.slot_of(view.image_list[u])
-        if dm._pending or dm._kp_dev is None or dm._kp_dev[0] != len(dm._counts):
-            # (the arenas are about to be rebuilt: an earlier traditional round's side stream may read them)
-            torch.cuda.current_stream().wait_stream(_side_stream())
-        store = dm.store()
-        kp_off, xy, key2 = dm.keypoints()
-        slots = np.ascontiguousarray(np.stack([slot_of[view.pi[live]], slot_of[view.pj[live]]], 1), np.int32)
-        # (one launch chain: the round was sized by _brute_pairs_per_batch)
-        r = h['r'] = kernels.brute_pairs(store, slots, kp_off, xy, dm.sizes(), key2, _brute_tol(), min_pairs,
-                                         match_ratio, _brute_step(), BRUTE_HYPOTHESES, 0, batch_bytes=1 << 62)
-        # the members of the taken cell: what the reference's log calls the filtered matches
-        took = r.chosen >= 0
-        h['n_fwd'] = torch.where(took, torch.gather(r.bin_cnt, 1, r.chosen.clamp(min=0).long()[:, None])[:, 0],
-                                 torch.zeros_like(r.chosen))
-        if surface:
-            dev = xy.device
-            d_pairs = torch.from_numpy(slots).to(dev)
-            h['aff'] = torch.empty((len(live), 2, 6), dtype=torch.float64, device=dev)
-            h['aff_ok'] = torch.empty((len(live), 2), dtype=torch.int32, device=dev)
-            check(lib().iamx_similarity_pairs(_ptr(d_pairs), _ptr(kp_off), _ptr(xy), _ptr(r.cnt),
-                                              _ptr(r.slots), len(live), r.stride, _ptr(h['aff']),
-                                              _ptr(h['aff_ok']), stream_ptr()), 'iamx_similarity_pairs')
-            h['tables'] = (d_pairs, kp_off, xy, key2)
-    h['done'] = torch.cuda.Event()
-    h['done'].record()
-    return h
-
-
-def _finish_brute_arrays(h):
-    """-> _RoundResult of a round of the 'bruteforce' strategy.  n_fwd: the members of the taken cell,
-    n_rev 0: there is no reverse search; the reverse list is the forward one mirrored, which is
-    _RoundResult's invariant."""
-    h['done'].synchronize()
-    n, live, r, view = h['n'], h['live'], h['r'], h['batch']
-    R = _RoundResult(n)
-    cnt = np.zeros(n, np.int64)
-    R.n_fwd, R.n_rev = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    src = np.zeros((0, 2), np.int32)
-    if r is not None:
-        _ratio_flags(r.flag.cpu().numpy())
-        cnt[live] = r.cnt.cpu().numpy()
-        R.n_fwd[live] = h['n_fwd'].cpu().numpy()
-        src = np.ascontiguousarray(r.rows[:int(cnt.sum())].cpu().numpy())
-    R.cc, R.quiet = cnt, cnt == 0
-    hit = np.nonzero(cnt > 0)[0]
-    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-    R.hit_rows, R.lo, R.hi = hit.astype(np.int64), off[hit], off[hit] + cnt[hit]
-    if len(hit):
-        R.fwd_all, R.rev_all = src, np.ascontiguousarray(src[:, ::-1])
-    R.fit = bool(h['surface'])
-    if R.fit:
-        where = np.searchsorted(live, hit)                   # (a pair with matches is a live one)
-        aff = h['aff'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2, 6))
-        aff_ok = h['aff_ok'].cpu().numpy()[where] if len(hit) else np.zeros((0, 2), np.int32)
-        _round_fits(R, view, aff, aff_ok)
-    return R
 
 
 def bruteforce_matches(proj, K, sort=False):
@@ -2331,11 +2270,8 @@ class _MatchRun(object):
                     first = image_list[int(wi[rank])]
                     _ensure_features(first)
                     known = [_rows_of(first)]
-                if self.strategy == 'bruteforce':
-                    ppb = _brute_pairs_per_batch(max(known))
-                else:
-                    ppb = _pairs_per_batch(1.25 * max(known)) if self.strategy == 'traditional' else \
-                        _ratio_pairs_per_batch(max(known))
+                ppb = _pairs_per_batch(1.25 * max(known)) if self.strategy == 'traditional' else \
+                    _strategy_pairs_per_batch(self.strategy, max(known))
         except (Exception, SystemExit) as exc:
             if ws == 1:
                 raise
@@ -2434,12 +2370,10 @@ class _MatchRun(object):
             if rows[k] <= 1 and self.strategy == 'traditional':
                 # raw_matches() returns [] and basic_pair_matches divides by len([]) (:232)
                 raise ZeroDivisionError("float division by zero")
-        if self.strategy == 'bruteforce':
-            # (bruteforce_pair_matches returns [], [] under raw_matches' guards, as below)
-            handle = _launch_brute_batch(view, rows[view.pi], rows[view.pj], bool(self.surface), self.match_ratio)
-        elif self.strategy == 'bestratio':
-            # (ratio_pair_matches returns [], [] under raw_matches' guards: such a pair ends with nothing)
-            handle = _launch_ratio_batch(view, rows[view.pi], rows[view.pj], bool(self.surface))
+        if self.strategy in _STRATEGY_ROUNDS:
+            # (the single-pair entries return [], [] under raw_matches' guards: such a pair ends with nothing)
+            handle = _launch_strategy_batch(view, rows[view.pi], rows[view.pj], bool(self.surface),
+                                            self.strategy, self.match_ratio)
         else:
             handle = _launch_batch(view, self.match_ratio, surface='fit' if self.surface else False)
         return view, sl, handle
@@ -2447,10 +2381,7 @@ class _MatchRun(object):
     def finish_round(self, launched):
         """-> _Part: the round's pairs of this rank and their results as arrays"""
         view, sl, handle = launched
-        if isinstance(handle, dict) and handle.get('brute'):
-            R = _finish_brute_arrays(handle)
-            return _Part(sl, view.pi, view.pj, self.wd[sl], self.rows[view.pi], self.rows[view.pj], R)
-        R = _finish_ratio_arrays(handle) if isinstance(handle, dict) and handle.get('ratio') else \
+        R = _finish_strategy_arrays(handle) if isinstance(handle, dict) and handle.get('strategy') else \
             _finish_batch_arrays(handle)
         return _Part(sl, view.pi, view.pj, self.wd[sl], self.rows[view.pi], self.rows[view.pj], R)
 

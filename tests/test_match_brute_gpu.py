@@ -494,7 +494,7 @@ def test_bruteforce_matches_equals_the_reference_loop(fresh_matcher, sort, round
     if rounds == 'many':
         rows = max(len(x) for x in g['xy'])
         monkeypatch.setattr(matcher, 'BRUTE_BATCH_BYTES', 7 * kernels.brute_bytes([rows]) + 1)
-        assert matcher._brute_pairs_per_batch(rows) == 7
+        assert matcher._strategy_pairs_per_batch('bruteforce', rows) == 7
     for call in range(2):
         matcher.bruteforce_matches(proj, None, sort=sort)
         loop.check_against(g, s['runs'][sort], call, proj)

@@ -30,15 +30,15 @@ def _device_ransac(hypotheses, seed):
     return run
 
 
-def _abi(top2, images, slots, tol, min_pairs, hypotheses=256, seed=0):
+def _abi(top2, images, slots, tol, min_pairs, hypotheses=256, seed=0, cutoffs=rr.CUTOFFS):
     """iamx_ratio_bins -> iamx_verify_pairs -> iamx_ratio_select through the C ABI.  top2: per pair
-    (idx [n, 2], d2 [n, 2]); images: per slot xy float32 [m, 2]; slots: per pair (query, train).
-    -> (per pair dict(fwd, chosen, stats, bin_cnt), flag [2])"""
+    (idx [n, 2], d2 [n, 2]); images: per slot xy float32 [m, 2]; slots: per pair (query, train);
+    cutoffs: the launch's bins.  -> (per pair dict(fwd, chosen, stats, bin_cnt), flag [2])"""
     import torch
     from imageanalysis_amd import _lib, matcher
     dev = torch.device('cuda', 0)
     L = _lib.lib()
-    P = len(top2)
+    P, NB = len(top2), len(cutoffs)
     n = np.array([len(t[0]) for t in top2], np.int64)
     row_off = np.zeros(P + 1, np.int64)
     np.cumsum(n, out=row_off[1:])
@@ -57,7 +57,7 @@ def _abi(top2, images, slots, tol, min_pairs, hypotheses=256, seed=0):
         d_idx = d_d2 = torch.zeros((1, 2), dtype=torch.int32, device=dev)
     d_row, d_pairs, d_kp, d_xy = up(row_off, np.int64), up(slots, np.int32), up(kp_off, np.int64), up(xy, np.float32)
     d_key = up(matcher.kp_key2(xy), np.int32)
-    cut = np.asarray(rr.CUTOFFS, np.float64)
+    cut = np.asarray(cutoffs, np.float64)
     poison = lambda count, dt=torch.int32: torch.full((count + GUARD,), POISON if dt != torch.uint8 else 0xAB,
                                                       dtype=dt, device=dev)
     bin_cnt, seg_cnt, seg_off = poison(P * NB), poison(P * NB), poison(P * NB + 1, torch.int64)
@@ -176,6 +176,25 @@ def test_query_row_edges(n):
         assert (np.diff(want['stats'][:, 0]) > 0).any()
     else:
         assert want['chosen'] == -1 and (want['stats'][:, 1] == -1).all()
+
+
+@pytest.mark.parametrize('nb', (1, 3))
+def test_fewer_bins_than_the_most(nb):
+    """n_bins below the 8 the bin kernels and the walk are compiled for: the tables are [n_pairs][nb],
+    the bins past nb hold no row and the walk stops at nb.  At 257 rows the widest bin of the launch wins
+    with a list; at 65 rows one cutoff takes no bin (restated with rr.host_ransac(256, 0): 68 and 105
+    unique at 257 rows, none and 25 at 65)"""
+    cutoffs = rr.CUTOFFS[:nb]
+    for n in (65, 257):
+        idx, d2, xy1, xy2 = e = _edge(n, 500 + n, twins=min(3, n // 8))
+        (got,), flag = _abi([e[:2]], [xy1, xy2], [(0, 1)], rr.TOL, 4, cutoffs=cutoffs)
+        assert flag.tolist() == [0, 0]
+        want = rr.ratio_pair(idx, d2, xy1, xy2, len(xy1), len(xy2), rr.TOL, 4, _device_ransac(256, 0),
+                             cutoffs=cutoffs)
+        assert got['stats'].shape == want['stats'].shape == (nb, 3)
+        _same(got, want, (nb, n))
+        if n == 257:
+            assert want['chosen'] == nb - 1 and len(want['fwd']) > rr.MIN_UNIQUE
 
 
 @pytest.mark.parametrize('n', (2001, 4097))

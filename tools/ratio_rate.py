@@ -128,7 +128,7 @@ def stages():
             t_ver[hyp], (mask, _m, _b, vstatus) = timed(
                 lambda: kernels.verify_pairs(pts, seg_off, 'homography', float(TOL), hypotheses=hyp, seed=0))
             masks[hyp] = (mask, vstatus)
-        stride, tab = n, kernels._ratio_tab_size(n)
+        stride, tab = n, kernels._tab_size(n)
         work = torch.empty(n_p * (6 * stride + 2 * tab), dtype=torch.int32, device=dev)
         slots = torch.empty((n_p, stride, 2), dtype=torch.int32, device=dev)
         cnt, chosen, stats = z32(n_p), z32(n_p), z32(n_p, nb, 3)

@@ -136,7 +136,7 @@ def stages():
     # ---- the pass loop, stage by stage
     _t, idx, d2 = res[3]
     cap, stride = NB * total, n
-    tab = kernels._ratio_tab_size(stride)
+    tab = kernels._tab_size(stride)
     a = np.radians(3.0)
     c, s, cx, cy = np.cos(a), np.sin(a), W_PX / 2.0, H_PX / 2.0
     turn = np.array([[c, -s, cx - c * cx + s * cy], [s, c, cy - s * cx - c * cy], [0, 0, 1.0]])
